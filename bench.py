@@ -12,9 +12,19 @@ One "step" = one full Gauss-Newton iteration of the hot path: linearise every fa
 assemble the block-tridiagonal normal equations, solve, retract, re-evaluate the error -- exactly what
 matlab/PlazaPose2.m:224-226 brackets with tic/toc around optimizer.iterate().  Inputs are resident in HBM before
 the timed region.  With N > 1 the ONE chain of N x 1e5 states is cut into N contiguous segments (weak scaling) and
-every iteration performs one RCCL all-gather of the 3.6 KB interface records (gpslam_amd/sharded.py).  Next to that
-headline every multi-rank line carries `strong_scaling`: north_star's ONE chain of 1e6 states cut N ways (--strong-states),
-measured after the timed region.  Rank 0 prints ONE JSON line.
+every iteration performs one RCCL all-gather of the 3.6 KB interface records (gpslam_amd/sharded.py).  Rank 0 prints ONE
+JSON line.
+
+A plain run sets up, warms up, times the --steps iterations and prints the headline (metric, value, unit, ms_per_step,
+dtype, ...) and nothing else.  --full adds everything measured beside it, all after the timed region: the convergence runs,
+the per-kernel times and the roofline, the CPU baselines (--no-cpu-baseline skips them), the extras of a one-GPU run
+(--no-extras skips them), and on more than one rank the collective, the projected sharded step and `strong_scaling`:
+north_star's ONE chain of 1e6 states cut N ways (--strong-states).
+
+  ... --dump-outputs DIR    after the timed steps: the states they produced (DIR/pose.npy, DIR/vel.npy: the ranks'
+                            segments joined, in state order; DIR/state_index.npy names the states, a fixed seeded sample
+                            where the whole chain would exceed 64 MB) and, on one GPU, the statistics of the last step
+                            (DIR/stats.npy: error before, error after, |delta|_inf); float64 throughout
 """
 import argparse
 import json
@@ -67,6 +77,25 @@ def pmc_traffic(which, n_states):
 def frac_or_none(bytes_, ms):
     """bytes / time as a fraction of the HBM peak, or None without a byte count"""
     return (bytes_ / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (bytes_ and ms > 0) else None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, pose, vel, stats):
+    """--dump-outputs: the states after the timed steps (and the statistics of the last step) as float64 .npy files, so that
+    two builds can be compared output for output.  A chain too large for DUMP_LIMIT_BYTES keeps a fixed, seeded sample of
+    its states, the same for every run of the same size; state_index.npy names them."""
+    os.makedirs(dirname, exist_ok=True)
+    n = pose.shape[0]
+    per_state = (pose.shape[1] + vel.shape[1] + 1) * 8          # + 1: the state's entry in state_index.npy
+    keep = min(n, (DUMP_LIMIT_BYTES - 4096) // per_state)      # (4096: the .npy headers and stats.npy)
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    arrays = {"pose": pose[idx], "vel": vel[idx], "state_index": idx}
+    if stats is not None:
+        arrays["stats"] = np.array([stats.error_before, stats.error_after, stats.delta_inf_norm])
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(problem, iters=3, threads=1):
@@ -359,8 +388,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--states", type=int, default=100000, help="states per GPU (BASELINE config 3: 100k poses)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the beyond-the-headline measurements (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too (convergence, roofline, baselines, extras); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (the states, the last step's statistics) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the beyond-the-headline measurements (profiling runs)")
     ap.add_argument("--total-states", type=int, default=0,
                     help="strong scaling: ONE chain of this many states cut into --gpus segments (the headline then says \"scaling\": \"strong\")")
     ap.add_argument("--strong-states", type=int, default=1000000,
@@ -443,7 +476,7 @@ def main():
                 return st.error_after, st.delta_inf_norm
 
             def run(k):
-                solver.run_gn(k)
+                return solver.run_gn(k)[0]
             w.update(problem=problem, solver=solver, sv=None, send=None, recv=None, lp=None)
         else:
             problem = S.pose3_chain(total)                  # ONE chain, cut into `world` contiguous segments
@@ -495,13 +528,14 @@ def main():
     problem, solver, sv, send, recv, lp = W["problem"], W["solver"], W["sv"], W["send"], W["recv"], W["lp"]
     reset, one_with_stats, run = W["reset"], W["one_with_stats"], W["run"]
 
-    # convergence run (outside the contract clock): iterations until |delta|_inf < 1e-6
+    # --full: convergence run (outside the contract clock): iterations until |delta|_inf < 1e-6
     conv_iters, conv_delta, final_error = 0, float("inf"), float("nan")
-    for _ in range(25):
-        final_error, conv_delta = one_with_stats()
-        conv_iters += 1
-        if conv_delta < 1e-6:
-            break
+    if args.full:
+        for _ in range(25):
+            final_error, conv_delta = one_with_stats()
+            conv_iters += 1
+            if conv_delta < 1e-6:
+                break
 
     # timed region: restart from the initial values so the steps do real Newton work
     reset()
@@ -510,7 +544,7 @@ def main():
     reset()
     barrier()
     t0 = time.perf_counter()
-    run(args.steps)
+    last_stats = run(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
     if dist is not None:
@@ -518,23 +552,35 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # a TIMED convergence run (outside the contract clock; VERDICT r2: the headline's states-to-convergence figure was derived
-    # from ms_per_step): from the initial values, the iterations the convergence run above needed, wall clock between barriers
-    reset()
-    barrier()
-    tc0 = time.perf_counter()
-    run(conv_iters)
-    barrier()
-    conv_seconds = time.perf_counter() - tc0
-    if dist is not None:
-        t = torch.tensor([conv_seconds], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        conv_seconds = float(t.item())
+    # what the timed steps computed, before anything below moves the states again; the ranks' segments are contiguous, in rank order
+    if args.dump_outputs:
+        pose_out, vel_out = solver.get_states()
+        if dist is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, (pose_out, vel_out))
+            pose_out, vel_out = np.concatenate([pp for pp, _ in parts]), np.concatenate([vv for _, vv in parts])
+        if rank == 0:
+            dump_outputs(args.dump_outputs, pose_out, vel_out, last_stats)
 
-    # N > 1: what the one data-path collective of an iteration costs (all ranks take part; outside the contract clock):
+    # --full: a TIMED convergence run (outside the contract clock; VERDICT r2: the headline's states-to-convergence figure was
+    # derived from ms_per_step): from the initial values, the iterations the convergence run above needed, wall clock between barriers
+    conv_seconds = None
+    if args.full:
+        reset()
+        barrier()
+        tc0 = time.perf_counter()
+        run(conv_iters)
+        barrier()
+        conv_seconds = time.perf_counter() - tc0
+        if dist is not None:
+            t = torch.tensor([conv_seconds], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            conv_seconds = float(t.item())
+
+    # N > 1 (--full): what the one data-path collective of an iteration costs (all ranks take part; outside the contract clock):
     # device time of `reps` all-gathers of the 3.6 KB interface records between events on the stream RCCL is ordered against
     collective_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         reps = 50
         for _ in range(5):
             sv.exchange()
@@ -556,12 +602,12 @@ def main():
         dist.all_reduce(tc, op=dist.ReduceOp.MAX)      # (every rank executes exactly the same sequence of collectives)
         collective_ms = float(tc.item())
 
-    # N > 1: the prediction this run is checked against -- what THIS rank's share of the sharded code path
+    # N > 1 (--full): the prediction this run is checked against -- what THIS rank's share of the sharded code path
     # costs per iteration when the all-gather is replaced by a device copy of its own record into every slot (the figure
     # `extras.projected_sharded_1e6_pose3` of the one-GPU run, for this run's segment); measured on every rank after the timed
     # region, reported as the maximum over the ranks
     projected_ms = None
-    if world > 1 and not model:
+    if world > 1 and not model and args.full:
         # (never allowed to cost the run its line: this branch has only ever executed on the gloo model and on one GPU; a failure
         #  of the local measurement is reported as such, and every rank still takes part in the one collective below)
         local_ms, projected_err = float("nan"), None
@@ -589,11 +635,11 @@ def main():
         dist.all_reduce(tp, op=dist.ReduceOp.MAX)
         projected_ms = float(tp.item()) if projected_err is None and float(tp.item()) > 0 else None
 
-    # N > 1 (and the one-GPU run unless --no-extras): north_star's STRONG-scaling point -- ONE chain of --strong-states (1e6)
+    # --full, N > 1 (and the one-GPU run unless --no-extras): north_star's STRONG-scaling point -- ONE chain of --strong-states (1e6)
     # Pose3 states cut `world` ways: iterations to |delta|_inf < 1e-6, wall clock of exactly that many iterations from the
     # initial values, and ms per iteration over `steps` iterations; every rank takes part, all of it outside the contract clock.
     strong_block = None
-    want_strong = args.strong_states > 0 and not strong and (world > 1 or not (args.no_extras or model))
+    want_strong = args.full and args.strong_states > 0 and not strong and (world > 1 or not (args.no_extras or model))
     if want_strong:
         Ws = setup(args.strong_states)            # (the headline's handle stays: the roofline probes below use it)
         it_s, dl_s = 0, float("inf")
@@ -623,22 +669,55 @@ def main():
             Ws["solver"].close()
         del Ws
 
+    ms_per_step = elapsed / args.steps * 1e3
     if rank == 0 and model:
         # the control-flow run of the CPU test: the line a real run prints, without what only a GPU can measure
-        print(json.dumps({
+        line = {
             "metric": "GN state-iterations/sec (states x Gauss-Newton iters/sec), Pose3 GP chain",
             "value": total_states * args.steps / elapsed, "unit": "state-iterations/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if strong else "weak",
             "vs_baseline": None, "dtype": "f64", "data": "model",
             "config": {"workload": "control-flow test: %d poses per rank, numpy + oracle model of the two phases over gloo" % N,
                        "states_per_gpu": N, "total_states": total_states,
                        "parallelism": "1 chain in %d contiguous segments, 1 all-gather of interface records per iteration" % world},
-            "ranks": world, "rccl_version": None, "iters_to_convergence": conv_iters, "delta_inf_at_convergence": conv_delta,
-            "final_error": final_error, "seconds_to_convergence": conv_seconds,
-            "collective": {"kind": "all_gather of the interface records (gloo)", "bytes_per_rank": int(send.numel() * send.element_size()),
-                           "ms_per_iteration": collective_ms, "share_of_step": collective_ms / (elapsed / args.steps * 1e3)},
-            "strong_scaling": strong_block, "roofline": None, "cpu_baseline": None}))
+            "ranks": world, "rccl_version": None}
+        if args.full:
+            line.update({
+                "iters_to_convergence": conv_iters, "delta_inf_at_convergence": conv_delta,
+                "final_error": final_error, "seconds_to_convergence": conv_seconds,
+                "collective": {"kind": "all_gather of the interface records (gloo)", "bytes_per_rank": int(send.numel() * send.element_size()),
+                               "ms_per_iteration": collective_ms, "share_of_step": collective_ms / ms_per_step},
+                "strong_scaling": strong_block, "roofline": None, "cpu_baseline": None})
+        print(json.dumps(line))
     if rank == 0 and not model:
+        try:
+            rccl = ".".join(str(v) for v in torch.cuda.nccl.version())
+        except Exception:
+            rccl = None
+        head = {
+            "metric": "GN state-iterations/sec (states x Gauss-Newton iters/sec), Pose3 GP chain",
+            "value": total_states * args.steps / elapsed,
+            "unit": "state-iterations/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "strong" if strong else "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": "BASELINE configs[2]: Pose3/SE(3) GP prior + synthetic odometry, "
+                                   "%d poses per GPU, fp64, Gauss-Newton" % N,
+                       "states_per_gpu": N, "total_states": total_states,
+                       "factors": "N-1 GaussianProcessPriorPose3 + N-1 BetweenFactor<Pose3> + 1 PriorFactor<Pose3>",
+                       "parallelism": "1 chain in %d contiguous segments, 1 all-gather of interface records per "
+                                      "iteration" % world if world > 1 else "single GPU"},
+            "ranks": world, "rccl_version": rccl,
+            "gn_iters_per_sec": args.steps / elapsed}
+        if not args.full:
+            print(json.dumps(head))
+    if rank == 0 and not model and args.full:
         # per-kernel device time (hipEvents on the handle's stream) of the per-GPU workload, for the roofline
         if world == 1:
             probe, pproblem = solver, problem
@@ -674,32 +753,8 @@ def main():
         probe.set_level0_stamps(False)
         if dom == 2 and l0_in_iter > 0:
             achieved = alg[dom] / (l0_in_iter * 1e-3) / 1e9
-        ms_per_step = elapsed / args.steps * 1e3
-        try:
-            rccl = ".".join(str(v) for v in torch.cuda.nccl.version())
-        except Exception:
-            rccl = None
         out = {
-            "metric": "GN state-iterations/sec (states x Gauss-Newton iters/sec), Pose3 GP chain",
-            "value": total_states * args.steps / elapsed,
-            "unit": "state-iterations/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2]: Pose3/SE(3) GP prior + synthetic odometry, "
-                                   "%d poses per GPU, fp64, Gauss-Newton" % N,
-                       "states_per_gpu": N, "total_states": total_states,
-                       "factors": "N-1 GaussianProcessPriorPose3 + N-1 BetweenFactor<Pose3> + 1 PriorFactor<Pose3>",
-                       "parallelism": "1 chain in %d contiguous segments, 1 all-gather of interface records per "
-                                      "iteration" % world if world > 1 else "single GPU"},
-            "ranks": world, "rccl_version": rccl,
-            "gn_iters_per_sec": args.steps / elapsed,
+            **head,
             "iters_to_convergence": conv_iters,
             "delta_inf_at_convergence": conv_delta,
             "final_error": final_error,

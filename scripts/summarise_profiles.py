@@ -28,7 +28,7 @@ def find(pattern):
     return g[0] if g else None
 
 
-out = ["# %s -- rocprofv3 --kernel-trace --stats of %s" % (name, ("`%s`" % what) if what else "`python bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline`" if states == 100000 else "`python scripts/profile_iter.py %d` (Pose3 chain of %d states, 2 + 5 Gauss-Newton iterations)" % (states, states)), ""]
+out = ["# %s -- rocprofv3 --kernel-trace --stats of %s" % (name, ("`%s`" % what) if what else "`python bench.py --gpus 1 --steps 20 --warmup 3 --full --no-cpu-baseline`" if states == 100000 else "`python scripts/profile_iter.py %d` (Pose3 chain of %d states, 2 + 5 Gauss-Newton iterations)" % (states, states)), ""]
 kt = find("trace/**/t_kernel_trace.csv")
 per = collections.OrderedDict()
 if kt:

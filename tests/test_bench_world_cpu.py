@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +22,7 @@ def _env():
     return env
 
 
-def _launch(world, gpus, states=20, steps=2, warmup=1, timeout=600, extra=("--strong-states", "0")):
+def _launch(world, gpus, states=20, steps=2, warmup=1, timeout=600, extra=("--full", "--strong-states", "0")):
     port = 29600 + (os.getpid() % 1500) + world
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", str(warmup),
@@ -57,10 +58,10 @@ def test_world_size_must_equal_gpus():
 
 def test_bench_starts_its_own_ranks_without_a_launcher():
     """`python bench.py --gpus 2` with no torchrun in front and no WORLD_SIZE in the environment re-executes
-    itself under torch.distributed.run and prints the one line; the multi-rank line carries the strong-scaling block (ONE
+    itself under torch.distributed.run and prints the one line; with --full the multi-rank line carries the strong-scaling block (ONE
     chain of --strong-states states cut two ways) beside the weak headline."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--states", "20",
-           "--strong-states", "60"]
+           "--full", "--strong-states", "60"]
     d = _line(subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=_env(), cwd=ROOT))
     assert d["n_gpus"] == 2 and d["ranks"] == 2 and d["scaling"] == "weak" and d["config"]["total_states"] == 40
     ss = d["strong_scaling"]
@@ -73,8 +74,29 @@ def test_bench_starts_its_own_ranks_without_a_launcher():
 def test_total_states_makes_the_headline_a_strong_scaling_line():
     """--total-states T: ONE chain of T states cut `world` ways is the headline itself ("scaling": "strong"); an odd T leaves
     segments that differ by one state."""
-    d = _line(_launch(2, 2, extra=("--total-states", "41")))
+    d = _line(_launch(2, 2, extra=("--full", "--total-states", "41")))
     assert d["scaling"] == "strong" and d["config"]["total_states"] == 41 and d["config"]["states_per_gpu"] == 21
     assert d["strong_scaling"] is None
     assert d["iters_to_convergence"] <= 8 and d["delta_inf_at_convergence"] < 1e-6
     assert abs(d["value"] - 41 * d["steps"] / (d["ms_per_step"] * 1e-3 * d["steps"])) <= 1e-6 * d["value"]
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line is the headline alone; --dump-outputs writes the states the timed steps left, the ranks' segments
+    joined in state order: the chain after `steps` Gauss-Newton iterations from the initial values, as the oracle computes it."""
+    from gpslam_amd import synthetic as S
+    from oracle import oracle as O
+    d = _line(_launch(2, 2, steps=3, extra=("--dump-outputs", str(tmp_path))))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dtype"] == "f64"
+    assert "iters_to_convergence" not in d and "collective" not in d and "strong_scaling" not in d
+    pose, vel = np.load(tmp_path / "pose.npy"), np.load(tmp_path / "vel.npy")
+    assert pose.dtype == vel.dtype == np.float64 and pose.shape == (40, 12) and vel.shape == (40, 6)
+    assert np.array_equal(np.load(tmp_path / "state_index.npy"), np.arange(40))
+    orc = S.apply(S.pose3_chain(40), O.Chain(O.POSE3))
+    for _ in range(3):
+        assert orc.iterate_gn()[0] == 0
+    p0, v0 = orc.get_states()
+    assert np.abs(pose - p0).max() <= 1e-9 * max(1.0, np.abs(p0).max())
+    assert np.abs(vel - v0).max() <= 1e-9 * max(1.0, np.abs(v0).max())

@@ -71,11 +71,8 @@ struct gpslam_hip_handle {
   hipStream_t aux_stream = nullptr;   // side stream for the light factor kernels (launch_factors)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // the fused level-0 launch of a timed iteration carries its own start / stop events (hipExtLaunchKernelGGL: the dispatch's own
-  // time stamps, what rocprofv3's kernel trace reads) -- events recorded AROUND a launch add their marker packets to it (7 us of 149)
-  hipEvent_t ev_l0a = nullptr, ev_l0b = nullptr;
-  bool l0_ext = false;        // ... and this iteration's launch took them
-  bool l0_stamps = false;     // gpslam_hip_set_level0_stamps: timed iterations do so (off: events around the launch, as in rounds 1-5)
+  hipEvent_t ev_l0a = nullptr, ev_l0b = nullptr;   // the fused level-0 launch's own stamps in a timed iteration (LaunchMode::l0_events)
+  bool l0_stamps = false;     // gpslam_hip_set_level0_stamps: timed iterations use them (off: events around the launch, as in rounds 1-5)
   double Qc[36], U[36];
   std::vector<double> h_lmk;
   DevBuf pose, vel, lmk, pose_bak, vel_bak, lmk_bak;
@@ -122,12 +119,10 @@ struct gpslam_hip_handle {
   DevBuf lm_gL;             // undamped landmark gradient of the segmented path (the dense path keeps it behind lm_S)
   bool upper_ok = false;    // the levels above level 0 run as LDS-resident cyclic reduction (upper.hip)
   bool fuse_ok = false;     // k_fused_level0 applies to this graph (compile())
-  bool fuse_now = false;    // ... and the iteration being enqueued uses it (enqueue_gn)
   bool struct_ok = false;   // the GP priors may reach k_fused_level0 as structured records (GpArgs::gps) instead of rows
-  bool struct_now = false;  // ... and the linearisation / elimination being enqueued do so
   // block size 6 (SE(2), SO(3), 3-D linear chains): the GP priors as 32-double records (kGp3*) that k_assemble_ghost and
-  // k_fused_level0<1, double, 6> decode; rows3: the launch being enqueued needs real rows after all (gpslam_hip_get_rows)
-  bool struct3_ok = false, rows3 = false;
+  // k_fused_level0<1, double, 6> decode
+  bool struct3_ok = false;
   bool pure6 = false;       // block size 6: nothing but d = 3 GP records in the full-width row table (fused level 0 at every size)
   bool odd_many = false;    // SE(3) records: more other full-width rows than k_fused_level0<2> fetches without a ring (-> <3>)
   DevBuf gps, gpidx, dU, gsave2;
@@ -148,8 +143,6 @@ struct gpslam_hip_handle {
   // Gauss-Newton runs (gpslam_hip_run_gn): the retraction of an iteration folded into the next iteration's K1 (kernels.hpp: PendUpd).
   // pend_ok: compile() found the graph eligible;  pend_upd: a solve's update sits in the level-0 solution array, not yet applied
   bool pend_ok = false, pend_upd = false;
-  bool keep_flag = false;   // inside gpslam_hip_run_gn on a sharded handle / split piece: phase 1 leaves the non-positive-pivot flag alone
-  bool gsave_now = false;   // the fused kernel being enqueued stores the gradient (Levenberg-Marquardt trials)
   int U_version = 0, dU_version = -1;   // set_qc after compile(): the device copy of U is refreshed before its next use
   bool compiled = false;
   double last_ms[5] = {0, 0, 0, 0, 0};
@@ -157,17 +150,30 @@ struct gpslam_hip_handle {
   // linearisation are summed by an extra workgroup of k_retract, the |delta|_inf partial maxima of the retraction by an
   // extra workgroup of the NEXT iteration's k_lin -- two launches (+ their gaps) less per iteration, same values, same order
   DevBuf partial2;            // the retraction's per-block maxima (its own buffer: the linearisation reuses `partial`)
-  bool defer_err = false, defer_dmax = false;   // what the call being enqueued may defer (enqueue_gn)
   int pend_err_n = 0, pend_err_slot = 0;        // pending: error partials in `partial`
   int pend_dmax_n = 0, pend_dmax_slot = 0;      // pending: maxima in `partial2`
-  bool time_l0 = false;       // a timed iteration also stamps the end of the level-0 forward launch (ev[5])
-  double l0_ms = 0.0;         // ... accumulated over the last timed run: the dominant kernel INSIDE an iteration
+  double l0_ms = 0.0;         // the level-0 forward launch, accumulated over the last timed run: the dominant kernel INSIDE an iteration
   double ph_lambda = 0.0;
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch
   int dbg_trace_waves = 0;
 #endif
+};
+
+// What the launches of one call do: each entry point builds the mode it means and hands it to the launch helpers.
+// LaunchMode{}: row tables (d = 3 records where the graph has them), level 0 unfused, every reduction at once, untimed.
+struct LaunchMode {
+  bool fused = false;         // level 0 runs as k_fused_level0 (the assembly inside the elimination)
+  bool se3_rec = false;       // the SE(3) GP priors travel as structured records (linearisation -> k_fused_level0)
+  bool d3_rows = false;       // the d = 3 GP priors as rows after all, not as kGp3* records (gpslam_hip_get_rows: the table is wanted)
+  bool gsave = false;         // k_fused_level0 stores the gradient (Levenberg-Marquardt trials)
+  bool defer_error = false;   // the linearisation leaves its error partial sums to the extra workgroup of this iteration's k_retract
+  bool defer_maxima = false;  // the retraction leaves its |delta|_inf partial maxima to the next iteration's k_lin
+  bool stamp_l0 = false;      // a timed iteration also stamps the end of the level-0 forward launch (ev[5])
+  // ... and the fused level-0 launch carries its own start / stop events (hipExtLaunchKernelGGL: the dispatch's own time stamps,
+  // what rocprofv3's kernel trace reads) -- events recorded AROUND a launch add their marker packets to it (7 us of 149)
+  bool l0_events = false;
 };
 
 #define HIPCHK(call)                                                                          \
@@ -286,6 +292,16 @@ template <typename F> void dispatch_fk(int fk, F &&f) {
 bool sharded(const gpslam_hip_handle *h) { return h->cfg.nranks > 1 || h->cfg.force_sharded == 1; }
 bool has_right_rank(const gpslam_hip_handle *h) { return sharded(h) && h->cfg.rank < h->cfg.nranks - 1; }
 
+// The one rule for level 0 of an iteration: fused where compile() found k_fused_level0 applicable, except on an unsharded
+// chain of a single level (that level is the top solve; a sharded rank's level 0 always keeps its separator), and then
+// with the GP priors as SE(3) records where the graph allows them.
+LaunchMode level0_mode(const gpslam_hip_handle *h) {
+  LaunchMode m;
+  m.fused = h->fuse_ok && (h->lv.size() >= 2 || sharded(h));
+  m.se3_rec = m.fused && h->struct_ok;
+  return m;
+}
+
 int read_scal(gpslam_hip_handle *h, double *out, int n, int *flag) {
   HIPCHK(hipMemcpyAsync(out, h->scal.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -293,7 +309,7 @@ int read_scal(gpslam_hip_handle *h, double *out, int n, int *flag) {
   return 0;
 }
 
-int collect_timing(gpslam_hip_handle *h, double *acc) {
+int collect_timing(gpslam_hip_handle *h, const LaunchMode &m, double *acc) {
   float ms;
   for (int i = 0; i < 4; i++) {
     HIPCHK(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]));
@@ -301,8 +317,8 @@ int collect_timing(gpslam_hip_handle *h, double *acc) {
   }
   HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[4]));
   acc[4] += ms;
-  if (h->time_l0) {            // the level-0 forward launch of this iteration: its own stamps, or (unfused) ev[2] = start of the solve phase
-    if (h->l0_ext) HIPCHK(hipEventElapsedTime(&ms, h->ev_l0a, h->ev_l0b));
+  if (m.stamp_l0) {             // the level-0 forward launch of this iteration: its own stamps, or (unfused) ev[2] = start of the solve phase
+    if (m.l0_events) HIPCHK(hipEventElapsedTime(&ms, h->ev_l0a, h->ev_l0b));
     else HIPCHK(hipEventElapsedTime(&ms, h->ev[2], h->ev[5]));
     h->l0_ms += ms;
   }

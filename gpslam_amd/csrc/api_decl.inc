@@ -31,4 +31,4 @@ int gpslam_hip_normal_equations(gpslam_hip_handle *h, double *D, double *O, doub
 int gpslam_hip_optimize(gpslam_hip_handle *h, const gpslam_hip_params *p, gpslam_hip_stats *st);
 int gpslam_hip_run_gn(gpslam_hip_handle *h, int32_t iters, gpslam_hip_stats *st, double *out5);
 int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, double *avg_ms);
-int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32);
+int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot, bool e32);

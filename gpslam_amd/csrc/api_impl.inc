@@ -15,7 +15,7 @@ UMat<RowT> make_umat(const gpslam_hip_handle *h) {
 
 // grp < 0: every GP prior in one launch (they share the handle's Qc); grp >= 0: the factors of Qc group grp -- the
 // device-side factor arrays are ordered by Qc when a graph has more than one (compile(), gpslam_hip_add_gp_priors_qc)
-GpArgs<RowT> gp_args(gpslam_hip_handle *h, RowT *partial, bool e32 = false, int grp = -1) {
+GpArgs<RowT> gp_args(gpslam_hip_handle *h, const LaunchMode &m, RowT *partial, bool e32 = false, int grp = -1) {
   GpArgs<RowT> a;
   a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride;
   a.count = (int)h->gp_left.size();
@@ -33,7 +33,7 @@ GpArgs<RowT> gp_args(gpslam_hip_handle *h, RowT *partial, bool e32 = false, int 
     }
   }
   a.vw = h->vw;
-  a.gps = (kIsF64 && (h->struct_now || (h->struct3_ok && !h->rows3))) ? h->gps.as<RowT>() : nullptr;
+  a.gps = (kIsF64 && (m.se3_rec || (h->struct3_ok && !m.d3_rows))) ? h->gps.as<RowT>() : nullptr;
   return a;
 }
 int gp_ngroups(const gpslam_hip_handle *h) { return (int)h->gp_groups.size() / 3; }
@@ -91,9 +91,9 @@ int launch_closures(gpslam_hip_handle *h) {
   return 0;
 }
 
-int launch_retract(gpslam_hip_handle *h, int slot);
-// mode 0: Jacobian rows + error, 1: error only.  Error partial sums land in h->partial, reduced into scal[slot].
-// e32 (the fp64 instantiation serving an fp32 handle, mode 1): the error pass also deposits its whitened errors as the
+int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot);
+// pass 0: Jacobian rows + error, 1: error only.  Error partial sums land in h->partial, reduced into scal[slot].
+// e32 (the fp64 instantiation serving an fp32 handle, pass 1): the error pass also deposits its whitened errors as the
 // fp32 right-hand side of the row tables -- the residual of the fp32 mode is always evaluated in fp64.
 // Kernels that do not depend on one another go to the handle's second stream only on graphs of at least this many states: below,
 // everything stays on one stream.  A/B of "never" against "always" (scripts/ab_fork.py, wall clock of run_gn(20), ms per
@@ -105,8 +105,8 @@ int launch_retract(gpslam_hip_handle *h, int slot);
 #define GPS_FORK_MIN 524288
 #endif
 constexpr int kForkMinStates = GPS_FORK_MIN;
-int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32 = false) {
-  if (!kIsF64 && mode == 1) return impl64::launch_factors(h, 1, slot, false);   // an fp32 handle's error is an fp64 error
+int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot, bool e32 = false) {
+  if (!kIsF64 && pass == 1) return impl64::launch_factors(h, m, 1, slot, false);   // an fp32 handle's error is an fp64 error
   RowT *part = h->partial.as<RowT>();
   int off = 0;
   // The factor kernels are independent of one another (disjoint rows, disjoint partial sums).  The GP-prior kernel
@@ -117,18 +117,18 @@ int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32 = false) {
   any_meas = any_meas || h->lpri.count() > 0;
   // GP priors, priors and between factors: ONE launch (k_lin) in the Jacobian pass.  Measurement factors, where a graph
   // has them, are light streaming kernels: they go to a second stream and run underneath (fork / join with events).
-  const bool merged = (mode == 0) && !h->gp_left.empty() && gp_ngroups(h) <= 1;
-  if (h->pend_upd && !(merged && kIsF64 && (h->struct_now || (h->struct3_ok && !h->rows3)))) {   // (defensive: an update is pending and this launch cannot apply it)
+  const bool merged = (pass == 0) && !h->gp_left.empty() && gp_ngroups(h) <= 1;
+  if (h->pend_upd && !(merged && kIsF64 && (m.se3_rec || (h->struct3_ok && !m.d3_rows)))) {   // (defensive: an update is pending and this launch cannot apply it)
     h->pend_upd = false;
-    int rcp = launch_retract(h, 2);
+    int rcp = launch_retract(h, LaunchMode{}, 2);
     if (rcp) return rcp;
   }
   // SE(3) chains whose GP priors travel as structured records: the interpolated measurement factors read their interval's record
   // (Jinv, Jinv Ad, the finite-difference block: MeasArgs::gps) instead of forming the same blocks again, so they run BEHIND k_lin
-  const bool meas_rec = (mode == 0) && kIsF64 && h->struct_now && h->mf == POSE3 && any_meas;
+  const bool meas_rec = (pass == 0) && kIsF64 && m.se3_rec && h->mf == POSE3 && any_meas;
   // (round 6: only on large graphs, kForkMinStates -- Plaza2's timeline: k_lin 7 us beside k_meas 10 us, then 12 us of nothing before
   //  the reduction starts)
-  const bool fork = (mode == 0) && !h->gp_left.empty() && h->aux_stream != nullptr && (merged ? any_meas : true) && !meas_rec && h->N >= kForkMinStates && h->fs.active;
+  const bool fork = (pass == 0) && !h->gp_left.empty() && h->aux_stream != nullptr && (merged ? any_meas : true) && !meas_rec && h->N >= kForkMinStates && h->fs.active;
   hipStream_t side = fork ? h->aux_stream : h->stream;
   if (fork) {
     HIPCHK(hipEventRecord(h->ev_fork, h->stream));
@@ -145,7 +145,7 @@ int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32 = false) {
     a.rowLR = compact ? h->rowC.as<RowT>() : h->rowLR.as<RowT>(); a.rowE = compact ? h->rowCE.as<RowT>() : h->rowE.as<RowT>();
     a.partial = partial; a.rowE32 = e32 ? (compact ? h->rowCE.as<float>() : h->rowE.as<float>()) : nullptr;
     // BetweenFactor<Pose3> of a launch whose consumer is the structured fused kernel: records instead of compact rows
-    a.rec = (kind == 2 && kIsF64 && h->struct_now && h->btw_rec_ok) ? h->brec.as<RowT>() : nullptr;
+    a.rec = (kind == 2 && kIsF64 && m.se3_rec && h->btw_rec_ok) ? h->brec.as<RowT>() : nullptr;
     return a;
   };
   // the previous retraction's maxima, if their reduction was deferred: into this launch (k_lin), or a launch of their own
@@ -162,7 +162,7 @@ int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32 = false) {
     la.red_in = red_here ? h->partial2.as<double>() : nullptr;
     la.red_n = h->pend_dmax_n; la.red_out = h->scal.as<double>() + h->pend_dmax_slot;
     h->pend_dmax_n = 0;
-    la.gp = gp_args(h, part + off, e32, gp_ngroups(h) == 1 ? 0 : -1);
+    la.gp = gp_args(h, m, part + off, e32, gp_ngroups(h) == 1 ? 0 : -1);
     la.nb_gp = nblocks(la.gp.count, 128);
     off += la.nb_gp;
     int total = la.nb_gp;
@@ -212,11 +212,11 @@ int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32 = false) {
     });
   } else {
   for (int grp = 0; grp < std::max(gp_ngroups(h), h->gp_left.empty() ? 0 : 1); grp++) {   // one launch per distinct Qc
-    GpArgs<RowT> a = gp_args(h, part + off, e32, gp_ngroups(h) >= 1 ? grp : -1);
+    GpArgs<RowT> a = gp_args(h, m, part + off, e32, gp_ngroups(h) >= 1 ? grp : -1);
     const int nb = nblocks(a.count, 128);
     dispatch_mf(h->mf, [&](auto tag) {
       constexpr int MF = decltype(tag)::value;
-      if (mode == 0) {
+      if (pass == 0) {
         launch_gp_rows<MF>(h, a, nb);
       } else {
         k_gp<RowT, MF, 1><<<dim3(nb), dim3(128), 0, h->stream>>>(a);
@@ -232,7 +232,7 @@ int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32 = false) {
     dispatch_mf(h->mf, [&](auto tag) {
       constexpr int MF = decltype(tag)::value;
       const dim3 g(nb), t(128);
-      if (mode == 0) {
+      if (pass == 0) {
         if (kind == 0) k_simple<RowT, MF, 0, true><<<g, t, 0, side>>>(a);
         else if (kind == 1) k_simple<RowT, MF, 1, true><<<g, t, 0, side>>>(a);
         else k_simple<RowT, MF, 2, true><<<g, t, 0, side>>>(a);
@@ -278,7 +278,7 @@ int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32 = false) {
       constexpr int MF = decltype(tag)::value;
       dispatch_fk(fk, [&](auto ftag) {
         constexpr int FK = decltype(ftag)::value;
-        if (mode == 0) k_meas<RowT, MF, FK, true><<<dim3(nb), dim3(128), 0, side>>>(a);
+        if (pass == 0) k_meas<RowT, MF, FK, true><<<dim3(nb), dim3(128), 0, side>>>(a);
         else k_meas<RowT, MF, FK, false><<<dim3(nb), dim3(128), 0, side>>>(a);
       });
     });
@@ -289,7 +289,7 @@ int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32 = false) {
     a.partial = reinterpret_cast<double *>(part + off);   // (RowT == double here)
     dispatch_mf(h->mf, [&](auto tag) {
       constexpr int MF = decltype(tag)::value;
-      if (mode == 0) k_clo_eval<MF, true><<<dim3(1), dim3(128), 0, side>>>(a);
+      if (pass == 0) k_clo_eval<MF, true><<<dim3(1), dim3(128), 0, side>>>(a);
       else k_clo_eval<MF, false><<<dim3(1), dim3(128), 0, side>>>(a);
     });
     off += 1;
@@ -313,9 +313,9 @@ int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32 = false) {
   }
   if (!kIsF64) {   // fp32 rows are in place; now the fp64 residual: whitened errors -> rowE (fp32), error -> scal[slot]
     HIPCHK(hipGetLastError());
-    return impl64::launch_factors(h, 1, slot, true);
+    return impl64::launch_factors(h, m, 1, slot, true);
   }
-  if (h->defer_err && kIsF64) {   // (RowT == double here: an fp32 handle's error comes out of the nested fp64 pass)
+  if (m.defer_error && kIsF64) {   // (RowT == double here: an fp32 handle's error comes out of the nested fp64 pass)
     h->pend_err_n = off; h->pend_err_slot = slot;     // summed by the extra workgroup of this iteration's k_retract
   } else {
     k_final_reduce<RowT><<<dim3(1), dim3(256), 0, h->stream>>>(part, off, h->scal.as<double>() + slot, 0);
@@ -324,7 +324,7 @@ int launch_factors(gpslam_hip_handle *h, int mode, int slot, bool e32 = false) {
   return 0;
 }
 
-int launch_assemble(gpslam_hip_handle *h, bool save_g) {
+int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g) {
   AsmArgs<Real, RowT> a;
   a.N = h->N; a.R = h->R;
   a.rowptr = h->rowptr.as<int>();
@@ -337,7 +337,7 @@ int launch_assemble(gpslam_hip_handle *h, bool save_g) {
   a.blk = h->lv[0].blk.as<Real>();
   a.gsave = save_g ? h->gsave.as<Real>() : nullptr;
   a.halo_add = has_right_rank(h) ? h->halo_add.as<Real>() : nullptr;
-  const bool rec3 = kIsF64 && h->struct3_ok && !h->rows3;
+  const bool rec3 = kIsF64 && h->struct3_ok && !m.d3_rows;
   a.gps3 = rec3 ? h->gps.as<Real>() : nullptr;
   a.gpidx = h->gpidx.as<int>(); a.gp_count = (int)h->gp_left.size(); a.Ud = h->dU.as<Real>();
   if (rec3 && h->gp_single_q == 0 && h->dU_version != h->U_version) {   // set_qc after compile()
@@ -385,26 +385,26 @@ bool fused_kernel_applies(const gpslam_hip_handle *h) {
   const bool b6 = h->b == 6 && (h->N <= 131072 || h->pure6);
   return (h->b == 12 || b6) && rows_kernel_applies(h) && h->nl == 0 && !off;   // (fp32 rows are widened as the assembly wave reads them)
 }
-void launch_fwd(gpslam_hip_handle *h, const FwdArgs<Real> &a, int grid) {
+void launch_fwd(gpslam_hip_handle *h, const LaunchMode &m, const FwdArgs<Real> &a, int grid) {
   const bool fast = (4 * h->b + 2 * h->R <= 64);   // room for the separator sums in spare lanes
   // level 0 of a Pose3 chain without landmark columns: four chunks per wave, panel rows in lanes
-  if (h->fuse_now && !a.no_sep && !a.add) {
+  if (m.fused && !a.no_sep && !a.add) {
     FusedArgs<Real, RowT> u;
     u.f = a;
     u.rowptr = h->rowptr.as<int>(); u.rowLR = h->rowLR.as<RowT>(); u.rowE = h->rowE.as<RowT>();
     u.crowptr = h->crowptr.as<int>(); u.rowC = h->rowC.as<RowT>(); u.rowCE = h->rowCE.as<RowT>();
     // SE(3): structured records when the launch says so; d = 3 manifolds: whenever the graph has them (every consumer decodes them)
-    u.gps = (h->struct_now || (kIsF64 && h->b == 6 && h->struct3_ok && !h->rows3)) ? h->gps.as<Real>() : nullptr;
+    u.gps = (m.se3_rec || (kIsF64 && h->b == 6 && h->struct3_ok && !m.d3_rows)) ? h->gps.as<Real>() : nullptr;
     u.gp_count = (int)h->gp_left.size();
     u.gpidx = h->gpidx.as<int>();
-    u.brec = (h->struct_now && h->btw_rec_ok) ? h->brec.as<Real>() : nullptr;
+    u.brec = (m.se3_rec && h->btw_rec_ok) ? h->brec.as<Real>() : nullptr;
     u.btwidx = h->btwidx.as<int>(); u.btw_count = h->btw.count();
     u.odd_rows = (h->M != (int)h->gp_left.size() * h->b) ? (h->odd_many ? 2 : 1) : 0;
     if constexpr (kIsF64) {
-      if (h->struct_now && h->irow_ok) { u.rowI = h->rowI.as<Real>(); u.irowptr = h->irowptr.as<int>(); }   // k_fused_level0<4>
+      if (m.se3_rec && h->irow_ok) { u.rowI = h->rowI.as<Real>(); u.irowptr = h->irowptr.as<int>(); }   // k_fused_level0<4>
     }
-    u.gsave = h->gsave_now ? h->gsave.as<Real>() : nullptr;
-    u.gsave2 = h->gsave_now ? h->gsave2.as<Real>() : nullptr;
+    u.gsave = m.gsave ? h->gsave.as<Real>() : nullptr;
+    u.gsave2 = m.gsave ? h->gsave2.as<Real>() : nullptr;
     u.simd_cnt = h->simd_cnt.as<int>();
     if (u.gps != nullptr && h->gp_single_q == 0 && h->dU_version != h->U_version) {   // (36 doubles, stream-ordered: set_qc was called after compile())
       (void)hipMemcpyAsync(h->dU.p, h->U, 36 * sizeof(double), hipMemcpyHostToDevice, h->stream);
@@ -413,7 +413,7 @@ void launch_fwd(gpslam_hip_handle *h, const FwdArgs<Real> &a, int grid) {
     u.Ud = h->dU.as<Real>();
     {   // a diagonal chol_upper(Qc^-1) (isotropic / diagonal Qc) takes the assembly wave's shorter form
       const double *Uh = h->gp_single_q > 0 ? &h->gp_Utab[(size_t)(h->gp_single_q - 1) * 36] : h->U;
-      bool dg = h->b == 12 && h->struct_now && !plan(h, GPSLAM_PLAN_GENERIC_QC);
+      bool dg = h->b == 12 && m.se3_rec && !plan(h, GPSLAM_PLAN_GENERIC_QC);
       for (int i = 0; i < 6 && dg; i++)
         for (int j = i + 1; j < 6; j++) dg = dg && Uh[i * 6 + j] == 0.0;
       u.u_diag = dg ? 1 : 0;
@@ -424,8 +424,7 @@ void launch_fwd(gpslam_hip_handle *h, const FwdArgs<Real> &a, int grid) {
     (void)hipMemsetAsync(h->dbg_trace.p, 0, (size_t)h->dbg_trace_waves * 64 * 8, h->stream);
     u.trace = h->dbg_trace.as<unsigned long long>();
 #endif
-    h->l0_ext = h->time_l0 && h->l0_stamps && h->ev_l0a != nullptr;
-    launch_fused_k(h->b, u, nblocks(grid, 4), h->stream, h->l0_ext ? h->ev_l0a : nullptr, h->l0_ext ? h->ev_l0b : nullptr);
+    launch_fused_k(h->b, u, nblocks(grid, 4), h->stream, m.l0_events ? h->ev_l0a : nullptr, m.l0_events ? h->ev_l0b : nullptr);
     return;
   }
   if (rows_kernel_applies(h) && !a.no_sep && !a.add) {
@@ -458,12 +457,12 @@ bool upper_applies(const gpslam_hip_handle *h) {
 }
 // Level 1 as groups of four (compile()): k_fused_level0 then reduces its four chunk separators in its own tail; the
 // unfused level-0 kernels leave that level to a launch of upper.hip's kernel with G = 4.
-bool tail_now(const gpslam_hip_handle *h) {
-  return h->upper_ok && h->fuse_now && h->lv.size() >= 3 && h->lv[1].m == 4;
+bool tail_now(const gpslam_hip_handle *h, const LaunchMode &m) {
+  return h->upper_ok && m.fused && h->lv.size() >= 3 && h->lv[1].m == 4;
 }
 // Forward elimination through the local levels.  Unsharded: the last level is the top solve.
 // Sharded: every level keeps its first block as separator; the last level reduces to the interface record.
-int launch_forward(gpslam_hip_handle *h, double lambda) {
+int launch_forward(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
   const int nl = (int)h->lv.size();
   const bool sh = sharded(h);
   const size_t BS = (size_t)2 * h->b * h->b + (size_t)h->b * h->R, AS = (size_t)h->b * h->b + (size_t)h->b * h->R;
@@ -471,7 +470,7 @@ int launch_forward(gpslam_hip_handle *h, double lambda) {
     Level &v = h->lv[l];
     const bool last = (l == nl - 1);
     if (h->upper_ok && l >= 1) {   // (the last level also solves and back-substitutes itself)
-      if (l == 1 && tail_now(h)) continue;   // done in the tail of the level-0 kernel
+      if (l == 1 && tail_now(h, m)) continue;   // done in the tail of the level-0 kernel
       UpFwdArgs u;
       u.blk = v.blk.as<double>(); u.add = v.add.as<double>();
       u.up_blk = last ? nullptr : h->lv[l + 1].blk.as<double>();
@@ -501,7 +500,7 @@ int launch_forward(gpslam_hip_handle *h, double lambda) {
       a.no_sep = last ? 1 : 0;
       a.last_has_right = 0;
       grid = last ? 1 : v.nch;
-      if (l == 0 && tail_now(h)) {   // the fused kernel reduces its four separators itself: its output is level 2's input
+      if (l == 0 && tail_now(h, m)) {   // the fused kernel reduces its four separators itself: its output is level 2's input
         a.tail = 1;
         a.l1_blk = h->lv[1].blk.as<Real>();
         a.up_blk = h->lv[2].blk.as<Real>();
@@ -517,8 +516,8 @@ int launch_forward(gpslam_hip_handle *h, double lambda) {
       if (a.last_has_right) a.remote_add = (l == 0) ? h->halo_add.as<Real>() : v.add.as<Real>() + (size_t)v.n * AS;
       grid = last ? 1 : v.nch;
     }
-    launch_fwd(h, a, grid);
-    if (l == 0 && h->time_l0) HIPCHK(hipEventRecord(h->ev[5], h->stream));
+    launch_fwd(h, m, a, grid);
+    if (l == 0 && m.stamp_l0) HIPCHK(hipEventRecord(h->ev[5], h->stream));
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -780,18 +779,18 @@ FsArgs<Real, RowT> fs_top_args(gpslam_hip_handle *h) {
   return t;
 }
 
-int launch_retract(gpslam_hip_handle *h, int slot);
+int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot);
 int launch_dot(gpslam_hip_handle *h, const Real *x, const Real *y, int n, int slot);
 
-// lm_trial: the rows are those of the linearisation point (gpslam_hip_lm_begin); the assembly also stores the gradient
-int fs_split_phase1(gpslam_hip_handle *h, double lambda, bool lm_trial = false) {
+// lm_trial: the rows are those of the linearisation point (gpslam_hip_lm_begin); the assembly also stores the gradient.
+// clear_flag = false: inside a multi-iteration run (dist_run_gn) the non-positive-pivot flag is sticky
+int fs_split_phase1(gpslam_hip_handle *h, double lambda, bool lm_trial, bool clear_flag) {
   FatSepPlan &p = h->fs;
   int rc;
   h->ph_lambda = lambda;
-  if (!h->keep_flag) HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  h->struct_now = false;
-  if (!lm_trial && (rc = launch_factors(h, 0, 0))) return rc;
-  if ((rc = launch_assemble(h, lm_trial))) return rc;
+  if (clear_flag) HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
+  if (!lm_trial && (rc = launch_factors(h, LaunchMode{}, 0, 0))) return rc;
+  if ((rc = launch_assemble(h, LaunchMode{}, lm_trial))) return rc;
   if ((rc = fs_forward(h, lambda))) return rc;
   FsArgs<Real, RowT> a = fs_args(h, lambda);
   k_fs_pack_record<Real, RowT><<<dim3(nblocks(p.nb_top * p.nb_top, 256)), dim3(256), 0, h->stream>>>(a, p.end_link, p.nb_top, p.send.as<Real>());
@@ -830,8 +829,8 @@ int fs_split_solve(gpslam_hip_handle *h) {
 int fs_split_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) {
   int rc;
   if ((rc = fs_split_solve(h))) return rc;
-  if ((rc = launch_retract(h, 2))) return rc;
-  if (st && (rc = launch_factors(h, 1, 1))) return rc;
+  if ((rc = launch_retract(h, LaunchMode{}, 2))) return rc;
+  if (st && (rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;
   HIPCHK(hipGetLastError());
   if (st) {
     double sc[4];
@@ -1048,17 +1047,17 @@ int fs_build(gpslam_hip_handle *h, const std::vector<int> &touch_lo, const std::
   return 0;
 }
 
-int launch_solve(gpslam_hip_handle *h, double lambda) {
+int launch_solve(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
   int rc;
   if (h->fs.active) return fs_solve(h, lambda);
-  if ((rc = launch_forward(h, lambda))) return rc;
+  if ((rc = launch_forward(h, m, lambda))) return rc;
   if ((rc = launch_backward(h, nullptr))) return rc;
   if ((rc = launch_closures(h))) return rc;
   return launch_landmarks(h, lambda);
 }
 
 // x <- x (+) delta for the local states (and landmarks); scal[slot] = |delta|_inf
-int launch_retract(gpslam_hip_handle *h, int slot) {
+int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot) {
   RetractArgs<Real> a;
   a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride; a.N = h->N; a.R = h->R;
   a.chart = h->cfg.chart; a.first = 0; a.x = h->lv[0].x.as<Real>(); a.partial = h->partial2.as<Real>(); a.flag = h->flag.as<int>();
@@ -1070,7 +1069,7 @@ int launch_retract(gpslam_hip_handle *h, int slot) {
     constexpr int MF = decltype(tag)::value;
     k_retract<Real, MF><<<dim3(nb + (red ? 1 : 0)), dim3(128), 0, h->stream>>>(a);
   });
-  if (h->defer_dmax && h->nl == 0) { h->pend_dmax_n = nb; h->pend_dmax_slot = slot; }   // reduced by the next linearisation's launch
+  if (m.defer_maxima && h->nl == 0) { h->pend_dmax_n = nb; h->pend_dmax_slot = slot; }   // reduced by the next linearisation's launch
   else k_final_reduce<Real><<<dim3(1), dim3(256), 0, h->stream>>>(h->partial2.as<Real>(), nb, h->scal.as<double>() + slot, 1);
   if (h->nl > 0 && h->fs.active) {
     const int nbl = std::min(nblocks(h->nl, 256), 1024);
@@ -1084,42 +1083,36 @@ int launch_retract(gpslam_hip_handle *h, int slot) {
   return 0;
 }
 
+// The mode of one Gauss-Newton iteration (enqueue_gn; collect_timing reads its level-0 stamps).  Deferred reductions: chains
+// without landmarks on an unsharded handle (the landmark update folds its maximum into the same slot; sharded iterations do not
+// come through here); eval_after = false: the next iteration's k_lin follows and reduces the retraction's maxima.
+LaunchMode gn_mode(const gpslam_hip_handle *h, bool timed, bool eval_after) {
+  LaunchMode m = level0_mode(h);
+  m.defer_error = h->nl == 0 && !h->fs.active && kIsF64;
+  m.defer_maxima = m.defer_error && !eval_after;
+  m.stamp_l0 = timed && !h->fs.active;
+  m.l0_events = m.stamp_l0 && m.fused && h->l0_stamps && h->ev_l0a != nullptr;
+  return m;
+}
 // one Gauss-Newton iteration enqueued on the stream (no host sync); records phase events when timed.
 // eval_after = false skips the error-only pass over the retracted state: inside a fixed-count run the next
 // iteration's linearisation evaluates exactly that error anyway (scal[0]), so it is computed once, not twice.
-int enqueue_gn(gpslam_hip_handle *h, double lambda, bool timed, bool eval_after = true, bool defer_retract = false) {
+int enqueue_gn(gpslam_hip_handle *h, const LaunchMode &m, double lambda, bool timed, bool eval_after, bool defer_retract) {
   int rc;
   if (timed) HIPCHK(hipEventRecord(h->ev[0], h->stream));
-  const bool fused = h->fuse_ok && h->lv.size() >= 2;   // the assembly happens inside the level-0 elimination
-  h->struct_now = fused && h->struct_ok;                // ... which then takes the GP priors as structured records
-  // deferred reductions: chains without landmarks on an unsharded handle (the landmark update folds its maximum into the
-  // same slot; sharded iterations do not come through here)
-  const bool may_defer = h->nl == 0 && !h->fs.active && kIsF64;
-  h->defer_err = may_defer;
-  rc = launch_factors(h, 0, 0);
-  h->defer_err = false;
-  if (rc) { h->struct_now = false; h->pend_err_n = 0; return rc; }
+  if ((rc = launch_factors(h, m, 0, 0))) { h->pend_err_n = 0; return rc; }
   if (timed) HIPCHK(hipEventRecord(h->ev[1], h->stream));
-  if (!fused && (rc = launch_assemble(h, false))) return rc;
+  if (!m.fused && (rc = launch_assemble(h, m, false))) return rc;   // (fused: the assembly happens inside the level-0 elimination)
   if (timed) HIPCHK(hipEventRecord(h->ev[2], h->stream));
-  h->fuse_now = fused;
-  h->time_l0 = timed && !h->fs.active;
-  h->l0_ext = false;
-  rc = launch_solve(h, lambda);
-  h->fuse_now = false;
-  h->struct_now = false;
-  if (rc) { h->time_l0 = false; return rc; }
+  if ((rc = launch_solve(h, m, lambda))) return rc;
   if (timed) HIPCHK(hipEventRecord(h->ev[3], h->stream));
   if (defer_retract) {                                  // run_gn, not the last iteration: the NEXT k_lin applies this update
     h->pend_upd = true;
     if (timed) HIPCHK(hipEventRecord(h->ev[4], h->stream));
     return 0;
   }
-  h->defer_dmax = may_defer && !eval_after;            // (the next iteration's k_lin follows; the last one reduces at once)
-  rc = launch_retract(h, 2);
-  h->defer_dmax = false;
-  if (rc) return rc;
-  if (eval_after && (rc = launch_factors(h, 1, 1))) return rc;
+  if ((rc = launch_retract(h, m, 2))) return rc;
+  if (eval_after && (rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;
   if (timed) HIPCHK(hipEventRecord(h->ev[4], h->stream));
   return 0;
 }
@@ -1552,7 +1545,7 @@ int gpslam_hip_linearize_gp(gpslam_hip_handle *h, double *errors, double *jacobi
   HIPCHK(h->api_e.reserve((size_t)F * b * sizeof(RowT)));
   if (jacobians) HIPCHK(h->api_H.reserve((size_t)F * 4 * b * d * sizeof(RowT)));
   // (unwhitened values do not depend on Qc: one launch over the device-side order, whatever the groups)
-  GpArgs<RowT> a = gp_args(h, nullptr);
+  GpArgs<RowT> a = gp_args(h, LaunchMode{}, nullptr);
   a.rowLR = nullptr; a.rowE = nullptr;
   a.out_e = h->api_e.as<RowT>(); a.out_H = jacobians ? h->api_H.as<RowT>() : nullptr;
   dispatch_mf(h->mf, [&](auto tag) {
@@ -1618,7 +1611,7 @@ int gpslam_hip_linearize_meas(gpslam_hip_handle *h, int32_t kind, double *errors
 // ---------------------------------------------------------------- the optimiser loops on a sharded handle / a split piece
 // (round 5: gpslam_hip_set_collectives).  The phases are the ones a caller-owned loop uses (include/gpslam_hip.h, "segment
 // sharding"); the collectives are the host's callbacks, enqueued on the handle's stream.
-int gpslam_hip_iterate_phase1(gpslam_hip_handle *h, double lambda);
+int iterate_phase1(gpslam_hip_handle *h, double lambda, bool clear_flag);
 int gpslam_hip_iterate_phase2a(gpslam_hip_handle *h);
 int gpslam_hip_iterate_phase2b(gpslam_hip_handle *h, gpslam_hip_stats *st);
 int gpslam_hip_lm_begin(gpslam_hip_handle *h);
@@ -1631,7 +1624,7 @@ int gpslam_hip_interface_send(gpslam_hip_handle *h, void **dev_ptr, size_t *byte
 int gpslam_hip_interface_recv(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes);
 int gpslam_hip_fs_interface(gpslam_hip_handle *h, void **send, size_t *send_bytes, void **recv, size_t *recv_bytes);
 int gpslam_hip_landmark_reduce_buffer(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes);
-int fs_split_phase1(gpslam_hip_handle *h, double lambda, bool lm_trial);
+int fs_split_phase1(gpslam_hip_handle *h, double lambda, bool lm_trial, bool clear_flag);
 int fs_split_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st);
 
 bool split_piece(const gpslam_hip_handle *h) { return h->fs.active && h->fs.split; }
@@ -1713,12 +1706,13 @@ struct DistErr {
   static int decode(double v) { return v != 0.0 ? -(int)v : 0; }
 };
 
-// one Gauss-Newton iteration over all ranks / pieces.  loc (optional): THIS rank's statistics.  Returns only what a collective
-// itself reported (then the ranks are out of step anyway); local failures go to `de`.
-int dist_gn_step(gpslam_hip_handle *h, gpslam_hip_stats *loc, DistErr &de) {
+// one Gauss-Newton iteration over all ranks / pieces.  loc (optional): THIS rank's statistics.  clear_flag: phase 1 clears the
+// non-positive-pivot flag.  Returns only what a collective itself reported (then the ranks are out of step anyway); local failures
+// go to `de`.
+int dist_gn_step(gpslam_hip_handle *h, gpslam_hip_stats *loc, DistErr &de, bool clear_flag) {
   int rc;
   if (split_piece(h)) {
-    if (de.ok()) de.note(fs_split_phase1(h, 0.0, false));
+    if (de.ok()) de.note(fs_split_phase1(h, 0.0, false, clear_flag));
     if ((rc = dist_exchange(h))) return rc;
     if (de.ok()) {
       rc = fs_split_phase2(h, loc);
@@ -1726,7 +1720,7 @@ int dist_gn_step(gpslam_hip_handle *h, gpslam_hip_stats *loc, DistErr &de) {
       else if (loc) loc->status = GPSLAM_E_NOT_SPD;
     }
   } else {
-    if (de.ok()) de.note(IMPL_NS::gpslam_hip_iterate_phase1(h, 0.0));
+    if (de.ok()) de.note(iterate_phase1(h, 0.0, clear_flag));
     if ((rc = dist_exchange(h))) return rc;
     if (de.ok()) de.note(IMPL_NS::gpslam_hip_iterate_phase2a(h));
     if ((rc = dist_reduce_landmarks(h))) {
@@ -1765,11 +1759,11 @@ int dist_iterate_gn(gpslam_hip_handle *h, gpslam_hip_stats *st) {
   gpslam_hip_stats loc;
   std::memset(&loc, 0, sizeof(loc));
   DistErr de;
-  if ((rc = dist_gn_step(h, &loc, de))) return rc;
+  if ((rc = dist_gn_step(h, &loc, de, true))) return rc;
   return dist_gn_finish(h, loc, de, st, 1);
 }
 // gpslam_hip_run_gn on a sharded handle / split piece: `iters` iterations, the statistics of the last one.  The non-positive-pivot
-// flag is cleared ONCE and stays up through the run (phase 1 does not clear it: keep_flag), a local failure of any iteration is
+// flag is cleared ONCE and stays up through the run (phase 1 does not clear it), a local failure of any iteration is
 // carried to the one scalar gather at the end: an indefinite pivot or an error in iteration k < last is reported by every rank, as
 // the unsharded run_gn reports it (ADVICE r5: both used to be swallowed).
 int dist_run_gn(gpslam_hip_handle *h, int iters, gpslam_hip_stats *st) {
@@ -1780,10 +1774,8 @@ int dist_run_gn(gpslam_hip_handle *h, int iters, gpslam_hip_stats *st) {
   std::memset(&loc, 0, sizeof(loc));
   DistErr de;
   de.note(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream) == hipSuccess ? 0 : GPSLAM_E_HIP);
-  h->keep_flag = true;
   for (int it = 0; it < iters; it++)
-    if ((rc = dist_gn_step(h, (it == iters - 1) ? &loc : nullptr, de))) break;
-  h->keep_flag = false;
+    if ((rc = dist_gn_step(h, (it == iters - 1) ? &loc : nullptr, de, false))) break;
   if (rc) return rc;
   return dist_gn_finish(h, loc, de, st, iters);
 }
@@ -1860,7 +1852,7 @@ int gpslam_hip_error(gpslam_hip_handle *h, double *err) {
   (void)hipSetDevice(h->cfg.device);
   double s[4] = {0, 0, 0, 0};
   int flag;
-  rc = launch_factors(h, 1, 1);
+  rc = launch_factors(h, LaunchMode{}, 1, 1);
   if (!rc) rc = read_scal(h, s, 4, &flag);
   *err = s[1];
   // (with the host's collectives registered: the error of the whole chain, NonlinearFactorGraph::error -- a collective call, which a
@@ -1882,13 +1874,14 @@ int gpslam_hip_iterate_gn(gpslam_hip_handle *h, gpslam_hip_stats *st) {
   if (dist_handle(h)) return dist_iterate_gn(h, st);     // (refuses without the host's collectives: the phase loop is the caller's then)
   (void)hipSetDevice(h->cfg.device);
   HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  if ((rc = enqueue_gn(h, 0.0, true))) return rc;
+  const LaunchMode m = gn_mode(h, true, true);
+  if ((rc = enqueue_gn(h, m, 0.0, true, true, false))) return rc;
   double s[4];
   int flag = 0;
   if ((rc = read_scal(h, s, 4, &flag))) return rc;
   for (int i = 0; i < 5; i++) h->last_ms[i] = 0;
   h->l0_ms = 0.0;
-  if ((rc = collect_timing(h, h->last_ms))) return rc;
+  if ((rc = collect_timing(h, m, h->last_ms))) return rc;
   if (st) {
     std::memset(st, 0, sizeof(*st));
     st->error_before = s[0];
@@ -1923,19 +1916,20 @@ int gpslam_hip_run_gn(gpslam_hip_handle *h, int32_t iters, gpslam_hip_stats *st,
     // never leave an update unapplied behind an error (ADVICE r5: EVERY exit, not only enqueue_gn's): the accessors of the states
     // (get_states, set_halo, the next linearisation) read h->pose / h->vel as they are
     auto bail = [&](int code) {
-      if (h->pend_upd) { h->pend_upd = false; (void)launch_retract(h, 2); (void)hipStreamSynchronize(h->stream); }
+      if (h->pend_upd) { h->pend_upd = false; (void)launch_retract(h, LaunchMode{}, 2); (void)hipStreamSynchronize(h->stream); }
       return code;
     };
-    if ((rc = enqueue_gn(h, 0.0, timed, last, h->pend_ok && !last))) return bail(rc);
+    const LaunchMode m = gn_mode(h, timed, last);
+    if ((rc = enqueue_gn(h, m, 0.0, timed, last, h->pend_ok && !last))) return bail(rc);
     if (timed) {
       if (hipEventSynchronize(h->ev[4]) != hipSuccess) { h->err = "hipEventSynchronize failed inside run_gn"; return bail(GPSLAM_E_HIP); }
-      if ((rc = collect_timing(h, acc))) return bail(rc);
+      if ((rc = collect_timing(h, m, acc))) return bail(rc);
     }
   }
   double s[4];
   int flag = 0;
   if ((rc = read_scal(h, s, 4, &flag))) {
-    if (h->pend_upd) { h->pend_upd = false; (void)launch_retract(h, 2); }
+    if (h->pend_upd) { h->pend_upd = false; (void)launch_retract(h, LaunchMode{}, 2); }
     return rc;
   }
   if (out5) for (int i = 0; i < 5; i++) out5[i] = acc[i];
@@ -1965,11 +1959,9 @@ int gpslam_hip_iterate_lm(gpslam_hip_handle *h, double *lambda, const gpslam_hip
   HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
   // Pose3-sized chains without landmarks: every trial is the fused level-0 kernel (it re-assembles from the row tables /
   // structured records of the linearisation point with the trial's lambda, and leaves the gradient in gsave / gsave2)
-  const bool fused = h->fuse_ok && h->lv.size() >= 2 && h->nl == 0;
-  h->struct_now = fused && h->struct_ok;
-  rc = launch_factors(h, 0, 0);                          // scal[0] = current error
-  h->struct_now = false;
-  if (rc) return rc;
+  LaunchMode m = level0_mode(h);
+  m.gsave = m.fused;
+  if ((rc = launch_factors(h, m, 0, 0))) return rc;     // scal[0] = current error
   if ((rc = backup_state(h, false))) return rc;
   double s[10];
   int flag = 0;
@@ -1979,25 +1971,22 @@ int gpslam_hip_iterate_lm(gpslam_hip_handle *h, double *lambda, const gpslam_hip
   const int nx = h->N * h->b;
   for (;;) {
     HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-    if (!fused && (rc = launch_assemble(h, true))) return rc;      // rows are still those of the linearisation point
-    h->fuse_now = fused; h->struct_now = fused && h->struct_ok; h->gsave_now = fused;
-    rc = launch_solve(h, *lambda);
-    h->fuse_now = false; h->struct_now = false; h->gsave_now = false;
-    if (rc) return rc;
+    if (!m.fused && (rc = launch_assemble(h, m, true))) return rc;   // rows are still those of the linearisation point
+    if ((rc = launch_solve(h, m, *lambda))) return rc;
     k_gather_delta<Real><<<dim3(nblocks(nx, 256)), dim3(256), 0, h->stream>>>(h->lv[0].x.as<Real>(), h->N, h->R, h->b, h->dvec.as<Real>());
     // delta . g (slot 3), its separator parts (fused: slot 8), |delta|^2 (slot 4)
-    if ((rc = launch_dot3(h, h->dvec.as<Real>(), h->gsave.as<Real>(), fused ? h->gsave2.as<Real>() : nullptr, nx, 3, 8, 4))) return rc;
+    if ((rc = launch_dot3(h, h->dvec.as<Real>(), h->gsave.as<Real>(), m.fused ? h->gsave2.as<Real>() : nullptr, nx, 3, 8, 4))) return rc;
     if (h->nl > 0) {
       const Real *gLp = h->fs.active ? h->lm_gL.as<Real>() : h->lm_S.as<Real>() + (size_t)h->nl * h->R;
       if ((rc = launch_dot(h, h->lm_dL.as<Real>(), gLp, h->nl, 5))) return rc;
       if ((rc = launch_dot(h, h->lm_dL.as<Real>(), h->lm_dL.as<Real>(), h->nl, 6))) return rc;
     }
-    if ((rc = launch_retract(h, 2))) return rc;
-    if ((rc = launch_factors(h, 1, 1))) return rc;       // scal[1] = trial error
+    if ((rc = launch_retract(h, m, 2))) return rc;
+    if ((rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;   // scal[1] = trial error
     if ((rc = read_scal(h, s, 10, &flag))) return rc;
     err0 = s[0];
     trials++;
-    const double s6[6] = {s[0], s[1], s[2], s[3] + (fused ? s[8] : 0.0) + (h->nl > 0 ? s[5] : 0.0), s[4] + (h->nl > 0 ? s[6] : 0.0),
+    const double s6[6] = {s[0], s[1], s[2], s[3] + (m.fused ? s[8] : 0.0) + (h->nl > 0 ? s[5] : 0.0), s[4] + (h->nl > 0 ? s[6] : 0.0),
                           flag ? 1.0 : 0.0};
     int32_t ok = 0, done = 0;
     if ((rc = ::gpslam_hip_lm_decide(s6, p, lambda, &ok, &done))) return rc;
@@ -2064,8 +2053,8 @@ int gpslam_hip_normal_equations(gpslam_hip_handle *h, double *D, double *O, doub
   if (rc) return rc;
   (void)hipSetDevice(h->cfg.device);
   if (B && h->fs.active) return fail(h, GPSLAM_E_UNSUPPORTED, "the dense landmark coupling B does not exist on the segmented landmark path");
-  if ((rc = launch_factors(h, 0, 0))) return rc;
-  if ((rc = launch_assemble(h, false))) return rc;
+  if ((rc = launch_factors(h, LaunchMode{}, 0, 0))) return rc;
+  if ((rc = launch_assemble(h, LaunchMode{}, false))) return rc;
   const int N = h->N, b = h->b, R = h->R;
   const size_t BS = (size_t)2 * b * b + (size_t)b * R;
   std::vector<Real> blk((size_t)N * BS);
@@ -2093,10 +2082,9 @@ int gpslam_hip_get_rows(gpslam_hip_handle *h, int32_t *n_rows, double *rowLR, do
   const size_t M = (size_t)h->M, Mc = (size_t)h->Mc, b = (size_t)h->b, d = (size_t)h->d;
   if (n_rows) *n_rows = (int32_t)(M + Mc);
   if (!rowLR && !rowE && !rowM && !rowLm) return 0;
-  h->rows3 = true;                          // the table itself is wanted: no structured records
-  rc = launch_factors(h, 0, 0);
-  h->rows3 = false;
-  if (rc) return rc;
+  LaunchMode m;
+  m.d3_rows = true;                         // the table itself is wanted: no structured records
+  if ((rc = launch_factors(h, m, 0, 0))) return rc;
   if (M + Mc == 0) return 0;
   std::vector<RowT> tLR(M * 2 * b), tE(M), tM(h->nl > 0 ? M * h->ld : 0), cLR(Mc * b), cE(Mc);
   if (M > 0) {
@@ -2144,7 +2132,7 @@ int gpslam_hip_block_tridiag_solve(gpslam_hip_handle *h, int32_t N, const double
   }
   HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
   HIPCHK(hipMemcpyAsync(h->lv[0].blk.p, blk.data(), blk.size() * sizeof(Real), hipMemcpyHostToDevice, h->stream));
-  if ((rc = launch_solve(h, 0.0))) return rc;
+  if ((rc = launch_solve(h, LaunchMode{}, 0.0))) return rc;
   std::vector<Real> xs((size_t)N * b);
   int flag = 0;
   HIPCHK(hipMemcpyAsync(xs.data(), h->lv[0].x.p, xs.size() * sizeof(Real), hipMemcpyDeviceToHost, h->stream));
@@ -2160,23 +2148,24 @@ int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, do
   if (reps <= 0 || !avg_ms || which < 0 || which > 4 || sharded(h)) return GPSLAM_E_INVALID;
   (void)hipSetDevice(h->cfg.device);
   double total = 0.0;
+  // (K1 and the fused elimination are timed in the form an iteration runs them: structured GP records where they apply)
+  LaunchMode m = level0_mode(h);
+  m.se3_rec = m.se3_rec && (which == 0 || which == 2);
   for (int r = 0; r < reps; r++) {
     // bring the inputs of the timed kernel into their real state (untimed)
-    // (K1 and the fused elimination are timed in the form an iteration runs them: structured GP records where they apply)
-    h->struct_now = (which == 0 || which == 2) && h->fuse_ok && h->struct_ok && h->lv.size() >= 2;
-    if (which >= 1 && (rc = launch_factors(h, 0, 0))) { h->struct_now = false; return rc; }
-    if (which >= 2 && (rc = launch_assemble(h, false))) return rc;
+    if (which >= 1 && (rc = launch_factors(h, m, 0, 0))) return rc;
+    if (which >= 2 && (rc = launch_assemble(h, m, false))) return rc;
     HIPCHK(hipEventRecord(h->ev[0], h->stream));
     if (which == 0) {
-      GpArgs<RowT> a = gp_args(h, h->partial.as<RowT>(), false, gp_ngroups(h) >= 1 ? 0 : -1);   // (several Qc: the first group)
+      GpArgs<RowT> a = gp_args(h, m, h->partial.as<RowT>(), false, gp_ngroups(h) >= 1 ? 0 : -1);   // (several Qc: the first group)
       const int nb = nblocks(a.count, 128);
       dispatch_mf(h->mf, [&](auto tag) {
         constexpr int MF = decltype(tag)::value;
         launch_gp_rows<MF>(h, a, nb);
       });
     } else if (which == 1) {
-      if (h->fuse_ok && h->lv.size() >= 2) { *avg_ms = 0.0; return 0; }   // no such launch: see the header
-      if ((rc = launch_assemble(h, false))) return rc;
+      if (m.fused) { *avg_ms = 0.0; return 0; }   // no such launch: see the header
+      if ((rc = launch_assemble(h, m, false))) return rc;
     } else if (which == 2 || which == 3) {
       Level &v = h->lv[0];
       const bool top = (h->lv.size() == 1);
@@ -2188,14 +2177,11 @@ int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, do
       a.remote_add = nullptr; a.lambda = Real(0); a.flag = h->flag.as<int>();
       a.l1_blk = nullptr; a.tail = 0;
       const int grid = top ? 1 : v.nch;
-      h->fuse_now = h->fuse_ok && !top;
-      if (tail_now(h)) {    // timed in the form an iteration runs it
+      if (tail_now(h, m)) {    // timed in the form an iteration runs it
         a.tail = 1; a.l1_blk = h->lv[1].blk.as<Real>();
         a.up_blk = h->lv[2].blk.as<Real>(); a.up_add = h->lv[2].add.as<Real>();
       }
-      launch_fwd(h, a, grid);
-      h->fuse_now = false;
-      h->struct_now = false;
+      launch_fwd(h, m, a, grid);
       if (which == 3) {  // time the level-0 back-substitution instead (separator solutions = whatever lv[1].x holds)
         HIPCHK(hipEventRecord(h->ev[0], h->stream));
         BwdArgs<Real> bw;
@@ -2217,7 +2203,6 @@ int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, do
         k_retract<Real, MF><<<dim3(nblocks(h->N, 128)), dim3(128), 0, h->stream>>>(a);
       });
     }
-    h->struct_now = false;
     HIPCHK(hipEventRecord(h->ev[1], h->stream));
     HIPCHK(hipEventSynchronize(h->ev[1]));
     float ms = 0.f;
@@ -2249,24 +2234,21 @@ int gpslam_hip_interface_recv(gpslam_hip_handle *h, void **dev_ptr, size_t *byte
   return 0;
 }
 
-// phase 1: linearise, assemble, eliminate the local segment down to its separator -> interface record
-int gpslam_hip_iterate_phase1(gpslam_hip_handle *h, double lambda) {
+// phase 1: linearise, assemble, eliminate the local segment down to its separator -> interface record.
+// clear_flag = false: inside a multi-iteration run (dist_run_gn) the non-positive-pivot flag is sticky
+int iterate_phase1(gpslam_hip_handle *h, double lambda, bool clear_flag) {
   int rc = need_compiled(h);
   if (rc) return rc;
   if (!sharded(h)) return GPSLAM_E_INVALID;
   (void)hipSetDevice(h->cfg.device);
+  const LaunchMode m = level0_mode(h);
   h->ph_lambda = lambda;
-  if (!h->keep_flag) HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));   // (inside a multi-iteration run the flag is sticky)
-  h->struct_now = h->fuse_ok && h->struct_ok;
-  rc = launch_factors(h, 0, 0);
-  if (rc) { h->struct_now = false; return rc; }
-  if (!h->fuse_ok && (rc = launch_assemble(h, false))) return rc;
-  h->fuse_now = h->fuse_ok;
-  rc = launch_forward(h, lambda);
-  h->fuse_now = false;
-  h->struct_now = false;
-  return rc;
+  if (clear_flag) HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
+  if ((rc = launch_factors(h, m, 0, 0))) return rc;
+  if (!m.fused && (rc = launch_assemble(h, m, false))) return rc;
+  return launch_forward(h, m, lambda);
 }
+int gpslam_hip_iterate_phase1(gpslam_hip_handle *h, double lambda) { return iterate_phase1(h, lambda, true); }
 
 // phase 2 (after the all-gather of the records into interface_recv): every rank solves the P-block reduced
 // system redundantly and back-substitutes its segment (2a); with landmarks it then forms its share of the landmark
@@ -2287,7 +2269,7 @@ int gpslam_hip_iterate_phase2a(gpslam_hip_handle *h) {
     a.blk = h->top_blk.as<Real>(); a.add = nullptr; a.up_blk = nullptr; a.up_add = nullptr;
     a.n = P; a.m = P; a.R = R; a.no_sep = 1; a.last_has_right = 0; a.remote_add = nullptr; a.lambda = Real(0);
     a.flag = h->flag.as<int>(); a.l1_blk = nullptr; a.tail = 0;
-    launch_fwd(h, a, 1);
+    launch_fwd(h, LaunchMode{}, a, 1);
     BwdArgs<Real> bw;
     bw.blk = h->top_blk.as<Real>(); bw.x = h->top_x.as<Real>(); bw.xup = nullptr;
     bw.n = P; bw.m = P; bw.R = R; bw.no_sep = 1; bw.last_has_right = 0;
@@ -2314,7 +2296,7 @@ int gpslam_hip_iterate_phase2b(gpslam_hip_handle *h, gpslam_hip_stats *st) {
   const int b = h->b, R = h->R;
   Real *xtop = h->top_x.as<Real>() + (size_t)h->cfg.rank * b * R;
   if ((rc = launch_landmarks_solve(h, h->ph_lambda))) return rc;
-  if ((rc = launch_retract(h, 2))) return rc;
+  if ((rc = launch_retract(h, LaunchMode{}, 2))) return rc;
   if (has_right_rank(h)) {  // keep the local copy of the neighbour's first state in step with its owner
     if (h->nl > 0) {        // its update needs the landmark correction too: delta = x0 - Z dL on that one block
       LmArgs<Real, RowT> la = lm_args(h, 0.0);
@@ -2331,7 +2313,7 @@ int gpslam_hip_iterate_phase2b(gpslam_hip_handle *h, gpslam_hip_stats *st) {
   }
   // the error of the new state: only when the caller wants statistics (inside a fixed-count run the next
   // iteration's linearisation evaluates it anyway)
-  if (st && (rc = launch_factors(h, 1, 1))) return rc;
+  if (st && (rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;
   HIPCHK(hipGetLastError());
   if (st) {
     double s[4];
@@ -2405,7 +2387,7 @@ int gpslam_hip_fs_phase1(gpslam_hip_handle *h, double lambda) {
   if (rc) return rc;
   if (!h->fs.active || !h->fs.split || h->fs.nb_top <= 0) return fail(h, GPSLAM_E_INVALID, "fs_phase1: set_split before compile(), set_top after it");
   (void)hipSetDevice(h->cfg.device);
-  return fs_split_phase1(h, lambda);
+  return fs_split_phase1(h, lambda, false, true);
 }
 int gpslam_hip_fs_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) {
   int rc = need_compiled(h);
@@ -2424,7 +2406,7 @@ int gpslam_hip_fs_lm_trial_phase1(gpslam_hip_handle *h, double lambda) {
   if (rc) return rc;
   if (!h->fs.active || !h->fs.split || h->fs.nb_top <= 0) return fail(h, GPSLAM_E_INVALID, "fs_lm_trial_phase1: set_split before compile(), set_top after it");
   (void)hipSetDevice(h->cfg.device);
-  return fs_split_phase1(h, lambda, true);
+  return fs_split_phase1(h, lambda, true, true);
 }
 int gpslam_hip_fs_lm_trial_phase2(gpslam_hip_handle *h, double *out6) {
   int rc = need_compiled(h);
@@ -2441,8 +2423,8 @@ int gpslam_hip_fs_lm_trial_phase2(gpslam_hip_handle *h, double *out6) {
   if ((rc = launch_dot(h, h->lm_dL.as<Real>(), h->lm_gL.as<Real>(), h->nl, 5))) return rc;
   k_fs_mask_mul<Real><<<dim3(nblocks(h->nl, 256)), dim3(256), 0, h->stream>>>(h->lm_dL.as<Real>(), p.d_lm_own.as<int>(), h->ld, h->nl, p.lm_tmp.as<Real>());
   if ((rc = launch_dot(h, p.lm_tmp.as<Real>(), h->lm_dL.as<Real>(), h->nl, 6))) return rc;     // |dL|^2, own landmarks
-  if ((rc = launch_retract(h, 2))) return rc;
-  if ((rc = launch_factors(h, 1, 1))) return rc;         // scal[1] = trial error
+  if ((rc = launch_retract(h, LaunchMode{}, 2))) return rc;
+  if ((rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;   // scal[1] = trial error
   double s[8];
   int flag = 0;
   if ((rc = read_scal(h, s, 8, &flag))) return rc;
@@ -2467,7 +2449,7 @@ int gpslam_hip_lm_begin(gpslam_hip_handle *h) {
   if (!sharded(h) && !(h->fs.active && h->fs.split)) return GPSLAM_E_INVALID;
   (void)hipSetDevice(h->cfg.device);
   HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  if ((rc = launch_factors(h, 0, 0))) return rc;        // rows + scal[0] = this rank's error
+  if ((rc = launch_factors(h, LaunchMode{}, 0, 0))) return rc;   // rows + scal[0] = this rank's error
   return backup_state(h, false);
 }
 
@@ -2478,8 +2460,8 @@ int gpslam_hip_lm_trial_phase1(gpslam_hip_handle *h, double lambda) {
   (void)hipSetDevice(h->cfg.device);
   h->ph_lambda = lambda;
   HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  if ((rc = launch_assemble(h, true))) return rc;       // rows are still those of the linearisation point
-  return launch_forward(h, lambda);
+  if ((rc = launch_assemble(h, LaunchMode{}, true))) return rc;   // rows are still those of the linearisation point
+  return launch_forward(h, LaunchMode{}, lambda);
 }
 
 // out6 = {error at the linearisation point, trial error, |delta|_inf, delta . g, |delta|^2, indefinite-pivot flag},
@@ -2510,7 +2492,7 @@ int gpslam_hip_lm_trial_phase2(gpslam_hip_handle *h, double *out6) {
   if (has_right_rank(h)) {
     if ((rc = launch_dot(h, xtop + (size_t)b * R, h->halo_add.as<Real>() + (size_t)b * b, b, 7))) return rc;
   }
-  if ((rc = launch_retract(h, 2))) return rc;
+  if ((rc = launch_retract(h, LaunchMode{}, 2))) return rc;
   if (has_right_rank(h)) {
     RetractArgs<Real> a;
     a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride; a.N = 1; a.R = R;
@@ -2520,7 +2502,7 @@ int gpslam_hip_lm_trial_phase2(gpslam_hip_handle *h, double *out6) {
       k_retract<Real, MF><<<dim3(1), dim3(128), 0, h->stream>>>(a);
     });
   }
-  if ((rc = launch_factors(h, 1, 1))) return rc;         // scal[1] = trial error
+  if ((rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;   // scal[1] = trial error
   double s[8];
   int flag = 0;
   if ((rc = read_scal(h, s, 8, &flag))) return rc;

@@ -42,9 +42,10 @@ ABI_SYMBOLS = [
     "gpslam_hip_interpolate_velocities", "gpslam_hip_body_centric_velocity", "gpslam_hip_last_level0_ms",
     "gpslam_hip_lm_decide", "gpslam_hip_set_collectives", "gpslam_hip_create_v2", "gpslam_hip_abi_version", "gpslam_hip_struct_size",
     "gpslam_hip_add_between_pairs", "gpslam_hip_set_level0_stamps",
+    "gpslam_hip_marginals", "gpslam_hip_get_marginals", "gpslam_hip_interpolate_covariances",
 ]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
-ABI_MAJOR, ABI_MINOR = 2, 2
+ABI_MAJOR, ABI_MINOR = 2, 3
 STRUCT_CONFIG, STRUCT_CONFIG_V2, STRUCT_STATS, STRUCT_PARAMS = 0, 1, 2, 3
 
 
@@ -455,6 +456,31 @@ class ChainSolver:
         self._chk(self.lib.gpslam_hip_interpolate_poses_jac(self._h, len(left), _p(left), _p(dt), _p(tau), _p(out), _p(H)),
                   "interpolate_poses_jac")
         return out, H
+
+    # ---- posterior covariances (gtsam::Marginals)
+    def marginals(self):
+        """gtsam::Marginals(graph, values) at the current states: computes Sigma = H^-1's blocks on the device (see get_marginals)."""
+        return self._chk(self.lib.gpslam_hip_marginals(self._h), "marginals")
+
+    def get_marginals(self, first=0, count=None, cross=False):
+        """Blocks of the last marginals() call for states [first, first + count): S (count, b, b) = Sigma_{i,i} and S_next
+        (count, b, b) = Sigma_{i,i+1}; with landmarks also S_lm (nl, nl) and S_x_lm (count, b, nl).  Returns (S, S_next) or, with
+        cross=True, (S, S_next, S_lm, S_x_lm) (None without landmarks)."""
+        count = self.N - first if count is None else count
+        b, nl = self.b, self.L * self.ld
+        S, Sn = np.zeros((count, b, b)), np.zeros((count, b, b))
+        Slm = np.zeros((nl, nl)) if (cross and nl) else None
+        Sxl = np.zeros((count, b, nl)) if (cross and nl) else None
+        self._chk(self.lib.gpslam_hip_get_marginals(self._h, int(first), int(count), _p(S), _p(Sn), _p(Slm), _p(Sxl)), "get_marginals")
+        return (S, Sn, Slm, Sxl) if cross else (S, Sn)
+
+    def interpolate_covariances(self, left, dt, tau, gp_term=True):
+        """Posterior covariance (count, d, d) of the GP-interpolated pose at tau in (left, left + 1), after marginals()."""
+        left, dt, tau = _i32(left), _f64(dt), _f64(tau)
+        out = np.zeros((len(left), self.d, self.d))
+        self._chk(self.lib.gpslam_hip_interpolate_covariances(self._h, len(left), _p(left), _p(dt), _p(tau), 1 if gp_term else 0, _p(out)),
+                  "interpolate_covariances")
+        return out
 
     def set_level0_stamps(self, on=True):
         """timed iterations stamp the fused level-0 launch with its own dispatch events (exact duration; perturbs the other phases)"""

@@ -153,6 +153,7 @@ int gpslam_hip_destroy(gpslam_hip_handle *h) {
                     &h->api_e, &h->api_H, &h->gps, &h->gpidx, &h->dU, &h->gsave2, &h->partial2, &h->brec, &h->btwidx,
                     &h->rowI, &h->irowptr, &h->coll_s, &h->coll_r, &h->d_clo_second, &h->clo_A, &h->clo_Y, &h->simd_cnt};
   for (DevBuf *b : bufs) b->release();
+  marginals_release(h);
   for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri, &h->clo}) s->release();
   for (MeasSet &s : h->ms) s.release();
   h->fs.release();
@@ -183,6 +184,7 @@ int gpslam_hip_set_stream(gpslam_hip_handle *h, void *stream) {
 }
 
 int gpslam_hip_set_qc(gpslam_hip_handle *h, const double *Qc) {
+  if (h) h->marg_ok = false;   // the marginals of gpslam_hip_marginals are stale from here on
   if (!h || !Qc) return GPSLAM_E_INVALID;
   double U[36], Qpad[36];
   if (h->mf == ROT3_BIAS) {   // Qc is the 3 x 3 of GaussianProcessPriorRot3; bias and pad components: identity (see GpPrior<ROT3_BIAS>)
@@ -201,6 +203,7 @@ int gpslam_hip_set_qc(gpslam_hip_handle *h, const double *Qc) {
 }
 
 int gpslam_hip_set_states(gpslam_hip_handle *h, int32_t N, const double *pose, const double *vel) {
+  if (h) h->marg_ok = false;   // the marginals of gpslam_hip_marginals are stale from here on
   if (!h || N <= 0 || !pose || !vel) return GPSLAM_E_INVALID;
   (void)hipSetDevice(h->cfg.device);
   const bool same = (N == h->N) && h->pose.p;
@@ -226,6 +229,7 @@ int gpslam_hip_set_states(gpslam_hip_handle *h, int32_t N, const double *pose, c
 }
 
 int gpslam_hip_set_halo_state(gpslam_hip_handle *h, const double *pose, const double *vel) {
+  if (h) h->marg_ok = false;   // the marginals of gpslam_hip_marginals are stale from here on
   if (!h || h->N <= 0 || !pose || !vel || !h->pose.p) return GPSLAM_E_INVALID;
   (void)hipSetDevice(h->cfg.device);
   std::vector<double> pv(h->pd), vv(h->d);
@@ -254,6 +258,7 @@ int gpslam_hip_get_states(gpslam_hip_handle *h, double *pose, double *vel) {
 }
 
 int gpslam_hip_set_landmarks(gpslam_hip_handle *h, int32_t L, const double *pts) {
+  if (h) h->marg_ok = false;   // the marginals of gpslam_hip_marginals are stale from here on
   if (!h || L < 0 || (L > 0 && (!pts || h->ld == 0))) return GPSLAM_E_INVALID;
   (void)hipSetDevice(h->cfg.device);
   if (L != h->L) h->compiled = false;
@@ -280,6 +285,7 @@ int gpslam_hip_add_gp_priors(gpslam_hip_handle *h, int32_t count, const int32_t 
   h->gp_dt.insert(h->gp_dt.end(), dt, dt + count);
   h->gp_q.insert(h->gp_q.end(), (size_t)count, 0);
   h->compiled = false;
+  h->marg_ok = false;
   return 0;
 }
 int gpslam_hip_add_gp_priors_qc(gpslam_hip_handle *h, int32_t count, const int32_t *left, const double *dt, const double *Qc) {
@@ -314,6 +320,7 @@ int gpslam_hip_add_gp_priors_qc(gpslam_hip_handle *h, int32_t count, const int32
   h->gp_dt.insert(h->gp_dt.end(), dt, dt + count);
   h->gp_q.insert(h->gp_q.end(), q.begin(), q.end());
   h->compiled = false;
+  h->marg_ok = false;
   return 0;
 }
 int gpslam_hip_set_meas_covariance(gpslam_hip_handle *h, int32_t kind, int32_t count, const double *cov) {
@@ -329,6 +336,7 @@ int gpslam_hip_set_meas_covariance(gpslam_hip_handle *h, int32_t kind, int32_t c
       s.sig[(size_t)(n - count + k)] = std::sqrt(cov[k]);
     }
     h->compiled = false;
+    h->marg_ok = false;
     return 0;
   }
   std::vector<double> R((size_t)count * rows * rows, 0.0);
@@ -341,6 +349,7 @@ int gpslam_hip_set_meas_covariance(gpslam_hip_handle *h, int32_t kind, int32_t c
   }
   std::memcpy(&s.sqi[(size_t)(n - count) * rows * rows], R.data(), R.size() * sizeof(double));
   h->compiled = false;
+  h->marg_ok = false;
   return 0;
 }
 int gpslam_hip_add_pose_priors(gpslam_hip_handle *h, int32_t count, const int32_t *idx, const double *prior,
@@ -379,6 +388,7 @@ int gpslam_hip_add_between_pairs(gpslam_hip_handle *h, int32_t count, const int3
     h->clo.sig.insert(h->clo.sig.end(), sg, sg + h->d);
   }
   h->compiled = false;
+  h->marg_ok = false;
   return 0;
 }
 int gpslam_hip_add_landmark_priors(gpslam_hip_handle *h, int32_t count, const int32_t *idx, const double *prior,
@@ -478,6 +488,7 @@ int gpslam_hip_clear_factors(gpslam_hip_handle *h) {
     s.any_aux = false;
   }
   h->compiled = false;
+  h->marg_ok = false;
   return 0;
 }
 
@@ -659,6 +670,8 @@ int gpslam_hip_body_centric_velocity(gpslam_hip_handle *h, int32_t which, int32_
 // ---- precision dispatch: the handle was created GPSLAM_FP64 or GPSLAM_FP32
 int gpslam_hip_compile(gpslam_hip_handle *h) {
   if (!h) return GPSLAM_E_INVALID;
+  h->marg_ok = false;
+  if (h->marg_N != 0 && h->marg_N != h->N) marginals_release(h);   // (the marginals' buffers are sized by N)
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_compile(h) : impl64::gpslam_hip_compile(h);
 }
 int gpslam_hip_linearize_gp(gpslam_hip_handle *h, double *errors, double *jacobians) {
@@ -674,18 +687,22 @@ int gpslam_hip_error(gpslam_hip_handle *h, double *err) {
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_error(h, err) : impl64::gpslam_hip_error(h, err);
 }
 int gpslam_hip_iterate_gn(gpslam_hip_handle *h, gpslam_hip_stats *st) {
+  if (h) h->marg_ok = false;
   if (!h) return GPSLAM_E_INVALID;
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_iterate_gn(h, st) : impl64::gpslam_hip_iterate_gn(h, st);
 }
 int gpslam_hip_run_gn(gpslam_hip_handle *h, int32_t iters, gpslam_hip_stats *st, double *out5) {
+  if (h) h->marg_ok = false;
   if (!h) return GPSLAM_E_INVALID;
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_run_gn(h, iters, st, out5) : impl64::gpslam_hip_run_gn(h, iters, st, out5);
 }
 int gpslam_hip_iterate_lm(gpslam_hip_handle *h, double *lambda, const gpslam_hip_params *p, gpslam_hip_stats *st) {
+  if (h) h->marg_ok = false;
   if (!h) return GPSLAM_E_INVALID;
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_iterate_lm(h, lambda, p, st) : impl64::gpslam_hip_iterate_lm(h, lambda, p, st);
 }
 int gpslam_hip_optimize(gpslam_hip_handle *h, const gpslam_hip_params *p, gpslam_hip_stats *st) {
+  if (h) h->marg_ok = false;
   if (!h) return GPSLAM_E_INVALID;
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_optimize(h, p, st) : impl64::gpslam_hip_optimize(h, p, st);
 }
@@ -714,6 +731,7 @@ int gpslam_hip_interface_recv(gpslam_hip_handle *h, void **dev_ptr, size_t *byte
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_interface_recv(h, dev_ptr, bytes) : impl64::gpslam_hip_interface_recv(h, dev_ptr, bytes);
 }
 int gpslam_hip_iterate_phase1(gpslam_hip_handle *h, double lambda) {
+  if (h) h->marg_ok = false;
   if (!h) return GPSLAM_E_INVALID;
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_iterate_phase1(h, lambda) : impl64::gpslam_hip_iterate_phase1(h, lambda);
 }
@@ -753,6 +771,7 @@ int gpslam_hip_fs_set_split(gpslam_hip_handle *h, int32_t rank, int32_t nranks, 
   h->fs.first_lm.assign(first_lm, first_lm + n_first);
   h->fs.last_lm.assign(last_lm, last_lm + n_last);
   h->compiled = false;
+  h->marg_ok = false;
   return 0;
 }
 int gpslam_hip_fs_split_info(gpslam_hip_handle *h, int32_t out4[4]) {
@@ -769,6 +788,7 @@ int gpslam_hip_fs_interface(gpslam_hip_handle *h, void **send, size_t *send_byte
                                          : impl64::gpslam_hip_fs_interface(h, send, send_bytes, recv, recv_bytes);
 }
 int gpslam_hip_fs_phase1(gpslam_hip_handle *h, double lambda) {
+  if (h) h->marg_ok = false;
   if (!h) return GPSLAM_E_INVALID;
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_fs_phase1(h, lambda) : impl64::gpslam_hip_fs_phase1(h, lambda);
 }
@@ -777,6 +797,7 @@ int gpslam_hip_fs_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) {
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_fs_phase2(h, st) : impl64::gpslam_hip_fs_phase2(h, st);
 }
 int gpslam_hip_fs_lm_trial_phase1(gpslam_hip_handle *h, double lambda) {
+  if (h) h->marg_ok = false;
   if (!h) return GPSLAM_E_INVALID;
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_fs_lm_trial_phase1(h, lambda) : impl64::gpslam_hip_fs_lm_trial_phase1(h, lambda);
 }
@@ -789,6 +810,7 @@ int gpslam_hip_lm_begin(gpslam_hip_handle *h) {
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_lm_begin(h) : impl64::gpslam_hip_lm_begin(h);
 }
 int gpslam_hip_lm_trial_phase1(gpslam_hip_handle *h, double lambda) {
+  if (h) h->marg_ok = false;
   if (!h) return GPSLAM_E_INVALID;
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_lm_trial_phase1(h, lambda) : impl64::gpslam_hip_lm_trial_phase1(h, lambda);
 }
@@ -797,6 +819,7 @@ int gpslam_hip_lm_trial_phase2(gpslam_hip_handle *h, double *out6) {
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_lm_trial_phase2(h, out6) : impl64::gpslam_hip_lm_trial_phase2(h, out6);
 }
 int gpslam_hip_lm_reject(gpslam_hip_handle *h) {
+  if (h) h->marg_ok = false;
   if (!h) return GPSLAM_E_INVALID;
   return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_lm_reject(h) : impl64::gpslam_hip_lm_reject(h);
 }

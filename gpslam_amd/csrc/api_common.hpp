@@ -154,12 +154,20 @@ struct gpslam_hip_handle {
   int pend_dmax_n = 0, pend_dmax_slot = 0;      // pending: maxima in `partial2`
   double l0_ms = 0.0;         // the level-0 forward launch, accumulated over the last timed run: the dominant kernel INSIDE an iteration
   double ph_lambda = 0.0;
+  // gpslam_hip_marginals (marginals.hip): blocks of H^-1 at the states of the last call; marg_ok is cleared by every call that
+  // can change states, landmarks, factors or Qc
+  bool marg_ok = false;
+  int marg_N = 0;
+  DevBuf mg_fac, mg_S, mg_Sn, mg_up, mg_K, mg_Slm, mg_Sxl;
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch
   int dbg_trace_waves = 0;
 #endif
 };
+
+// frees the marginals' buffers (destroy; compile when N changed)
+void marginals_release(gpslam_hip_handle *h);
 
 // What the launches of one call do: each entry point builds the mode it means and hands it to the launch helpers.
 // LaunchMode{}: row tables (d = 3 records where the graph has them), level 0 unfused, every reduction at once, untimed.
@@ -343,6 +351,7 @@ int add_simple(gpslam_hip_handle *h, SimpleSet &s, int width, int sigw, int32_t 
   s.meas.insert(s.meas.end(), meas, meas + (size_t)count * width);
   s.sig.insert(s.sig.end(), sig, sig + (size_t)count * sigw);
   h->compiled = false;
+  h->marg_ok = false;
   return 0;
 }
 
@@ -389,6 +398,7 @@ int add_meas(gpslam_hip_handle *h, int fk, int rows, int mw, bool two, bool hasl
     if (sensor || calib) s.any_aux = true;
   }
   h->compiled = false;
+  h->marg_ok = false;
   return 0;
 }
 

@@ -32,3 +32,7 @@ int gpslam_hip_optimize(gpslam_hip_handle *h, const gpslam_hip_params *p, gpslam
 int gpslam_hip_run_gn(gpslam_hip_handle *h, int32_t iters, gpslam_hip_stats *st, double *out5);
 int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, double *avg_ms);
 int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot, bool e32);
+// gpslam_hip_marginals (marginals.hip): the assembly of gpslam_hip_normal_equations; then the solver's right-hand sides at
+// lambda = 0 (forward, backward, closure correction) and the landmark Schur complement, without the landmark solve
+int marginals_assemble(gpslam_hip_handle *h);
+int marginals_border(gpslam_hip_handle *h);

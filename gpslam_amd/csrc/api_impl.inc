@@ -2072,6 +2072,22 @@ int gpslam_hip_normal_equations(gpslam_hip_handle *h, double *D, double *O, doub
   return 0;
 }
 
+// gpslam_hip_marginals (marginals.hip): the records of the current linearisation, as gpslam_hip_normal_equations assembles them
+int marginals_assemble(gpslam_hip_handle *h) {
+  int rc;
+  if ((rc = launch_factors(h, LaunchMode{}, 0, 0))) return rc;
+  return launch_assemble(h, LaunchMode{}, false);
+}
+// ... and the solver's right-hand sides at lambda = 0: the closure columns Z = A^-1 J_c^T, the landmark columns corrected for the
+// closures, and the landmark Schur complement S of the whole chain -- launch_solve without the landmark solve (the states stay)
+int marginals_border(gpslam_hip_handle *h) {
+  int rc;
+  if ((rc = launch_forward(h, LaunchMode{}, 0.0))) return rc;
+  if ((rc = launch_backward(h, nullptr))) return rc;
+  if ((rc = launch_closures(h))) return rc;
+  return launch_landmarks_reduce(h, 0.0);
+}
+
 // whitened Jacobian rows of the current linearisation, in row-table order (rows grouped by left state; inside a
 // state: GP priors, pose priors, velocity priors, between, then the measurement kinds in FKind order)
 int gpslam_hip_get_rows(gpslam_hip_handle *h, int32_t *n_rows, double *rowLR, double *rowE, double *rowM, int32_t *rowLm) {

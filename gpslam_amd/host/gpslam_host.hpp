@@ -822,6 +822,141 @@ class LevenbergMarquardtOptimizer : public NonlinearOptimizer {
   double lambda_;
 };
 
+// ---------------------------------------------------------------- gtsam::Marginals (gtsam/nonlinear/Marginals.h, GTSAM 4.0)
+typedef std::vector<Key> KeyVector;
+
+/// gtsam::JointMarginal: the joint covariance of a key set, block (k1, k2) or the whole matrix in the order of the keys given
+class JointMarginal {
+ public:
+  Matrix operator()(Key k1, Key k2) const {
+    const size_t i = at(k1), j = at(k2);
+    Matrix m(dim_[i], dim_[j]);
+    for (int r = 0; r < dim_[i]; r++)
+      for (int c = 0; c < dim_[j]; c++) m(r, c) = full_(off_[i] + r, off_[j] + c);
+    return m;
+  }
+  const Matrix &fullMatrix() const { return full_; }
+ private:
+  friend class Marginals;
+  size_t at(Key k) const {
+    for (size_t i = 0; i < keys_.size(); i++) if (keys_[i] == k) return i;
+    throw std::invalid_argument("JointMarginal: key not in this joint marginal");
+  }
+  KeyVector keys_;
+  std::vector<int> off_, dim_;
+  Matrix full_;
+};
+
+/// gtsam::Marginals(graph, values): the Gauss-Newton Hessian of the whole graph at `values`, inverted on the device
+/// (gpslam_hip_marginals).  Served: single keys (x, v, w, b and landmark keys), joint sets whose state keys belong to one
+/// state or to two adjacent states, with any landmarks; other sets throw std::invalid_argument.
+class Marginals {
+ public:
+  Marginals(const NonlinearFactorGraph &graph, const Values &values) {
+    s_.build(graph, values);
+    detail::check(gpslam_hip_marginals(s_.h), s_.h, "marginals");
+  }
+  /// Marginals::marginalCovariance(variable)
+  Matrix marginalCovariance(Key k) const { return jointMarginalCovariance(KeyVector{k}).fullMatrix(); }
+  /// Marginals::marginalInformation(variable): the inverse of the marginal covariance
+  Matrix marginalInformation(Key k) const { return inverse(marginalCovariance(k)); }
+  /// Marginals::jointMarginalCovariance(variables)
+  JointMarginal jointMarginalCovariance(const KeyVector &keys) const {
+    if (keys.empty()) throw std::invalid_argument("jointMarginalCovariance: no keys");
+    std::vector<Var> vars;
+    int lo = -1, hi = -1;
+    for (Key k : keys) {
+      const Var v = var_of(k);
+      if (v.state >= 0) { lo = lo < 0 ? v.state : std::min(lo, v.state); hi = std::max(hi, v.state); }
+      vars.push_back(v);
+    }
+    if (lo >= 0 && hi - lo > 1)
+      throw std::invalid_argument("jointMarginalCovariance: the keys span non-adjacent states; only one state or two adjacent states (with any landmarks) are served");
+    const int b = 2 * s_.d, nl = s_.L * s_.ld, first = lo < 0 ? 0 : lo, count = lo < 0 ? 0 : hi - lo + 1;
+    std::vector<double> S((size_t)std::max(count, 1) * b * b), Sn(S.size()), Slm((size_t)std::max(nl * nl, 1)),
+        Sxl((size_t)std::max(count * b * nl, 1));
+    detail::check(gpslam_hip_get_marginals(s_.h, first, count, count ? S.data() : nullptr, count ? Sn.data() : nullptr,
+                                           nl ? Slm.data() : nullptr, (count && nl) ? Sxl.data() : nullptr), s_.h, "get_marginals");
+    // one coordinate of the set: (state - first) * b + c for a state, or -1 - c for landmark coordinate c
+    auto cov = [&](int p, int q) -> double {
+      if (p >= 0 && q >= 0) {
+        const int sp = p / b, sq = q / b, cp = p % b, cq = q % b;
+        if (sp == sq) return S[(size_t)sp * b * b + cp * b + cq];
+        return sp < sq ? Sn[(size_t)sp * b * b + cp * b + cq] : Sn[(size_t)sq * b * b + cq * b + cp];
+      }
+      if (p < 0 && q < 0) return Slm[(size_t)(-1 - p) * nl + (-1 - q)];
+      if (p >= 0) return Sxl[((size_t)(p / b) * b + p % b) * nl + (-1 - q)];
+      return Sxl[((size_t)(q / b) * b + q % b) * nl + (-1 - p)];
+    };
+    JointMarginal jm;
+    jm.keys_ = keys;
+    std::vector<int> coord;
+    for (const Var &v : vars) {
+      jm.off_.push_back((int)coord.size());
+      jm.dim_.push_back(v.dim);
+      for (int c = 0; c < v.dim; c++) coord.push_back(v.state >= 0 ? (v.state - first) * b + v.off + c : -1 - (v.off + c));
+    }
+    const int n = (int)coord.size();
+    jm.full_ = Matrix(n, n);
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < n; j++) jm.full_(i, j) = cov(coord[i], coord[j]);
+    return jm;
+  }
+  /// Posterior covariance (d x d) of the GP-interpolated pose at tau[q] after the state with pose key left[q] (interval dt[q]):
+  /// gpslam_hip_interpolate_covariances, the covariance half of NonlinearOptimizer::interpolatePoses
+  std::vector<Matrix> interpolatePoseCovariances(const KeyVector &left, const std::vector<double> &dt, const std::vector<double> &tau) const {
+    if (left.size() != dt.size() || left.size() != tau.size()) throw std::invalid_argument("interpolatePoseCovariances: size mismatch");
+    std::vector<int32_t> idx(left.size());
+    for (size_t q = 0; q < left.size(); q++) idx[q] = s_.state_of(left[q]);
+    const int d = s_.d;
+    std::vector<double> out(left.size() * (size_t)d * d);
+    detail::check(gpslam_hip_interpolate_covariances(s_.h, (int32_t)left.size(), idx.data(), dt.data(), tau.data(), 1, out.data()), s_.h,
+                  "interpolate_covariances");
+    std::vector<Matrix> r;
+    for (size_t q = 0; q < left.size(); q++) {
+      Matrix m(d, d);
+      std::copy(out.begin() + q * d * d, out.begin() + (q + 1) * d * d, m.a.begin());
+      r.push_back(m);
+    }
+    return r;
+  }
+  /// the C-ABI handle behind these marginals
+  gpslam_hip_handle *handle() const { return s_.h; }
+
+ private:
+  struct Var { int state, off, dim; };   // state -1: landmark coordinates off .. off + dim
+  Var var_of(Key k) const {
+    auto it = s_.values.raw().find(k);
+    if (it == s_.values.raw().end()) throw std::invalid_argument("Marginals: key not in the Values");
+    const unsigned char c = symbolChr(k);
+    const int d = s_.d;
+    if (it->second.type == detail::T_POINT2 || it->second.type == detail::T_POINT3) return {-1, s_.lm_of(k) * s_.ld, s_.ld};
+    if (c == 'v') return {s_.state_of(k), d, (s_.vw || s_.bias) ? 3 : d};
+    if (s_.vw && c == 'w') return {s_.state_of(k), d + 3, 3};
+    if (s_.bias && c == 'b') return {s_.state_of(k), 3, 3};
+    return {s_.state_of(k), 0, s_.bias ? 3 : d};
+  }
+  static Matrix inverse(Matrix m) {   // Gauss-Jordan with partial pivoting
+    const int n = m.rows;
+    Matrix r = Matrix::Identity(n);
+    for (int k = 0; k < n; k++) {
+      int p = k;
+      for (int i = k + 1; i < n; i++) if (std::fabs(m(i, k)) > std::fabs(m(p, k))) p = i;
+      if (m(p, k) == 0.0) throw std::runtime_error("marginalInformation: singular marginal covariance");
+      for (int j = 0; j < n; j++) { std::swap(m(k, j), m(p, j)); std::swap(r(k, j), r(p, j)); }
+      const double piv = 1.0 / m(k, k);
+      for (int j = 0; j < n; j++) { m(k, j) *= piv; r(k, j) *= piv; }
+      for (int i = 0; i < n; i++) {
+        if (i == k) continue;
+        const double f = m(i, k);
+        for (int j = 0; j < n; j++) { m(i, j) -= f * m(k, j); r(i, j) -= f * r(k, j); }
+      }
+    }
+    return r;
+  }
+  detail::Session s_;
+};
+
 // ---------------------------------------------------------------- AHRS (gtsam/navigation/AHRSFactor.h, GTSAM 4.0; third party)
 /// gtsam::PreintegratedAhrsMeasurements(biasHat, measuredOmegaCovariance): the constructor matlab/GPAHRSexample.m:188 uses.
 /// integrateMeasurement restates PreintegratedRotation::integrateMeasurement + the covariance propagation of AHRSFactor.cpp:

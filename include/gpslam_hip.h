@@ -77,10 +77,11 @@ enum {
  * through a corrupted stack.  History: 1.0 rounds 1-4 (gpslam_hip_stats 48 bytes); 1.1 round 5 (stats 56 bytes: trials,
  * last_trial_error; GPSLAM_E_COMM; plan bits 64, 128) -- shipped without a version symbol; 2.0 this header: gpslam_hip_config_v2 +
  * gpslam_hip_create_v2 (named fields, struct_size first), gpslam_hip_abi_version, gpslam_hip_struct_size.  The v1 config and
- * gpslam_hip_create stay, bit for bit; 2.1 gpslam_hip_add_between_pairs (loop closures); 2.2 gpslam_hip_set_level0_stamps.  A MAJOR bump changes a struct or a
+ * gpslam_hip_create stay, bit for bit; 2.1 gpslam_hip_add_between_pairs (loop closures); 2.2 gpslam_hip_set_level0_stamps; 2.3
+ * gpslam_hip_marginals, gpslam_hip_get_marginals, gpslam_hip_interpolate_covariances.  A MAJOR bump changes a struct or a
  * signature, a MINOR bump only adds. */
 #define GPSLAM_HIP_ABI_MAJOR 2
-#define GPSLAM_HIP_ABI_MINOR 2
+#define GPSLAM_HIP_ABI_MINOR 3
 #define GPSLAM_HIP_ABI_VERSION ((GPSLAM_HIP_ABI_MAJOR << 16) | GPSLAM_HIP_ABI_MINOR)
 uint32_t gpslam_hip_abi_version(void);
 enum { GPSLAM_STRUCT_CONFIG = 0, GPSLAM_STRUCT_CONFIG_V2 = 1, GPSLAM_STRUCT_STATS = 2, GPSLAM_STRUCT_PARAMS = 3 };
@@ -351,6 +352,35 @@ int gpslam_hip_interpolate_poses(gpslam_hip_handle *h, int32_t count, const int3
  * out_H count x 4 x d x d = H1..H4 of interpolatePose (gpslam/gp/GaussianProcessInterpolatorPose3.h:82-98, gpslam.h:57-86) */
 int gpslam_hip_interpolate_poses_jac(gpslam_hip_handle *h, int32_t count, const int32_t *left, const double *dt,
                                      const double *tau, double *out_pose, double *out_H);
+/* ---- posterior covariances (ABI 2.3) ----
+ * gtsam::Marginals(graph, values) at the current states and landmarks (GTSAM 4.0 gtsam/nonlinear/Marginals.h): H = J^T J of the whole
+ * whitened graph -- chain factors, measurement factors, landmark priors, loop closures; no Levenberg-Marquardt damping -- in the
+ * columns of gpslam_hip_normal_equations (state i: [pose tangent (d) | velocity (d)], b = 2d, in the handle's chart; then the
+ * landmarks, landmark_dim each), and the blocks of Sigma = H^-1 that the chain's structure makes cheap:
+ *   S[i]       b x b   Sigma_{i,i}                  (Marginals::marginalCovariance of x_i / v_i: its diagonal blocks)
+ *   S_next[i]  b x b   Sigma_{i,i+1} (rows: state i; the last state's block is zero)   (jointMarginalCovariance({x_i, x_i+1}))
+ *   S_lm       nl x nl Sigma_{L,L}, every landmark coordinate jointly, nl = L * landmark_dim
+ *   S_x_lm[i]  b x nl  Sigma_{i,L}
+ * The three pad coordinates of GPSLAM_ROT3_BIAS's velocity slot report zero rows and columns; the VW family reports its velocity
+ * slot as stored, [v; w].  Computed on the device (selected inversion of the block-tridiagonal chain, landmarks and closures as a
+ * low-rank term) and kept there.  GPSLAM_E_UNSUPPORTED on fp32 handles, sharded handles, split pieces and the segmented landmark
+ * path; GPSLAM_E_NOT_SPD when H is indeterminate (e.g. nothing anchors the chain), as iterate_gn. */
+int gpslam_hip_marginals(gpslam_hip_handle *h);
+/* copies the window [first, first + count) of S / S_next / S_x_lm (count x b x b, count x b x b, count x b x nl), and S_lm; any pointer
+ * may be NULL.  GPSLAM_E_INVALID ("stale") before gpslam_hip_marginals, or after any call that can change states, landmarks,
+ * factors or Qc since: set_states, set_landmarks, set_qc, add_*, set_meas_covariance, clear_factors, compile, iterate_gn, iterate_lm,
+ * run_gn, optimize. */
+int gpslam_hip_get_marginals(gpslam_hip_handle *h, int32_t first, int32_t count, double *S, double *S_next, double *S_lm,
+                             double *S_x_lm);
+/* Posterior covariance (count x d x d) of the GP-interpolated pose at tau[q] in (left[q], left[q] + 1), batched like
+ * interpolate_poses -- the covariance half of the sparse-GP interpolation (Barfoot, Tong & Sarkka, RSS 2014), which GTSAM has no
+ * call for:  P(tau) = H_J Sigma_J H_J^T + gp_term * c(dt, tau) * Qc,  H_J = [H1 H2 H3 H4] of interpolate_poses_jac,
+ * Sigma_J = [[S[i], S_next[i]], [S_next[i]^T, S[i+1]]],  c = tau^3 (dt - tau)^3 / (3 dt^3): c Qc is the pose block of the GP's
+ * conditional covariance Q(tau) - Psi Phi(dt - tau) Q(tau) (gpslam/gp/GPutils.h:24-71) for the handle's Qc (GPSLAM_ROT3_BIAS: on
+ * the rotation; the bias is held over the interval).  Exact on GPSLAM_LINEAR2 / GPSLAM_LINEAR3 with gp_term = 1; on the Lie groups
+ * first order in the local variable.  Same refusals and staleness rule as gpslam_hip_get_marginals. */
+int gpslam_hip_interpolate_covariances(gpslam_hip_handle *h, int32_t count, const int32_t *left, const double *dt,
+                                       const double *tau, int32_t gp_term, double *out_cov);
 /* GaussianProcessInterpolatorLinear<D>::interpolateVelocity (gpslam.h:193, gpslam/gp/GaussianProcessInterpolatorLinear.h:106-126)
  * of the current estimate, batched like interpolate_poses: out_vel count x d; out_H (may be NULL) count x 4 x d x d = H1..H4
  * (:117-120, the lower blocks of Lambda and Psi).  GPSLAM_LINEAR2 / GPSLAM_LINEAR3 handles; the reference declares the method

@@ -667,89 +667,68 @@ int gpslam_hip_body_centric_velocity(gpslam_hip_handle *h, int32_t which, int32_
   return 0;
 }
 
-// ---- precision dispatch: the handle was created GPSLAM_FP64 or GPSLAM_FP32
+// ---- precision dispatch: the handle was created GPSLAM_FP64 or GPSLAM_FP32.  The one forwarder: null check, then the namespace.
+#define GPS_BY_PRECISION(name, h, ...) \
+  (!(h) ? GPSLAM_E_INVALID : (h)->cfg.precision == GPSLAM_FP32 ? impl32::name(h, ##__VA_ARGS__) : impl64::name(h, ##__VA_ARGS__))
+// in front of every forwarder that moves the estimate (a step, a trial, a reject): covariances held from before are stale
+static void invalidates_marginals(gpslam_hip_handle *h) { if (h) h->marg_ok = false; }
+
 int gpslam_hip_compile(gpslam_hip_handle *h) {
   if (!h) return GPSLAM_E_INVALID;
   h->marg_ok = false;
   if (h->marg_N != 0 && h->marg_N != h->N) marginals_release(h);   // (the marginals' buffers are sized by N)
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_compile(h) : impl64::gpslam_hip_compile(h);
+  return GPS_BY_PRECISION(gpslam_hip_compile, h);
 }
 int gpslam_hip_linearize_gp(gpslam_hip_handle *h, double *errors, double *jacobians) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_linearize_gp(h, errors, jacobians) : impl64::gpslam_hip_linearize_gp(h, errors, jacobians);
+  return GPS_BY_PRECISION(gpslam_hip_linearize_gp, h, errors, jacobians);
 }
 int gpslam_hip_linearize_meas(gpslam_hip_handle *h, int32_t kind, double *errors, double *jacobians) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_linearize_meas(h, kind, errors, jacobians) : impl64::gpslam_hip_linearize_meas(h, kind, errors, jacobians);
+  return GPS_BY_PRECISION(gpslam_hip_linearize_meas, h, kind, errors, jacobians);
 }
-int gpslam_hip_error(gpslam_hip_handle *h, double *err) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_error(h, err) : impl64::gpslam_hip_error(h, err);
-}
+int gpslam_hip_error(gpslam_hip_handle *h, double *err) { return GPS_BY_PRECISION(gpslam_hip_error, h, err); }
 int gpslam_hip_iterate_gn(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  if (h) h->marg_ok = false;
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_iterate_gn(h, st) : impl64::gpslam_hip_iterate_gn(h, st);
+  invalidates_marginals(h);
+  return GPS_BY_PRECISION(gpslam_hip_iterate_gn, h, st);
 }
 int gpslam_hip_run_gn(gpslam_hip_handle *h, int32_t iters, gpslam_hip_stats *st, double *out5) {
-  if (h) h->marg_ok = false;
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_run_gn(h, iters, st, out5) : impl64::gpslam_hip_run_gn(h, iters, st, out5);
+  invalidates_marginals(h);
+  return GPS_BY_PRECISION(gpslam_hip_run_gn, h, iters, st, out5);
 }
 int gpslam_hip_iterate_lm(gpslam_hip_handle *h, double *lambda, const gpslam_hip_params *p, gpslam_hip_stats *st) {
-  if (h) h->marg_ok = false;
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_iterate_lm(h, lambda, p, st) : impl64::gpslam_hip_iterate_lm(h, lambda, p, st);
+  invalidates_marginals(h);
+  return GPS_BY_PRECISION(gpslam_hip_iterate_lm, h, lambda, p, st);
 }
 int gpslam_hip_optimize(gpslam_hip_handle *h, const gpslam_hip_params *p, gpslam_hip_stats *st) {
-  if (h) h->marg_ok = false;
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_optimize(h, p, st) : impl64::gpslam_hip_optimize(h, p, st);
+  invalidates_marginals(h);
+  return GPS_BY_PRECISION(gpslam_hip_optimize, h, p, st);
 }
 int gpslam_hip_normal_equations(gpslam_hip_handle *h, double *D, double *O, double *g, double *B) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_normal_equations(h, D, O, g, B) : impl64::gpslam_hip_normal_equations(h, D, O, g, B);
+  return GPS_BY_PRECISION(gpslam_hip_normal_equations, h, D, O, g, B);
 }
 int gpslam_hip_get_rows(gpslam_hip_handle *h, int32_t *n_rows, double *rowLR, double *rowE, double *rowM, int32_t *rowLm) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_get_rows(h, n_rows, rowLR, rowE, rowM, rowLm) : impl64::gpslam_hip_get_rows(h, n_rows, rowLR, rowE, rowM, rowLm);
+  return GPS_BY_PRECISION(gpslam_hip_get_rows, h, n_rows, rowLR, rowE, rowM, rowLm);
 }
 int gpslam_hip_block_tridiag_solve(gpslam_hip_handle *h, int32_t N, const double *D, const double *O, const double *g, double *x) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_block_tridiag_solve(h, N, D, O, g, x) : impl64::gpslam_hip_block_tridiag_solve(h, N, D, O, g, x);
+  return GPS_BY_PRECISION(gpslam_hip_block_tridiag_solve, h, N, D, O, g, x);
 }
 int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, double *avg_ms) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_time_kernel(h, which, reps, avg_ms) : impl64::gpslam_hip_time_kernel(h, which, reps, avg_ms);
+  return GPS_BY_PRECISION(gpslam_hip_time_kernel, h, which, reps, avg_ms);
 }
 int gpslam_hip_interface_send(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_interface_send(h, dev_ptr, bytes) : impl64::gpslam_hip_interface_send(h, dev_ptr, bytes);
+  return GPS_BY_PRECISION(gpslam_hip_interface_send, h, dev_ptr, bytes);
 }
 int gpslam_hip_interface_recv(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_interface_recv(h, dev_ptr, bytes) : impl64::gpslam_hip_interface_recv(h, dev_ptr, bytes);
+  return GPS_BY_PRECISION(gpslam_hip_interface_recv, h, dev_ptr, bytes);
 }
 int gpslam_hip_iterate_phase1(gpslam_hip_handle *h, double lambda) {
-  if (h) h->marg_ok = false;
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_iterate_phase1(h, lambda) : impl64::gpslam_hip_iterate_phase1(h, lambda);
+  invalidates_marginals(h);
+  return GPS_BY_PRECISION(gpslam_hip_iterate_phase1, h, lambda);
 }
-int gpslam_hip_iterate_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_iterate_phase2(h, st) : impl64::gpslam_hip_iterate_phase2(h, st);
-}
-int gpslam_hip_iterate_phase2a(gpslam_hip_handle *h) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_iterate_phase2a(h) : impl64::gpslam_hip_iterate_phase2a(h);
-}
-int gpslam_hip_iterate_phase2b(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_iterate_phase2b(h, st) : impl64::gpslam_hip_iterate_phase2b(h, st);
-}
+int gpslam_hip_iterate_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) { return GPS_BY_PRECISION(gpslam_hip_iterate_phase2, h, st); }
+int gpslam_hip_iterate_phase2a(gpslam_hip_handle *h) { return GPS_BY_PRECISION(gpslam_hip_iterate_phase2a, h); }
+int gpslam_hip_iterate_phase2b(gpslam_hip_handle *h, gpslam_hip_stats *st) { return GPS_BY_PRECISION(gpslam_hip_iterate_phase2b, h, st); }
 int gpslam_hip_landmark_reduce_buffer(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_landmark_reduce_buffer(h, dev_ptr, bytes) : impl64::gpslam_hip_landmark_reduce_buffer(h, dev_ptr, bytes);
+  return GPS_BY_PRECISION(gpslam_hip_landmark_reduce_buffer, h, dev_ptr, bytes);
 }
 int gpslam_hip_fs_set_split(gpslam_hip_handle *h, int32_t rank, int32_t nranks, const int32_t *first_lm, int32_t n_first,
                             const int32_t *last_lm, int32_t n_last) {
@@ -774,54 +753,24 @@ int gpslam_hip_fs_set_split(gpslam_hip_handle *h, int32_t rank, int32_t nranks, 
   h->marg_ok = false;
   return 0;
 }
-int gpslam_hip_fs_split_info(gpslam_hip_handle *h, int32_t out4[4]) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_fs_split_info(h, out4) : impl64::gpslam_hip_fs_split_info(h, out4);
-}
-int gpslam_hip_fs_set_top(gpslam_hip_handle *h, int32_t nb_top) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_fs_set_top(h, nb_top) : impl64::gpslam_hip_fs_set_top(h, nb_top);
-}
+int gpslam_hip_fs_split_info(gpslam_hip_handle *h, int32_t out4[4]) { return GPS_BY_PRECISION(gpslam_hip_fs_split_info, h, out4); }
+int gpslam_hip_fs_set_top(gpslam_hip_handle *h, int32_t nb_top) { return GPS_BY_PRECISION(gpslam_hip_fs_set_top, h, nb_top); }
 int gpslam_hip_fs_interface(gpslam_hip_handle *h, void **send, size_t *send_bytes, void **recv, size_t *recv_bytes) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_fs_interface(h, send, send_bytes, recv, recv_bytes)
-                                         : impl64::gpslam_hip_fs_interface(h, send, send_bytes, recv, recv_bytes);
+  return GPS_BY_PRECISION(gpslam_hip_fs_interface, h, send, send_bytes, recv, recv_bytes);
 }
-int gpslam_hip_fs_phase1(gpslam_hip_handle *h, double lambda) {
-  if (h) h->marg_ok = false;
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_fs_phase1(h, lambda) : impl64::gpslam_hip_fs_phase1(h, lambda);
-}
-int gpslam_hip_fs_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_fs_phase2(h, st) : impl64::gpslam_hip_fs_phase2(h, st);
-}
+int gpslam_hip_fs_phase1(gpslam_hip_handle *h, double lambda) { invalidates_marginals(h); return GPS_BY_PRECISION(gpslam_hip_fs_phase1, h, lambda); }
+int gpslam_hip_fs_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) { return GPS_BY_PRECISION(gpslam_hip_fs_phase2, h, st); }
 int gpslam_hip_fs_lm_trial_phase1(gpslam_hip_handle *h, double lambda) {
-  if (h) h->marg_ok = false;
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_fs_lm_trial_phase1(h, lambda) : impl64::gpslam_hip_fs_lm_trial_phase1(h, lambda);
+  invalidates_marginals(h);
+  return GPS_BY_PRECISION(gpslam_hip_fs_lm_trial_phase1, h, lambda);
 }
-int gpslam_hip_fs_lm_trial_phase2(gpslam_hip_handle *h, double *out6) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_fs_lm_trial_phase2(h, out6) : impl64::gpslam_hip_fs_lm_trial_phase2(h, out6);
-}
-int gpslam_hip_lm_begin(gpslam_hip_handle *h) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_lm_begin(h) : impl64::gpslam_hip_lm_begin(h);
-}
+int gpslam_hip_fs_lm_trial_phase2(gpslam_hip_handle *h, double *out6) { return GPS_BY_PRECISION(gpslam_hip_fs_lm_trial_phase2, h, out6); }
+int gpslam_hip_lm_begin(gpslam_hip_handle *h) { return GPS_BY_PRECISION(gpslam_hip_lm_begin, h); }
 int gpslam_hip_lm_trial_phase1(gpslam_hip_handle *h, double lambda) {
-  if (h) h->marg_ok = false;
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_lm_trial_phase1(h, lambda) : impl64::gpslam_hip_lm_trial_phase1(h, lambda);
+  invalidates_marginals(h);
+  return GPS_BY_PRECISION(gpslam_hip_lm_trial_phase1, h, lambda);
 }
-int gpslam_hip_lm_trial_phase2(gpslam_hip_handle *h, double *out6) {
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_lm_trial_phase2(h, out6) : impl64::gpslam_hip_lm_trial_phase2(h, out6);
-}
-int gpslam_hip_lm_reject(gpslam_hip_handle *h) {
-  if (h) h->marg_ok = false;
-  if (!h) return GPSLAM_E_INVALID;
-  return h->cfg.precision == GPSLAM_FP32 ? impl32::gpslam_hip_lm_reject(h) : impl64::gpslam_hip_lm_reject(h);
-}
+int gpslam_hip_lm_trial_phase2(gpslam_hip_handle *h, double *out6) { return GPS_BY_PRECISION(gpslam_hip_lm_trial_phase2, h, out6); }
+int gpslam_hip_lm_reject(gpslam_hip_handle *h) { invalidates_marginals(h); return GPS_BY_PRECISION(gpslam_hip_lm_reject, h); }
 
 }  // extern "C"

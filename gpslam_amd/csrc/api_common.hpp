@@ -1,4 +1,5 @@
-// api_common.hpp -- what the three translation units of the library share: the handle, the host helpers and the kernel launchers
+// api_common.hpp -- what the translation units of the library's host side share (api.hip: the C ABI; api_impl64.hip / api_impl32.hip:
+// api_impl.inc + api_iterate.inc once per row precision; marginals.hip): the handle, the host helpers and the kernel launchers
 // (round 3: api.hip was one 3.5-minute translation unit; the fp64 and fp32 halves compile side by side now)
 #pragma once
 // api.hip -- host side of libgpslam_hip.so: the opaque handle, the graph-compile pass and the C ABI
@@ -337,6 +338,13 @@ int need_compiled(gpslam_hip_handle *h) {
   if (!h) return GPSLAM_E_INVALID;
   if (!h->compiled) return fail(h, GPSLAM_E_NOT_COMPILED, "call gpslam_hip_compile() first");
   return 0;
+}
+// ... and its device current: the opening of every call that works on this handle's own share of the chain, whatever the scheme
+// (api_iterate.inc has the guards that also ask for a kind of handle)
+int need_local(gpslam_hip_handle *h) {
+  int rc = need_compiled(h);
+  if (!rc) (void)hipSetDevice(h->cfg.device);
+  return rc;
 }
 
 int add_simple(gpslam_hip_handle *h, SimpleSet &s, int width, int sigw, int32_t count, const int32_t *idx,

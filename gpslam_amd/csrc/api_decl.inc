@@ -1,4 +1,4 @@
-// api_decl.inc -- the entry points of a precision namespace (api_impl.inc), included inside namespace impl64 / impl32 by
+// api_decl.inc -- the entry points of a precision namespace (api_impl.inc, api_iterate.inc), included inside namespace impl64 / impl32 by
 // every translation unit that calls across them
 int gpslam_hip_block_tridiag_solve(gpslam_hip_handle *h, int32_t N, const double *D, const double *O,
                                    const double *g, double *x);

@@ -1,6 +1,7 @@
-// api_impl.inc -- the precision-dependent half of libgpslam_hip.so's host side.  api.hip includes this file twice, inside
-// namespace impl64 (RowT = double: GPSLAM_FP64) and namespace impl32 (RowT = float: GPSLAM_FP32); the extern "C" entry
-// points in api.hip dispatch on the handle's precision.  RowT is the type the factor kernels compute the Jacobians in
+// api_impl.inc -- the precision-dependent half of libgpslam_hip.so's host side: argument packing and launches, compile(), the
+// inspection calls.  The iteration driver follows it in api_iterate.inc.  Both are included twice, by api_impl64.hip inside
+// namespace impl64 (RowT = double: GPSLAM_FP64) and by api_impl32.hip inside namespace impl32 (RowT = float: GPSLAM_FP32); the
+// extern "C" entry points in api.hip dispatch on the handle's precision (GPS_BY_PRECISION).  RowT is the type the factor kernels compute the Jacobians in
 // and of the row tables in HBM (the dominant traffic of an iteration); Real -- the normal equations and the solver -- is
 // double in both: J^T J squares the condition number, and a 1e5-state chain anchored by one prior (BASELINE config 3) is
 // beyond what an fp32 factorisation survives (measured: non-positive pivots).  States, landmarks and factor parameters
@@ -779,8 +780,6 @@ FsArgs<Real, RowT> fs_top_args(gpslam_hip_handle *h) {
   return t;
 }
 
-int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot);
-int launch_dot(gpslam_hip_handle *h, const Real *x, const Real *y, int n, int slot);
 
 // lm_trial: the rows are those of the linearisation point (gpslam_hip_lm_begin); the assembly also stores the gradient.
 // clear_flag = false: inside a multi-iteration run (dist_run_gn) the non-positive-pivot flag is sticky
@@ -826,27 +825,6 @@ int fs_split_solve(gpslam_hip_handle *h) {
   return fs_backward(h, h->ph_lambda);
 }
 
-int fs_split_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  int rc;
-  if ((rc = fs_split_solve(h))) return rc;
-  if ((rc = launch_retract(h, LaunchMode{}, 2))) return rc;
-  if (st && (rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;
-  HIPCHK(hipGetLastError());
-  if (st) {
-    double sc[4];
-    int flag = 0;
-    if ((rc = read_scal(h, sc, 4, &flag))) return rc;
-    std::memset(st, 0, sizeof(*st));
-    st->error_before = sc[0];
-    st->error_after = sc[1];
-    st->delta_inf_norm = sc[2];
-    st->iterations = 1;
-    st->accepted = 1;
-    st->status = flag ? GPSLAM_E_NOT_SPD : 0;
-    if (flag) return fail(h, GPSLAM_E_NOT_SPD, "non-positive pivot in the block elimination");
-  }
-  return 0;
-}
 
 // compile(): segment plan, level sets of the cyclic reduction, buffers.  per_lm: rows touching each landmark (row, left
 // state), sorted by state; touch_hi: last state touched.
@@ -1536,10 +1514,9 @@ int gpslam_hip_compile(gpslam_hip_handle *h) {
 
 int gpslam_hip_linearize_gp(gpslam_hip_handle *h, double *errors, double *jacobians) {
   if (!kIsF64) return impl64::gpslam_hip_linearize_gp(h, errors, jacobians);   // the inspection API answers in fp64
-  int rc = need_compiled(h);
+  int rc = need_local(h);
   if (rc) return rc;
   if (!errors) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
   const int F = (int)h->gp_left.size(), b = h->b, d = h->d;
   if (F == 0) return 0;
   HIPCHK(h->api_e.reserve((size_t)F * b * sizeof(RowT)));
@@ -1572,10 +1549,9 @@ int gpslam_hip_linearize_gp(gpslam_hip_handle *h, double *errors, double *jacobi
 // unwhitened evaluateError + H1..H5 of every measurement factor of one kind, in the order they were added
 int gpslam_hip_linearize_meas(gpslam_hip_handle *h, int32_t kind, double *errors, double *jacobians) {
   if (!kIsF64) return impl64::gpslam_hip_linearize_meas(h, kind, errors, jacobians);   // the inspection API answers in fp64
-  int rc = need_compiled(h);
+  int rc = need_local(h);
   if (rc) return rc;
   if (kind < 0 || kind >= kNumMeasKinds || !errors) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
   MeasSet &s = h->ms[kind];
   const int F = s.count(), b = h->b, W = 2 * b + 3;
   if (F == 0) return 0;
@@ -1608,450 +1584,9 @@ int gpslam_hip_linearize_meas(gpslam_hip_handle *h, int32_t kind, double *errors
   return F;
 }
 
-// ---------------------------------------------------------------- the optimiser loops on a sharded handle / a split piece
-// (round 5: gpslam_hip_set_collectives).  The phases are the ones a caller-owned loop uses (include/gpslam_hip.h, "segment
-// sharding"); the collectives are the host's callbacks, enqueued on the handle's stream.
-int iterate_phase1(gpslam_hip_handle *h, double lambda, bool clear_flag);
-int gpslam_hip_iterate_phase2a(gpslam_hip_handle *h);
-int gpslam_hip_iterate_phase2b(gpslam_hip_handle *h, gpslam_hip_stats *st);
-int gpslam_hip_lm_begin(gpslam_hip_handle *h);
-int gpslam_hip_lm_trial_phase1(gpslam_hip_handle *h, double lambda);
-int gpslam_hip_lm_trial_phase2(gpslam_hip_handle *h, double *out6);
-int gpslam_hip_lm_reject(gpslam_hip_handle *h);
-int gpslam_hip_fs_lm_trial_phase1(gpslam_hip_handle *h, double lambda);
-int gpslam_hip_fs_lm_trial_phase2(gpslam_hip_handle *h, double *out6);
-int gpslam_hip_interface_send(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes);
-int gpslam_hip_interface_recv(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes);
-int gpslam_hip_fs_interface(gpslam_hip_handle *h, void **send, size_t *send_bytes, void **recv, size_t *recv_bytes);
-int gpslam_hip_landmark_reduce_buffer(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes);
-int fs_split_phase1(gpslam_hip_handle *h, double lambda, bool lm_trial, bool clear_flag);
-int fs_split_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st);
-
-bool split_piece(const gpslam_hip_handle *h) { return h->fs.active && h->fs.split; }
-bool dist_handle(const gpslam_hip_handle *h) { return sharded(h) || split_piece(h); }
-int dist_nranks(const gpslam_hip_handle *h) { return split_piece(h) ? h->fs.nranks : h->cfg.nranks; }
-// refuses a handle that needs collectives and has none; a single rank gathers by copying
-int dist_ready(gpslam_hip_handle *h, const char *what) {
-  if (split_piece(h) && h->fs.nb_top <= 0) return fail(h, GPSLAM_E_INVALID, "piece of a split chain: gpslam_hip_fs_set_top after compile()");
-  if (dist_nranks(h) > 1 && !h->coll_gather) {
-    std::string m = std::string(what) + " on a sharded handle / split piece needs the host's collectives (gpslam_hip_set_collectives), or the caller-owned phase loop";
-    return fail(h, GPSLAM_E_INVALID, m.c_str());
-  }
-  return 0;
-}
-int dist_gather(gpslam_hip_handle *h, const void *send, void *recv, size_t bytes) {
-  if (dist_nranks(h) == 1 && !h->coll_gather) { HIPCHK(hipMemcpyAsync(recv, send, bytes, hipMemcpyDeviceToDevice, h->stream)); return 0; }
-  if (h->coll_gather(h->coll_user, send, recv, bytes, (void *)h->stream) != 0) return fail(h, GPSLAM_E_COMM, "the all_gather callback failed");
-  return 0;
-}
-// the ONE data-path collective of an iteration: all-gather of the interface records of either scheme
-int dist_exchange(gpslam_hip_handle *h) {
-  void *s = nullptr, *r = nullptr;
-  size_t sb = 0, rb = 0;
-  int rc;
-  if (split_piece(h)) { if ((rc = IMPL_NS::gpslam_hip_fs_interface(h, &s, &sb, &r, &rb))) return rc; }
-  else {
-    if ((rc = IMPL_NS::gpslam_hip_interface_send(h, &s, &sb))) return rc;
-    if ((rc = IMPL_NS::gpslam_hip_interface_recv(h, &r, &rb))) return rc;
-  }
-  return dist_gather(h, s, r, sb);
-}
-// dense landmark border on more than one rank: the ranks' Schur complements are summed (SURVEY 8(e) collective (3))
-int dist_reduce_landmarks(gpslam_hip_handle *h) {
-  if (split_piece(h) || h->nl == 0 || h->cfg.nranks <= 1) return 0;
-  void *p = nullptr;
-  size_t nb = 0;
-  int rc = IMPL_NS::gpslam_hip_landmark_reduce_buffer(h, &p, &nb);
-  if (rc) return rc;
-  if (!h->coll_reduce) return fail(h, GPSLAM_E_INVALID, "a landmark border on more than one rank needs the all_reduce_sum callback");
-  if (h->coll_reduce(h->coll_user, p, nb / sizeof(double), (void *)h->stream) != 0) return fail(h, GPSLAM_E_COMM, "the all_reduce_sum callback failed");
-  return 0;
-}
-// n <= 8 scalars of every rank -> sums (mask bit clear) / maxima (bit set), in rank order: one all-gather of 64 bytes per rank.
-// Every rank reduces the same gathered numbers in the same order, so all of them see bit-identical results.
-int dist_scalars(gpslam_hip_handle *h, double *v, int n, unsigned max_mask) {
-  const int P = dist_nranks(h);
-  if (P == 1 && !h->coll_gather) return 0;
-  double mine[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int k = 0; k < n; k++) mine[k] = v[k];
-  HIPCHK(h->coll_s.reserve(8 * sizeof(double)));
-  HIPCHK(h->coll_r.reserve((size_t)P * 8 * sizeof(double)));
-  HIPCHK(hipMemcpyAsync(h->coll_s.p, mine, sizeof(mine), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));                     // (`mine` is pageable stack memory)
-  int rc = dist_gather(h, h->coll_s.p, h->coll_r.p, 8 * sizeof(double));
-  if (rc) return rc;
-  std::vector<double> all((size_t)P * 8);
-  HIPCHK(hipMemcpyAsync(all.data(), h->coll_r.p, all.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  for (int k = 0; k < n; k++) {
-    double acc = all[k];
-    for (int r = 1; r < P; r++) acc = ((max_mask >> k) & 1u) ? std::fmax(acc, all[(size_t)r * 8 + k]) : acc + all[(size_t)r * 8 + k];
-    v[k] = acc;
-  }
-  return 0;
-}
-
-// ---- Failures on ONE rank inside a collective loop (ADVICE r5).  Every rank must make the same sequence of collective calls: a rank
-// that returned at its first local error would leave its peers blocked in the next all-gather.  So a local failure (a HIP error, a
-// phase's status) is only RECORDED (`lrc`, the first one wins), the rank skips the local work that follows and goes on making every
-// collective call of the iteration with whatever its buffers hold; the failure code then travels in a spare slot of the 64-byte
-// scalar gather (maximum over the ranks of -code) and EVERY rank returns the same error.  What can still desynchronise ranks: a rank
-// that never enters the call (not compiled, no collectives registered: dist_ready), a collective callback that itself fails or hangs,
-// and a HIP failure inside the scalar gather's own two small copies.
-struct DistErr {
-  int lrc = 0;
-  bool ok() const { return lrc == 0; }
-  void note(int rc) { if (rc != 0 && lrc == 0) lrc = rc; }
-  double slot() const { return lrc ? (double)(-lrc) : 0.0; }           // codes are negative: the slot carries a positive number
-  static int decode(double v) { return v != 0.0 ? -(int)v : 0; }
-};
-
-// one Gauss-Newton iteration over all ranks / pieces.  loc (optional): THIS rank's statistics.  clear_flag: phase 1 clears the
-// non-positive-pivot flag.  Returns only what a collective itself reported (then the ranks are out of step anyway); local failures
-// go to `de`.
-int dist_gn_step(gpslam_hip_handle *h, gpslam_hip_stats *loc, DistErr &de, bool clear_flag) {
-  int rc;
-  if (split_piece(h)) {
-    if (de.ok()) de.note(fs_split_phase1(h, 0.0, false, clear_flag));
-    if ((rc = dist_exchange(h))) return rc;
-    if (de.ok()) {
-      rc = fs_split_phase2(h, loc);
-      if (rc != GPSLAM_E_NOT_SPD) de.note(rc);          // (a non-positive pivot is a property of the graph, reduced with the statistics)
-      else if (loc) loc->status = GPSLAM_E_NOT_SPD;
-    }
-  } else {
-    if (de.ok()) de.note(iterate_phase1(h, 0.0, clear_flag));
-    if ((rc = dist_exchange(h))) return rc;
-    if (de.ok()) de.note(IMPL_NS::gpslam_hip_iterate_phase2a(h));
-    if ((rc = dist_reduce_landmarks(h))) {
-      if (rc != GPSLAM_E_COMM) return rc;
-      de.note(rc);                                      // this rank's callback failed: tell the others through the scalars
-    }
-    if (de.ok()) {
-      rc = IMPL_NS::gpslam_hip_iterate_phase2b(h, loc);
-      if (rc != GPSLAM_E_NOT_SPD) de.note(rc);
-      else if (loc) loc->status = GPSLAM_E_NOT_SPD;
-    }
-  }
-  return 0;
-}
-// the statistics of the whole chain + the first failure of any rank: one all-gather of 64 bytes.  Every rank returns the same code.
-int dist_gn_finish(gpslam_hip_handle *h, const gpslam_hip_stats &loc, const DistErr &de, gpslam_hip_stats *st, int iters) {
-  double v[5] = {loc.error_before, loc.error_after, loc.delta_inf_norm, loc.status == GPSLAM_E_NOT_SPD ? 1.0 : 0.0, de.slot()};
-  int rc = dist_scalars(h, v, 5, 0x1Cu);                // sums of [0], [1]; maxima of [2], [3], [4]
-  if (rc) return rc;
-  if (st) {
-    std::memset(st, 0, sizeof(*st));
-    st->error_before = v[0]; st->error_after = v[1]; st->delta_inf_norm = v[2];
-    st->iterations = iters; st->accepted = 1; st->status = v[4] != 0.0 ? DistErr::decode(v[4]) : (v[3] != 0.0 ? GPSLAM_E_NOT_SPD : 0);
-  }
-  if (v[4] != 0.0) return fail(h, DistErr::decode(v[4]), de.ok() ? "another rank failed inside the iteration" : "this rank failed inside the iteration (every rank returns its code)");
-  if (v[3] != 0.0) return fail(h, GPSLAM_E_NOT_SPD, "non-positive pivot in the block elimination (on some rank)");
-  return 0;
-}
-
-// GaussNewtonOptimizer::iterate over all ranks / pieces; st (optional): the statistics of the whole chain.  The scalar gather runs
-// with or without st: it is also how a rank learns that another one failed.
-int dist_iterate_gn(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  int rc = dist_ready(h, "iterate_gn");
-  if (rc) return rc;
-  (void)hipSetDevice(h->cfg.device);
-  gpslam_hip_stats loc;
-  std::memset(&loc, 0, sizeof(loc));
-  DistErr de;
-  if ((rc = dist_gn_step(h, &loc, de, true))) return rc;
-  return dist_gn_finish(h, loc, de, st, 1);
-}
-// gpslam_hip_run_gn on a sharded handle / split piece: `iters` iterations, the statistics of the last one.  The non-positive-pivot
-// flag is cleared ONCE and stays up through the run (phase 1 does not clear it), a local failure of any iteration is
-// carried to the one scalar gather at the end: an indefinite pivot or an error in iteration k < last is reported by every rank, as
-// the unsharded run_gn reports it (ADVICE r5: both used to be swallowed).
-int dist_run_gn(gpslam_hip_handle *h, int iters, gpslam_hip_stats *st) {
-  int rc = dist_ready(h, "run_gn");
-  if (rc) return rc;
-  (void)hipSetDevice(h->cfg.device);
-  gpslam_hip_stats loc;
-  std::memset(&loc, 0, sizeof(loc));
-  DistErr de;
-  de.note(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream) == hipSuccess ? 0 : GPSLAM_E_HIP);
-  for (int it = 0; it < iters; it++)
-    if ((rc = dist_gn_step(h, (it == iters - 1) ? &loc : nullptr, de, false))) break;
-  if (rc) return rc;
-  return dist_gn_finish(h, loc, de, st, iters);
-}
-
-// LevenbergMarquardtOptimizer::iterate over all ranks / pieces: the loop of gpslam_hip_iterate_lm below with its scalars
-// summed over the ranks; every branch is gpslam_hip_lm_decide on identical numbers.  Local failures: as above (slot 6 of the gather).
-int dist_iterate_lm(gpslam_hip_handle *h, double *lambda, const gpslam_hip_params *p, gpslam_hip_stats *st) {
-  int rc = dist_ready(h, "iterate_lm");
-  if (rc) return rc;
-  (void)hipSetDevice(h->cfg.device);
-  DistErr de;
-  de.note(IMPL_NS::gpslam_hip_lm_begin(h));
-  bool accepted = false;
-  double err0 = 0, new_err = 0, dinf = 0, last = 0;
-  int trials = 0;
-  for (;;) {
-    double o[7] = {0, 0, 0, 0, 0, 0, 0};
-    if (split_piece(h)) {
-      if (de.ok()) de.note(IMPL_NS::gpslam_hip_fs_lm_trial_phase1(h, *lambda));
-      if ((rc = dist_exchange(h))) return rc;
-      if (de.ok()) de.note(IMPL_NS::gpslam_hip_fs_lm_trial_phase2(h, o));
-    } else {
-      if (de.ok()) de.note(IMPL_NS::gpslam_hip_lm_trial_phase1(h, *lambda));
-      if ((rc = dist_exchange(h))) return rc;
-      if (de.ok()) de.note(IMPL_NS::gpslam_hip_iterate_phase2a(h));
-      if ((rc = dist_reduce_landmarks(h))) {
-        if (rc != GPSLAM_E_COMM) return rc;
-        de.note(rc);
-      }
-      if (de.ok()) de.note(IMPL_NS::gpslam_hip_lm_trial_phase2(h, o));
-    }
-    o[6] = de.slot();
-    if ((rc = dist_scalars(h, o, 7, 0x64u))) return rc;     // sums of [0], [1], [3], [4]; maxima of [2], [5], [6]
-    if (o[6] != 0.0) {                                      // some rank failed: every rank leaves the loop here, with its code
-      if (de.ok()) (void)IMPL_NS::gpslam_hip_lm_reject(h);  // (this rank's trial update is not kept)
-      return fail(h, DistErr::decode(o[6]), de.ok() ? "another rank failed inside the Levenberg-Marquardt trial" : "this rank failed inside the Levenberg-Marquardt trial");
-    }
-    trials++;
-    err0 = o[0];
-    last = o[5] == 0.0 ? o[1] : o[0];
-    int32_t ok = 0, done = 0;
-    if ((rc = ::gpslam_hip_lm_decide(o, p, lambda, &ok, &done))) return rc;     // (host arithmetic on identical numbers: the same on every rank)
-    if (ok) { accepted = true; new_err = o[1]; dinf = o[2]; break; }
-    de.note(IMPL_NS::gpslam_hip_lm_reject(h));              // (a failure here is reported by the next trial's gather, or below)
-    if (done) break;
-  }
-  if (!de.ok()) {                                           // a reject that failed behind the last trial: one more 64-byte round so that all ranks agree
-    double v[1] = {de.slot()};
-    if ((rc = dist_scalars(h, v, 1, 0x1u))) return rc;
-    return fail(h, DistErr::decode(v[0]), "restoring the linearisation point failed on some rank");
-  } else if (!accepted) {                                   // (the same round on the ranks whose reject went through)
-    double v[1] = {0.0};
-    if ((rc = dist_scalars(h, v, 1, 0x1u))) return rc;
-    if (v[0] != 0.0) return fail(h, DistErr::decode(v[0]), "restoring the linearisation point failed on another rank");
-  }
-  if (st) {
-    std::memset(st, 0, sizeof(*st));
-    st->error_before = err0;
-    st->error_after = accepted ? new_err : err0;
-    st->delta_inf_norm = accepted ? dinf : 0.0;
-    st->lambda = *lambda;
-    st->iterations = 1;
-    st->accepted = accepted ? 1 : 0;
-    st->trials = trials;
-    st->last_trial_error = last;
-  }
-  return 0;
-}
-
-int gpslam_hip_error(gpslam_hip_handle *h, double *err) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!err) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
-  double s[4] = {0, 0, 0, 0};
-  int flag;
-  rc = launch_factors(h, LaunchMode{}, 1, 1);
-  if (!rc) rc = read_scal(h, s, 4, &flag);
-  *err = s[1];
-  // (with the host's collectives registered: the error of the whole chain, NonlinearFactorGraph::error -- a collective call, which a
-  //  rank whose own evaluation failed still takes part in: the failure code rides beside the sum and every rank returns it)
-  if (dist_handle(h) && h->coll_gather) {
-    double v[2] = {s[1], rc ? (double)(-rc) : 0.0};
-    int rc2 = dist_scalars(h, v, 2, 0x2u);
-    if (rc2) return rc2;
-    *err = v[0];
-    if (v[1] != 0.0) return fail(h, -(int)v[1], rc ? "evaluating the error failed on this rank" : "evaluating the error failed on another rank");
-    return 0;
-  }
-  return rc;
-}
-
-int gpslam_hip_iterate_gn(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (dist_handle(h)) return dist_iterate_gn(h, st);     // (refuses without the host's collectives: the phase loop is the caller's then)
-  (void)hipSetDevice(h->cfg.device);
-  HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  const LaunchMode m = gn_mode(h, true, true);
-  if ((rc = enqueue_gn(h, m, 0.0, true, true, false))) return rc;
-  double s[4];
-  int flag = 0;
-  if ((rc = read_scal(h, s, 4, &flag))) return rc;
-  for (int i = 0; i < 5; i++) h->last_ms[i] = 0;
-  h->l0_ms = 0.0;
-  if ((rc = collect_timing(h, m, h->last_ms))) return rc;
-  if (st) {
-    std::memset(st, 0, sizeof(*st));
-    st->error_before = s[0];
-    st->error_after = s[1];
-    st->delta_inf_norm = s[2];
-    st->iterations = 1;
-    st->accepted = 1;
-    st->status = flag ? GPSLAM_E_NOT_SPD : 0;
-  }
-  if (flag) return fail(h, GPSLAM_E_NOT_SPD, "non-positive pivot in the block elimination (indeterminate system)");
-  if (!(s[1] == s[1])) return fail(h, GPSLAM_E_NAN, "NaN error after update");
-  return 0;
-}
-
-int gpslam_hip_run_gn(gpslam_hip_handle *h, int32_t iters, gpslam_hip_stats *st, double *out5) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (iters <= 0) return GPSLAM_E_INVALID;
-  if (dist_handle(h)) {             // all ranks / pieces: ONE small all-gather at the end (statistics of the last iteration + failures of any)
-    if (out5) for (int i = 0; i < 5; i++) out5[i] = 0.0;
-    return dist_run_gn(h, iters, st);
-  }
-  (void)hipSetDevice(h->cfg.device);
-  HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  double acc[5] = {0, 0, 0, 0, 0};
-  h->l0_ms = 0.0;
-  for (int it = 0; it < iters; it++) {
-    const bool timed = (out5 != nullptr);
-    const bool last = it == iters - 1;
-    // (round 5) every iteration but the last leaves its retraction to the next iteration's K1 (PendUpd); |delta|_inf and the error
-    // are reported for the last iteration, as before
-    // never leave an update unapplied behind an error (ADVICE r5: EVERY exit, not only enqueue_gn's): the accessors of the states
-    // (get_states, set_halo, the next linearisation) read h->pose / h->vel as they are
-    auto bail = [&](int code) {
-      if (h->pend_upd) { h->pend_upd = false; (void)launch_retract(h, LaunchMode{}, 2); (void)hipStreamSynchronize(h->stream); }
-      return code;
-    };
-    const LaunchMode m = gn_mode(h, timed, last);
-    if ((rc = enqueue_gn(h, m, 0.0, timed, last, h->pend_ok && !last))) return bail(rc);
-    if (timed) {
-      if (hipEventSynchronize(h->ev[4]) != hipSuccess) { h->err = "hipEventSynchronize failed inside run_gn"; return bail(GPSLAM_E_HIP); }
-      if ((rc = collect_timing(h, m, acc))) return bail(rc);
-    }
-  }
-  double s[4];
-  int flag = 0;
-  if ((rc = read_scal(h, s, 4, &flag))) {
-    if (h->pend_upd) { h->pend_upd = false; (void)launch_retract(h, LaunchMode{}, 2); }
-    return rc;
-  }
-  if (out5) for (int i = 0; i < 5; i++) out5[i] = acc[i];
-  if (st) {
-    std::memset(st, 0, sizeof(*st));
-    st->error_before = s[0];
-    st->error_after = s[1];
-    st->delta_inf_norm = s[2];
-    st->iterations = iters;
-    st->accepted = 1;
-    st->status = flag ? GPSLAM_E_NOT_SPD : 0;
-  }
-  return flag ? fail(h, GPSLAM_E_NOT_SPD, "non-positive pivot in the block elimination") : 0;
-}
-
-// LevenbergMarquardtOptimizer::iterate (GTSAM 4.0 defaults: diagonalDamping = false, fixed lambda factor):
-// linearise once; tryLambda { damp with lambda I; solve; rho = (err - newErr) / (linErr(0) - linErr(delta));
-// keep the step if rho > minModelFidelity and lambda /= factor; otherwise, if |err - newErr| < relativeErrorTol * err,
-// stop with lambda and the values untouched; otherwise lambda *= factor and again, giving up at lambdaUpperBound }.
-// linErr(0) - linErr(delta) = 0.5 delta.g + 0.5 lambda |delta|^2 because (H + lambda I) delta = g.
-int gpslam_hip_iterate_lm(gpslam_hip_handle *h, double *lambda, const gpslam_hip_params *p, gpslam_hip_stats *st) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!lambda || !p) return GPSLAM_E_INVALID;
-  if (dist_handle(h)) return dist_iterate_lm(h, lambda, p, st);   // (refuses without the host's collectives)
-  (void)hipSetDevice(h->cfg.device);
-  HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  // Pose3-sized chains without landmarks: every trial is the fused level-0 kernel (it re-assembles from the row tables /
-  // structured records of the linearisation point with the trial's lambda, and leaves the gradient in gsave / gsave2)
-  LaunchMode m = level0_mode(h);
-  m.gsave = m.fused;
-  if ((rc = launch_factors(h, m, 0, 0))) return rc;     // scal[0] = current error
-  if ((rc = backup_state(h, false))) return rc;
-  double s[10];
-  int flag = 0;
-  bool accepted = false;
-  double err0 = 0, new_err = 0, dinf = 0;
-  int trials = 0;
-  const int nx = h->N * h->b;
-  for (;;) {
-    HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-    if (!m.fused && (rc = launch_assemble(h, m, true))) return rc;   // rows are still those of the linearisation point
-    if ((rc = launch_solve(h, m, *lambda))) return rc;
-    k_gather_delta<Real><<<dim3(nblocks(nx, 256)), dim3(256), 0, h->stream>>>(h->lv[0].x.as<Real>(), h->N, h->R, h->b, h->dvec.as<Real>());
-    // delta . g (slot 3), its separator parts (fused: slot 8), |delta|^2 (slot 4)
-    if ((rc = launch_dot3(h, h->dvec.as<Real>(), h->gsave.as<Real>(), m.fused ? h->gsave2.as<Real>() : nullptr, nx, 3, 8, 4))) return rc;
-    if (h->nl > 0) {
-      const Real *gLp = h->fs.active ? h->lm_gL.as<Real>() : h->lm_S.as<Real>() + (size_t)h->nl * h->R;
-      if ((rc = launch_dot(h, h->lm_dL.as<Real>(), gLp, h->nl, 5))) return rc;
-      if ((rc = launch_dot(h, h->lm_dL.as<Real>(), h->lm_dL.as<Real>(), h->nl, 6))) return rc;
-    }
-    if ((rc = launch_retract(h, m, 2))) return rc;
-    if ((rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;   // scal[1] = trial error
-    if ((rc = read_scal(h, s, 10, &flag))) return rc;
-    err0 = s[0];
-    trials++;
-    const double s6[6] = {s[0], s[1], s[2], s[3] + (m.fused ? s[8] : 0.0) + (h->nl > 0 ? s[5] : 0.0), s[4] + (h->nl > 0 ? s[6] : 0.0),
-                          flag ? 1.0 : 0.0};
-    int32_t ok = 0, done = 0;
-    if ((rc = ::gpslam_hip_lm_decide(s6, p, lambda, &ok, &done))) return rc;
-    if (ok) { accepted = true; new_err = s[1]; dinf = s[2]; break; }
-    if ((rc = backup_state(h, true))) return rc;          // not kept: restore the linearisation point
-    if (done) break;                                      // small cost change (lambda untouched) or lambda at its bound
-  }
-  if (st) {
-    std::memset(st, 0, sizeof(*st));
-    st->error_before = err0;
-    st->error_after = accepted ? new_err : err0;
-    st->delta_inf_norm = accepted ? dinf : 0.0;
-    st->lambda = *lambda;
-    st->iterations = 1;
-    st->accepted = accepted ? 1 : 0;
-    st->trials = trials;
-    st->last_trial_error = flag ? err0 : s[1];
-  }
-  return 0;
-}
-
-int gpslam_hip_optimize(gpslam_hip_handle *h, const gpslam_hip_params *p, gpslam_hip_stats *st) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!p) return GPSLAM_E_INVALID;
-  // NonlinearOptimizer::defaultOptimize: do { cur = error(); iterate(); } while (!converged)
-  double err0;
-  if ((rc = IMPL_NS::gpslam_hip_error(h, &err0))) return rc;
-  gpslam_hip_stats it;
-  std::memset(&it, 0, sizeof(it));
-  double new_err = err0, dinf = 0.0, lambda = p->lambda_initial;
-  int iters = 0;
-  if (!(err0 <= p->error_tol)) {
-    for (;;) {
-      const double cur = new_err;
-      rc = p->use_lm ? IMPL_NS::gpslam_hip_iterate_lm(h, &lambda, p, &it) : IMPL_NS::gpslam_hip_iterate_gn(h, &it);
-      if (rc) break;
-      iters++;
-      new_err = it.error_after;
-      dinf = it.delta_inf_norm;
-      if (iters >= p->max_iterations) break;
-      if (new_err <= p->error_tol) break;
-      const double abs_dec = cur - new_err, rel_dec = abs_dec / cur;
-      if (rel_dec <= p->relative_error_tol || abs_dec <= p->absolute_error_tol) break;
-      if (p->delta_tol > 0.0 && dinf < p->delta_tol) break;
-      if (p->use_lm && !it.accepted) break;
-    }
-  }
-  if (st) {
-    std::memset(st, 0, sizeof(*st));
-    st->error_before = err0;
-    st->error_after = new_err;
-    st->delta_inf_norm = dinf;
-    st->lambda = lambda;
-    st->iterations = iters;
-    st->status = rc;
-    st->accepted = 1;
-  }
-  return rc;
-}
-
 int gpslam_hip_normal_equations(gpslam_hip_handle *h, double *D, double *O, double *g, double *B) {
-  int rc = need_compiled(h);
+  int rc = need_local(h);
   if (rc) return rc;
-  (void)hipSetDevice(h->cfg.device);
   if (B && h->fs.active) return fail(h, GPSLAM_E_UNSUPPORTED, "the dense landmark coupling B does not exist on the segmented landmark path");
   if ((rc = launch_factors(h, LaunchMode{}, 0, 0))) return rc;
   if ((rc = launch_assemble(h, LaunchMode{}, false))) return rc;
@@ -2091,9 +1626,8 @@ int marginals_border(gpslam_hip_handle *h) {
 // whitened Jacobian rows of the current linearisation, in row-table order (rows grouped by left state; inside a
 // state: GP priors, pose priors, velocity priors, between, then the measurement kinds in FKind order)
 int gpslam_hip_get_rows(gpslam_hip_handle *h, int32_t *n_rows, double *rowLR, double *rowE, double *rowM, int32_t *rowLm) {
-  int rc = need_compiled(h);
+  int rc = need_local(h);
   if (rc) return rc;
-  (void)hipSetDevice(h->cfg.device);
   // the M rows of the full-width table, then the Mc compact rows (pose priors, between factors) expanded to full width
   const size_t M = (size_t)h->M, Mc = (size_t)h->Mc, b = (size_t)h->b, d = (size_t)h->d;
   if (n_rows) *n_rows = (int32_t)(M + Mc);
@@ -2134,10 +1668,9 @@ int gpslam_hip_get_rows(gpslam_hip_handle *h, int32_t *n_rows, double *rowLR, do
 
 int gpslam_hip_block_tridiag_solve(gpslam_hip_handle *h, int32_t N, const double *D, const double *O,
                                    const double *g, double *x) {
-  int rc = need_compiled(h);
+  int rc = need_local(h);
   if (rc) return rc;
   if (N != h->N || h->R != 1 || sharded(h) || !D || !O || !g || !x) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
   const int b = h->b;
   const size_t BS = (size_t)2 * b * b + b;
   std::vector<Real> blk((size_t)N * BS);
@@ -2159,10 +1692,9 @@ int gpslam_hip_block_tridiag_solve(gpslam_hip_handle *h, int32_t N, const double
 }
 
 int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, double *avg_ms) {
-  int rc = need_compiled(h);
+  int rc = need_local(h);
   if (rc) return rc;
   if (reps <= 0 || !avg_ms || which < 0 || which > 4 || sharded(h)) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
   double total = 0.0;
   // (K1 and the fused elimination are timed in the form an iteration runs them: structured GP records where they apply)
   LaunchMode m = level0_mode(h);
@@ -2227,320 +1759,4 @@ int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, do
   }
   *avg_ms = total / reps;
   return 0;
-}
-
-// ---------------------------------------------------------------- segment sharding
-
-int gpslam_hip_interface_send(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!sharded(h) || !dev_ptr || !bytes) return GPSLAM_E_INVALID;
-  const size_t BS = (size_t)2 * h->b * h->b + (size_t)h->b * h->R, AS = (size_t)h->b * h->b + (size_t)h->b * h->R;
-  *dev_ptr = h->iface_send.p;
-  *bytes = (BS + AS) * sizeof(Real);
-  return 0;
-}
-int gpslam_hip_interface_recv(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!sharded(h) || !dev_ptr || !bytes) return GPSLAM_E_INVALID;
-  const size_t BS = (size_t)2 * h->b * h->b + (size_t)h->b * h->R, AS = (size_t)h->b * h->b + (size_t)h->b * h->R;
-  *dev_ptr = h->iface_recv.p;
-  *bytes = (size_t)h->cfg.nranks * (BS + AS) * sizeof(Real);
-  return 0;
-}
-
-// phase 1: linearise, assemble, eliminate the local segment down to its separator -> interface record.
-// clear_flag = false: inside a multi-iteration run (dist_run_gn) the non-positive-pivot flag is sticky
-int iterate_phase1(gpslam_hip_handle *h, double lambda, bool clear_flag) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!sharded(h)) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
-  const LaunchMode m = level0_mode(h);
-  h->ph_lambda = lambda;
-  if (clear_flag) HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  if ((rc = launch_factors(h, m, 0, 0))) return rc;
-  if (!m.fused && (rc = launch_assemble(h, m, false))) return rc;
-  return launch_forward(h, m, lambda);
-}
-int gpslam_hip_iterate_phase1(gpslam_hip_handle *h, double lambda) { return iterate_phase1(h, lambda, true); }
-
-// phase 2 (after the all-gather of the records into interface_recv): every rank solves the P-block reduced
-// system redundantly and back-substitutes its segment (2a); with landmarks it then forms its share of the landmark
-// Schur complement, which the caller sums over the ranks (one all-reduce of gpslam_hip_landmark_reduce_buffer);
-// 2b solves the landmark system (redundantly), corrects the chain update, retracts the states, the landmarks and
-// the local copy of the halo state.  st (optional) returns THIS RANK's error terms and |delta|_inf; the caller
-// reduces them across ranks.
-int gpslam_hip_iterate_phase2a(gpslam_hip_handle *h) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!sharded(h)) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
-  const int P = h->cfg.nranks, b = h->b, R = h->R;
-  const size_t BS = (size_t)2 * b * b + (size_t)b * R;
-  k_iface_build<Real><<<dim3(nblocks(P * (int)BS, 256)), dim3(256), 0, h->stream>>>(h->iface_recv.as<Real>(), P, b, R, h->top_blk.as<Real>());
-  {
-    FwdArgs<Real> a;
-    a.blk = h->top_blk.as<Real>(); a.add = nullptr; a.up_blk = nullptr; a.up_add = nullptr;
-    a.n = P; a.m = P; a.R = R; a.no_sep = 1; a.last_has_right = 0; a.remote_add = nullptr; a.lambda = Real(0);
-    a.flag = h->flag.as<int>(); a.l1_blk = nullptr; a.tail = 0;
-    launch_fwd(h, LaunchMode{}, a, 1);
-    BwdArgs<Real> bw;
-    bw.blk = h->top_blk.as<Real>(); bw.x = h->top_x.as<Real>(); bw.xup = nullptr;
-    bw.n = P; bw.m = P; bw.R = R; bw.no_sep = 1; bw.last_has_right = 0;
-    launch_bwd(h, bw, 1);
-  }
-  const Real *xtop = h->top_x.as<Real>() + (size_t)h->cfg.rank * b * R;   // [x_sep(rank), x_sep(rank + 1)]
-  if ((rc = launch_backward(h, xtop))) return rc;
-  // the ranks' Schur complements are summed: the LM damping of the landmark block goes in exactly once
-  return launch_landmarks_reduce(h, (h->cfg.nranks > 1 && h->cfg.rank != 0) ? 0.0 : h->ph_lambda);
-}
-
-int gpslam_hip_landmark_reduce_buffer(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes) {
-  if (!h || !dev_ptr || !bytes) return GPSLAM_E_INVALID;
-  *dev_ptr = h->nl > 0 ? h->lm_S.p : nullptr;
-  *bytes = h->nl > 0 ? ((size_t)h->nl * h->R + h->nl) * sizeof(Real) : 0;
-  return 0;
-}
-
-int gpslam_hip_iterate_phase2b(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!sharded(h)) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
-  const int b = h->b, R = h->R;
-  Real *xtop = h->top_x.as<Real>() + (size_t)h->cfg.rank * b * R;
-  if ((rc = launch_landmarks_solve(h, h->ph_lambda))) return rc;
-  if ((rc = launch_retract(h, LaunchMode{}, 2))) return rc;
-  if (has_right_rank(h)) {  // keep the local copy of the neighbour's first state in step with its owner
-    if (h->nl > 0) {        // its update needs the landmark correction too: delta = x0 - Z dL on that one block
-      LmArgs<Real, RowT> la = lm_args(h, 0.0);
-      la.N = 1; la.x = xtop + (size_t)b * R;
-      k_lm_correct<Real, RowT><<<dim3(nblocks(b, 256)), dim3(256), 0, h->stream>>>(la);
-    }
-    RetractArgs<Real> a;
-    a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride; a.N = 1; a.R = R;
-    a.chart = h->cfg.chart; a.first = h->N; a.x = xtop + (size_t)b * R; a.partial = h->partial.as<Real>() + nblocks(h->N, 128) + 4; a.flag = h->flag.as<int>();
-    dispatch_mf(h->mf, [&](auto tag) {
-      constexpr int MF = decltype(tag)::value;
-      k_retract<Real, MF><<<dim3(1), dim3(128), 0, h->stream>>>(a);
-    });
-  }
-  // the error of the new state: only when the caller wants statistics (inside a fixed-count run the next
-  // iteration's linearisation evaluates it anyway)
-  if (st && (rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;
-  HIPCHK(hipGetLastError());
-  if (st) {
-    double s[4];
-    int flag = 0;
-    if ((rc = read_scal(h, s, 4, &flag))) return rc;
-    std::memset(st, 0, sizeof(*st));
-    st->error_before = s[0];
-    st->error_after = s[1];
-    st->delta_inf_norm = s[2];
-    st->iterations = 1;
-    st->accepted = 1;
-    st->status = flag ? GPSLAM_E_NOT_SPD : 0;
-    if (flag) return fail(h, GPSLAM_E_NOT_SPD, "non-positive pivot in the block elimination");
-  }
-  return 0;
-}
-
-// ---- config 4 across GPUs: the segmented landmark elimination on a chain split into pieces (DESIGN.md section 5).
-// compile() has planned this piece with its end blocks kept (FatSepPlan::split); set_top sizes the interface record once
-// the caller knows the widest fat block of any piece.
-int gpslam_hip_fs_split_info(gpslam_hip_handle *h, int32_t out4[4]) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!out4 || !h->fs.active || !h->fs.split) return GPSLAM_E_INVALID;
-  out4[0] = h->fs.NB; out4[1] = h->fs.K; out4[2] = h->fs.C; out4[3] = h->fs.nb_top;
-  return 0;
-}
-int gpslam_hip_fs_set_top(gpslam_hip_handle *h, int32_t nb_top) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  FatSepPlan &p = h->fs;
-  if (!p.active || !p.split) return fail(h, GPSLAM_E_INVALID, "fs_set_top: not a piece of a split chain (gpslam_hip_fs_set_split before compile)");
-  if (nb_top < p.NB || nb_top > kFatMax) return fail(h, GPSLAM_E_INVALID, "fs_set_top: the top block size must lie between this piece's fat block size and 128");
-  (void)hipSetDevice(h->cfg.device);
-  const int P = p.nranks, NT = nb_top;
-  const size_t NT2 = (size_t)NT * NT, RS = 3 * NT2 + 2 * NT;
-  p.nb_top = NT;
-  std::vector<int> elim, upd;
-  int nlinks = 0, endl = 0;
-  FatSepPlan::build_levels(P + 1, false, elim, upd, p.tlevels, p.ttop, nlinks, endl);
-  if (elim.empty()) elim.assign(6, 0);
-  if (upd.empty()) upd.assign(3, 0);
-  HIPCHK(upload_vec(h->stream, p.d_telim, elim));
-  HIPCHK(upload_vec(h->stream, p.d_tupd, upd));
-  HIPCHK(p.send.reserve(RS * sizeof(Real)));
-  HIPCHK(p.recv.reserve((size_t)P * RS * sizeof(Real)));
-  HIPCHK(p.tD.reserve((size_t)(P + 1) * NT2 * sizeof(Real)));
-  HIPCHK(p.tlink.reserve((size_t)std::max(nlinks, P) * NT2 * sizeof(Real)));
-  HIPCHK(p.tg.reserve((size_t)(P + 1) * NT * sizeof(Real)));
-  HIPCHK(p.tQ.reserve((size_t)(P + 1) * NT2 * sizeof(Real)));
-  HIPCHK(p.tS1.reserve((size_t)(P + 1) * NT2 * sizeof(Real)));
-  HIPCHK(p.tS2.reserve((size_t)(P + 1) * NT2 * sizeof(Real)));
-  HIPCHK(p.tsv.reserve((size_t)(P + 1) * 2 * NT * sizeof(Real)));
-  HIPCHK(p.tx.reserve((size_t)(P + 1) * NT * sizeof(Real)));
-  // (the dynamic-LDS attribute of k_fat_elim_mfma / k_fat_top was set to the largest fat block's size by compile(): fs_build)
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
-}
-int gpslam_hip_fs_interface(gpslam_hip_handle *h, void **send, size_t *send_bytes, void **recv, size_t *recv_bytes) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  FatSepPlan &p = h->fs;
-  if (!send || !send_bytes || !recv || !recv_bytes || !p.active || !p.split || p.nb_top <= 0) return GPSLAM_E_INVALID;
-  const size_t RS = ((size_t)3 * p.nb_top * p.nb_top + 2 * p.nb_top) * sizeof(Real);
-  *send = p.send.p; *send_bytes = RS;
-  *recv = p.recv.p; *recv_bytes = (size_t)p.nranks * RS;
-  return 0;
-}
-int gpslam_hip_fs_phase1(gpslam_hip_handle *h, double lambda) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!h->fs.active || !h->fs.split || h->fs.nb_top <= 0) return fail(h, GPSLAM_E_INVALID, "fs_phase1: set_split before compile(), set_top after it");
-  (void)hipSetDevice(h->cfg.device);
-  return fs_split_phase1(h, lambda, false, true);
-}
-int gpslam_hip_fs_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!h->fs.active || !h->fs.split || h->fs.nb_top <= 0) return fail(h, GPSLAM_E_INVALID, "fs_phase2: set_split before compile(), set_top after it");
-  (void)hipSetDevice(h->cfg.device);
-  return fs_split_phase2(h, st);
-}
-
-// Levenberg-Marquardt on a split chain (the caller's loop, as for the dense-border sharding below):  gpslam_hip_lm_begin;
-// per trial fs_lm_trial_phase1(lambda) -> all-gather of the records -> fs_lm_trial_phase2(out6) -> all-reduce of out6 ->
-// accept, or gpslam_hip_lm_reject and a larger lambda.  delta . g adds up over the pieces as it is (every piece holds its
-// own share of a shared unknown's gradient); |delta|^2 counts a shared unknown on the piece to its right only.
-int gpslam_hip_fs_lm_trial_phase1(gpslam_hip_handle *h, double lambda) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!h->fs.active || !h->fs.split || h->fs.nb_top <= 0) return fail(h, GPSLAM_E_INVALID, "fs_lm_trial_phase1: set_split before compile(), set_top after it");
-  (void)hipSetDevice(h->cfg.device);
-  return fs_split_phase1(h, lambda, true, true);
-}
-int gpslam_hip_fs_lm_trial_phase2(gpslam_hip_handle *h, double *out6) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  FatSepPlan &p = h->fs;
-  if (!out6 || !p.active || !p.split || p.nb_top <= 0) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
-  if ((rc = fs_split_solve(h))) return rc;
-  const bool right = p.rank < p.nranks - 1;
-  const int nx = h->N * h->b, nx_own = (h->N - (right ? 1 : 0)) * h->b;
-  k_gather_delta<Real><<<dim3(nblocks(nx, 256)), dim3(256), 0, h->stream>>>(h->lv[0].x.as<Real>(), h->N, h->R, h->b, h->dvec.as<Real>());
-  if ((rc = launch_dot(h, h->dvec.as<Real>(), h->gsave.as<Real>(), nx, 3))) return rc;        // delta . g
-  if ((rc = launch_dot(h, h->dvec.as<Real>(), h->dvec.as<Real>(), nx_own, 4))) return rc;     // |delta|^2, own states
-  if ((rc = launch_dot(h, h->lm_dL.as<Real>(), h->lm_gL.as<Real>(), h->nl, 5))) return rc;
-  k_fs_mask_mul<Real><<<dim3(nblocks(h->nl, 256)), dim3(256), 0, h->stream>>>(h->lm_dL.as<Real>(), p.d_lm_own.as<int>(), h->ld, h->nl, p.lm_tmp.as<Real>());
-  if ((rc = launch_dot(h, p.lm_tmp.as<Real>(), h->lm_dL.as<Real>(), h->nl, 6))) return rc;     // |dL|^2, own landmarks
-  if ((rc = launch_retract(h, LaunchMode{}, 2))) return rc;
-  if ((rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;   // scal[1] = trial error
-  double s[8];
-  int flag = 0;
-  if ((rc = read_scal(h, s, 8, &flag))) return rc;
-  out6[0] = s[0]; out6[1] = s[1]; out6[2] = s[2];
-  out6[3] = s[3] + s[5];
-  out6[4] = s[4] + s[6];
-  out6[5] = flag ? 1.0 : 0.0;
-  return 0;
-}
-
-// ---- Levenberg-Marquardt on a sharded chain.  The decisions of gpslam_hip_iterate_lm need three global sums (error,
-// delta . g, |delta|^2), so the loop lives with the caller (gpslam_amd/sharded.py: ShardedSolver.iterate_lm) and the
-// library provides its device-side steps:
-//   lm_begin            linearise once at the current estimate, remember it
-//   lm_trial_phase1     damp with lambda, eliminate the segment            -> all-gather of the interface records
-//   iterate_phase2a     reduced solve, back-substitution, landmark share   -> all-reduce of the landmark buffer
-//   lm_trial_phase2     landmark solve, trial update, this rank's scalars  -> all-reduce of the scalars, decision
-//   lm_reject           back to the linearisation point (an accepted trial needs nothing)
-int gpslam_hip_lm_begin(gpslam_hip_handle *h) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!sharded(h) && !(h->fs.active && h->fs.split)) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
-  HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  if ((rc = launch_factors(h, LaunchMode{}, 0, 0))) return rc;   // rows + scal[0] = this rank's error
-  return backup_state(h, false);
-}
-
-int gpslam_hip_lm_trial_phase1(gpslam_hip_handle *h, double lambda) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!sharded(h)) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
-  h->ph_lambda = lambda;
-  HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  if ((rc = launch_assemble(h, LaunchMode{}, true))) return rc;   // rows are still those of the linearisation point
-  return launch_forward(h, LaunchMode{}, lambda);
-}
-
-// out6 = {error at the linearisation point, trial error, |delta|_inf, delta . g, |delta|^2, indefinite-pivot flag},
-// all for THIS rank's states (landmark terms on rank 0 only); sums / maxima over the ranks give the global values
-int gpslam_hip_lm_trial_phase2(gpslam_hip_handle *h, double *out6) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!sharded(h) || !out6) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
-  const int b = h->b, R = h->R, nx = h->N * h->b;
-  Real *xtop = h->top_x.as<Real>() + (size_t)h->cfg.rank * b * R;
-  if ((rc = launch_landmarks_solve(h, h->ph_lambda))) return rc;
-  if (has_right_rank(h) && h->nl > 0) {
-    LmArgs<Real, RowT> la = lm_args(h, 0.0);
-    la.N = 1; la.x = xtop + (size_t)b * R;
-    k_lm_correct<Real, RowT><<<dim3(nblocks(b, 256)), dim3(256), 0, h->stream>>>(la);
-  }
-  k_gather_delta<Real><<<dim3(nblocks(nx, 256)), dim3(256), 0, h->stream>>>(h->lv[0].x.as<Real>(), h->N, h->R, h->b, h->dvec.as<Real>());
-  if ((rc = launch_dot(h, h->dvec.as<Real>(), h->gsave.as<Real>(), nx, 3))) return rc;   // delta . g
-  if ((rc = launch_dot(h, h->dvec.as<Real>(), h->dvec.as<Real>(), nx, 4))) return rc;    // |delta|^2
-  const bool lm_here = h->nl > 0 && h->cfg.rank == 0;    // replicated landmark update: counted once
-  if (lm_here) {
-    if ((rc = launch_dot(h, h->lm_dL.as<Real>(), h->lm_S.as<Real>() + (size_t)h->nl * h->R, h->nl, 5))) return rc;
-    if ((rc = launch_dot(h, h->lm_dL.as<Real>(), h->lm_dL.as<Real>(), h->nl, 6))) return rc;
-  }
-  // the rows of the last local state also feed the gradient of the neighbour's first state (halo_add = [RD | Rg]):
-  // that share of delta . g is only known here
-  if (has_right_rank(h)) {
-    if ((rc = launch_dot(h, xtop + (size_t)b * R, h->halo_add.as<Real>() + (size_t)b * b, b, 7))) return rc;
-  }
-  if ((rc = launch_retract(h, LaunchMode{}, 2))) return rc;
-  if (has_right_rank(h)) {
-    RetractArgs<Real> a;
-    a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride; a.N = 1; a.R = R;
-    a.chart = h->cfg.chart; a.first = h->N; a.x = xtop + (size_t)b * R; a.partial = h->partial.as<Real>() + nblocks(h->N, 128) + 4; a.flag = h->flag.as<int>();
-    dispatch_mf(h->mf, [&](auto tag) {
-      constexpr int MF = decltype(tag)::value;
-      k_retract<Real, MF><<<dim3(1), dim3(128), 0, h->stream>>>(a);
-    });
-  }
-  if ((rc = launch_factors(h, LaunchMode{}, 1, 1))) return rc;   // scal[1] = trial error
-  double s[8];
-  int flag = 0;
-  if ((rc = read_scal(h, s, 8, &flag))) return rc;
-  out6[0] = s[0]; out6[1] = s[1]; out6[2] = s[2];
-  out6[3] = s[3] + (has_right_rank(h) ? s[7] : 0.0) + (lm_here ? s[5] : 0.0);
-  out6[4] = s[4] + (lm_here ? s[6] : 0.0);
-  out6[5] = flag ? 1.0 : 0.0;
-  return 0;
-}
-
-int gpslam_hip_lm_reject(gpslam_hip_handle *h) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!sharded(h) && !(h->fs.active && h->fs.split)) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
-  return backup_state(h, true);
-}
-
-// 2a + 2b for chains without landmarks (or a single rank): nothing to reduce in between
-int gpslam_hip_iterate_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  if (h && h->nl > 0 && h->cfg.nranks > 1)
-    return fail(h, GPSLAM_E_INVALID, "landmarks on a sharded chain: phase2a, all-reduce of the landmark buffer, phase2b");
-  int rc = IMPL_NS::gpslam_hip_iterate_phase2a(h);
-  return rc ? rc : IMPL_NS::gpslam_hip_iterate_phase2b(h, st);
 }

@@ -1,5 +1,5 @@
 // api_impl32.hip -- the precision-dependent half of the library with RowT = float (Jacobian row tables); Real (normal equations,
-// solver) is double in both halves.  See api_impl.inc.
+// solver) is double in both halves.  See api_impl.inc (launchers, compile) and api_iterate.inc (the iteration driver).
 #include "api_common.hpp"
 
 namespace impl64 {
@@ -14,5 +14,6 @@ typedef double Real;
 typedef float RowT;
 #define IMPL_NS impl32
 #include "api_impl.inc"
+#include "api_iterate.inc"
 #undef IMPL_NS
 }  // namespace impl32

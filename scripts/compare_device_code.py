@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Is the device code of two builds the same?  compare_device_code.py LIB_A LIB_B [--arch gfx950]
+
+LIB_A / LIB_B: two gpslam_amd/lib directories (obj/*.o and libgpslam_hip.so, as `python -m gpslam_amd.build` leaves them).
+Per object: the gfx950 code object is taken out of .hip_fatbin, and every kernel is compared by name, by the bytes of its code and
+by its metadata (registers, LDS, scratch: the amdhsa.kernels note).  Per symbol, not per file: the order of instantiation moves
+with the host code.  Also compares the C ABI (the exported gpslam_hip_* symbols) of the two libraries.  Exit status 1 on any difference.
+"""
+import argparse
+import hashlib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROCM_LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
+
+
+def run(*cmd):
+    return subprocess.run(cmd, check=True, capture_output=True, text=True).stdout
+
+
+def tool(name):
+    p = os.path.join(ROCM_LLVM, name)
+    return p if os.path.exists(p) else name
+
+
+def kernels(obj, arch, tmp):
+    """{kernel name: (sha256 of its code, its metadata block)} of one host object"""
+    base = os.path.join(tmp, os.path.basename(obj))
+    run(tool("llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", obj, base + ".fatbin")
+    run(tool("clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--" + arch, "--input=" + base + ".fatbin",
+        "--output=" + base + ".co", "--unbundle")
+    text = None
+    for line in run(tool("llvm-readelf"), "-SW", base + ".co").splitlines():
+        m = re.match(r"\s*\[\s*\d+\]\s+\.text\s+PROGBITS\s+([0-9a-f]+)\s+([0-9a-f]+)\s+([0-9a-f]+)", line)
+        if m:
+            text = (int(m.group(1), 16), int(m.group(2), 16))
+    blob = open(base + ".co", "rb").read()
+    code = {}
+    for line in run(tool("llvm-readelf"), "-sW", base + ".co").splitlines():
+        f = line.split()
+        if len(f) == 8 and f[3] == "FUNC" and f[6] != "UND":
+            addr, size = int(f[1], 16), int(f[2])
+            off = text[1] + addr - text[0]
+            code[f[7]] = hashlib.sha256(blob[off:off + size]).hexdigest()
+    meta = {}
+    notes = run(tool("llvm-readelf"), "--notes", base + ".co")
+    for block in re.split(r"\n\s*- \.agpr_count", notes)[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block)
+        body = "\n".join(l.strip() for l in block.splitlines() if not l.strip().startswith("amdhsa.") and "---" not in l)
+        meta[name.group(1)] = body.split("amdhsa.target")[0]
+    return {k: (v, meta.get(k, "")) for k, v in code.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("lib_a")
+    ap.add_argument("lib_b")
+    ap.add_argument("--arch", default="gfx950")
+    a = ap.parse_args()
+    bad = 0
+    with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
+        objs = sorted(f for f in os.listdir(os.path.join(a.lib_a, "obj")) if f.endswith(".o"))
+        if objs != sorted(f for f in os.listdir(os.path.join(a.lib_b, "obj")) if f.endswith(".o")):
+            print("different sets of objects")
+            bad += 1
+        for o in objs:
+            ka, kb = kernels(os.path.join(a.lib_a, "obj", o), a.arch, ta), kernels(os.path.join(a.lib_b, "obj", o), a.arch, tb)
+            for k in sorted(set(ka) | set(kb)):
+                if k not in ka or k not in kb:
+                    print("%s: %s only in %s" % (o, k, "A" if k in ka else "B"))
+                    bad += 1
+                elif ka[k][0] != kb[k][0]:
+                    print("%s: %s: code differs" % (o, k))
+                    bad += 1
+                elif ka[k][1] != kb[k][1]:
+                    print("%s: %s: metadata differs" % (o, k))
+                    bad += 1
+            print("%-16s %4d kernels in A, %4d in B" % (o, len(ka), len(kb)))
+    sym = [sorted(l.split()[-1] for l in run("nm", "-D", "--defined-only", os.path.join(d, "libgpslam_hip.so")).splitlines() if l.split()[-1].startswith("gpslam_hip_"))
+           for d in (a.lib_a, a.lib_b)]
+    if sym[0] != sym[1]:
+        print("exported symbols differ:", sorted(set(sym[0]) ^ set(sym[1])))
+        bad += 1
+    print("%d exported gpslam_hip_* symbols in A, %d in B" % (len(sym[0]), len(sym[1])))
+    print("IDENTICAL" if not bad else "%d DIFFERENCES" % bad)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

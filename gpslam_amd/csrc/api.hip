@@ -497,8 +497,9 @@ int gpslam_hip_plan_info(gpslam_hip_handle *h, int32_t out8[8]) {
   if (rc) return rc;
   if (!out8) return GPSLAM_E_INVALID;
   const LaunchMode m = level0_mode(h);   // (what an iteration's launches do)
+  const LaunchForm f = launch_form(h, m);
   const int32_t v[8] = {(int32_t)h->lv.size(), h->lv.empty() ? 0 : h->lv[0].m, h->lv.size() > 1 ? h->lv[1].m : 0, m.fused ? 1 : 0,
-                        (m.se3_rec || h->struct3_ok) ? ((m.se3_rec && h->irow_ok) ? 2 : 1) : 0, h->M, h->Mc, h->R};
+                        f.gp != GpForm::Rows ? (f.lines ? 2 : 1) : 0, h->M, h->Mc, h->R};
   for (int i = 0; i < 8; i++) out8[i] = v[i];
   return 0;
 }

@@ -55,9 +55,32 @@ struct MeasSet {  // measurement factors (kernels.hpp FKind)
   // factor, diag(1 / sigma) for those that kept their diagonal model; empty: every factor is diagonal
   std::vector<double> sqi;
   DevBuf d_idx, d_lm, d_meas, d_sig, d_coef, d_row0, d_aux, d_aidx, d_sqi;
-  DevBuf d_irow0;                      // first row of each factor in the table of 16-double interpolated rows (handle: irow_ok)
+  DevBuf d_irow0;                      // first row of each factor in the table of 16-double interpolated rows (Plan::lines)
   int count() const { return (int)idx.size(); }
   void release() { d_idx.release(); d_lm.release(); d_meas.release(); d_sig.release(); d_coef.release(); d_row0.release(); d_aux.release(); d_aidx.release(); d_sqi.release(); d_irow0.release(); }
+};
+
+// Which kernels serve a compiled graph, and in which form.  make_plan() (api_impl.inc) fills one per compile(), once the row layout
+// is known, and nothing else writes it; what a single launch then does is launch_form(handle, LaunchMode) below.
+enum class Level0 { Column, Rows, Fused };     // level-0 elimination: k_chunk_forward, k_chunk_forward_rows, or k_fused_level0 where the mode asks for it
+enum class GpForm { Rows, Se3Rec, D3Rec };     // GP priors as Jacobian rows, as SE(3) records (kGps*: GpArgs::gps -> k_fused_level0) or as d = 3
+                                               // records (kGp3*: block size 6, which k_assemble_ghost decodes as well)
+struct Plan {
+  Level0 level0 = Level0::Column;
+  bool upper_cr = false;        // the levels above level 0 run as LDS-resident cyclic reduction (upper.hip)
+  GpForm gp_rec = GpForm::Rows; // the form a launch that carries records uses
+  bool btw_rec = false;         // BetweenFactor<Pose3> rides with the SE(3) records as 48-double records (kBtw*): at most one per left state
+  bool lines = false;           // SE(3) records + interpolated GPS rows as 16-double lines (k_gps_lines -> k_fused_level0<4>): every
+                                // full-width row besides the GP priors' belongs to such a factor on an interval that has a GP prior
+  int odd_rows = 0;             // full-width rows besides the GP priors': 0 none, 1 a few (k_fused_level0<2> fetches them without a ring), 2 many (<3>)
+  bool pure6 = false;           // block size 6: next to nothing but d = 3 GP records in the full-width table (fused level 0 at every size)
+  bool fold_retract = false;    // run_gn folds an iteration's retraction into the next iteration's K1 (kernels.hpp: PendUpd)
+  // level 1 as groups of four: a fused level 0 reduces them in its own tail, k_chunk_backward_rows solves its group itself
+  bool tail_fold = false, fold_tail_bwd = false;
+  // the row placement the record decoders rely on (checks, not options: without them the record forms above are off)
+  bool gp_rows_lead = true, btw_rows_trail = true;
+  bool rows() const { return level0 != Level0::Column; }
+  bool fused() const { return level0 == Level0::Fused; }
 };
 
 }  // namespace
@@ -118,33 +141,21 @@ struct gpslam_hip_handle {
   // landmark elimination at scale (fatsep.hpp): segments + fat separators instead of the dense border
   FatSepPlan fs;
   DevBuf lm_gL;             // undamped landmark gradient of the segmented path (the dense path keeps it behind lm_S)
-  bool upper_ok = false;    // the levels above level 0 run as LDS-resident cyclic reduction (upper.hip)
-  bool fuse_ok = false;     // k_fused_level0 applies to this graph (compile())
-  bool struct_ok = false;   // the GP priors may reach k_fused_level0 as structured records (GpArgs::gps) instead of rows
-  // block size 6 (SE(2), SO(3), 3-D linear chains): the GP priors as 32-double records (kGp3*) that k_assemble_ghost and
-  // k_fused_level0<1, double, 6> decode
-  bool struct3_ok = false;
-  bool pure6 = false;       // block size 6: nothing but d = 3 GP records in the full-width row table (fused level 0 at every size)
-  bool odd_many = false;    // SE(3) records: more other full-width rows than k_fused_level0<2> fetches without a ring (-> <3>)
+  Plan plan;                // compile(): which kernels serve this graph, in which form
   DevBuf gps, gpidx, dU, gsave2;
-  DevBuf simd_cnt;          // k_fused_level0 (GPS_ROLE_SWAP): wave-0 count per SIMD of the chip, zero between launches
-  // BetweenFactor<Pose3> of a chain on the structured path as 48-double records (kBtw*): at most one per left state
-  bool btw_rec_ok = false;
-  bool gp_rows_lead = true, btw_rows_trail = true;   // compile(): the row placement the record decoders rely on holds
-  // SE(3) records + interpolated measurement rows as 16-double lines (round 5, k_fused_level0<4>): every full-width row besides the
-  // GP priors' belongs to a GPInterpolatedGPSFactorPose3 on an interval that has a GP prior
-  bool irow_ok = false;
-  DevBuf rowI, irowptr;
+  DevBuf simd_cnt;          // k_fused_level0 (role swap): wave-0 count per SIMD of the chip, zero between launches
+  DevBuf rowI, irowptr;     // Plan::lines
   // the host's collectives (gpslam_hip_set_collectives): with them the optimiser loops run on sharded handles / split pieces
   gpslam_hip_all_gather_fn coll_gather = nullptr;
   gpslam_hip_all_reduce_sum_fn coll_reduce = nullptr;
   void *coll_user = nullptr;
   DevBuf coll_s, coll_r;     // 8 doubles of this rank's scalars, nranks x 8 gathered
-  DevBuf brec, btwidx;
-  // Gauss-Newton runs (gpslam_hip_run_gn): the retraction of an iteration folded into the next iteration's K1 (kernels.hpp: PendUpd).
-  // pend_ok: compile() found the graph eligible;  pend_upd: a solve's update sits in the level-0 solution array, not yet applied
-  bool pend_ok = false, pend_upd = false;
-  int U_version = 0, dU_version = -1;   // set_qc after compile(): the device copy of U is refreshed before its next use
+  DevBuf brec, btwidx;      // Plan::btw_rec
+  // Gauss-Newton runs (gpslam_hip_run_gn, Plan::fold_retract): a solve's update sits in the level-0 solution array, not yet applied
+  bool pend_upd = false;
+  // set_qc after compile(): refresh_dU brings the device copy of U (and U_diag) up to date before a launch reads it
+  int U_version = 0, dU_version = -1;
+  bool U_diag = false;        // the U in dU is diagonal (an isotropic or diagonal Qc): the SE(3) record variants take the shorter assembly form
   bool compiled = false;
   double last_ms[5] = {0, 0, 0, 0, 0};
   // deferred reductions inside run_gn / iterate_gn (chains without landmarks, unsharded): the error partial sums of the
@@ -301,14 +312,43 @@ template <typename F> void dispatch_fk(int fk, F &&f) {
 bool sharded(const gpslam_hip_handle *h) { return h->cfg.nranks > 1 || h->cfg.force_sharded == 1; }
 bool has_right_rank(const gpslam_hip_handle *h) { return sharded(h) && h->cfg.rank < h->cfg.nranks - 1; }
 
+bool plan_bit(const gpslam_hip_handle *h, int bit) { return (h->cfg.plan & bit) != 0; }   // GPSLAM_PLAN_*
+
 // The one rule for level 0 of an iteration: fused where compile() found k_fused_level0 applicable, except on an unsharded
 // chain of a single level (that level is the top solve; a sharded rank's level 0 always keeps its separator), and then
 // with the GP priors as SE(3) records where the graph allows them.
 LaunchMode level0_mode(const gpslam_hip_handle *h) {
   LaunchMode m;
-  m.fused = h->fuse_ok && (h->lv.size() >= 2 || sharded(h));
-  m.se3_rec = m.fused && h->struct_ok;
+  m.fused = h->plan.fused() && (h->lv.size() >= 2 || sharded(h));
+  m.se3_rec = m.fused && h->plan.gp_rec == GpForm::Se3Rec;
   return m;
+}
+
+// What one launch uses, from the plan and the launch's mode -- the one place that says so.
+struct LaunchForm {
+  GpForm gp = GpForm::Rows;   // the GP priors on this launch
+  bool btw_rec = false;       // between factors travel as records
+  bool lines = false;         // interpolated GPS rows travel as 16-double lines
+  int sv = 0;                 // k_fused_level0<sv, ., ., dg> (launch_fused_k)
+  bool dg = false;
+};
+// SE(3) records when the launch says so; d = 3 records whenever the graph has them (every consumer decodes them) and the row table
+// itself is not what is wanted
+GpForm gp_form(const gpslam_hip_handle *h, const LaunchMode &m) {
+  if (m.se3_rec && h->plan.gp_rec == GpForm::Se3Rec) return GpForm::Se3Rec;
+  return (h->plan.gp_rec == GpForm::D3Rec && !m.d3_rows) ? GpForm::D3Rec : GpForm::Rows;
+}
+LaunchForm launch_form(const gpslam_hip_handle *h, const LaunchMode &m) {
+  const Plan &p = h->plan;
+  LaunchForm f;
+  f.gp = gp_form(h, m);
+  const bool se3 = f.gp == GpForm::Se3Rec;
+  f.btw_rec = se3 && p.btw_rec;
+  f.lines = se3 && p.lines;
+  // records + lines: <4>; + a ring of full-width rows (measurement factors): <3>; + a few rows fetched where they are used: <2>
+  f.sv = f.gp == GpForm::Rows ? 0 : (!se3 ? 1 : (f.lines ? 4 : (p.odd_rows == 2 ? 3 : (p.odd_rows == 1 ? 2 : 1))));
+  f.dg = se3 && h->U_diag && !plan_bit(h, GPSLAM_PLAN_GENERIC_QC);   // (U_diag: as of refresh_dU, which every launch that reads dU calls first)
+  return f;
 }
 
 int read_scal(gpslam_hip_handle *h, double *out, int n, int *flag) {
@@ -439,10 +479,24 @@ int backup_state(gpslam_hip_handle *h, bool restore) {
   return 0;
 }
 
+// chol_upper(Qc^-1) as the record forms read it from device memory (FusedArgs::Ud, AsmArgs::Ud): the one Qc every prior was added
+// with, or the handle's.  compile() and, after a set_qc, the next launch that reads it come through here (36 doubles, stream-ordered).
+int refresh_dU(gpslam_hip_handle *h) {
+  if (h->dU_version == h->U_version) return 0;
+  const double *U = h->gp_single_q > 0 ? &h->gp_Utab[(size_t)(h->gp_single_q - 1) * 36] : h->U;
+  HIPCHK(h->dU.reserve(36 * sizeof(double)));
+  HIPCHK(hipMemcpyAsync(h->dU.p, U, 36 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  h->U_diag = true;     // (6 x 6, zero below the diagonal: U is upper triangular; only the SE(3) forms ask)
+  for (int i = 0; i < 6; i++)
+    for (int j = i + 1; j < 6; j++) h->U_diag = h->U_diag && U[i * 6 + j] == 0.0;
+  h->dU_version = h->U_version;
+  return 0;
+}
+
 }  // namespace
 
 // kernels that exist for fp64 only (hand-written 64-bit DPP row layout, v_mfma_f64): the fp32 instantiation of the
-// host code never selects them (rows_kernel_applies / compile()), these overloads only keep it compiling
+// host code never selects them (make_plan), these overloads only keep it compiling
 namespace {
 // ea / eb != null: the launch carries its own start / stop events (a timed iteration: the dispatch's own time stamps)
 #define GPS_FUSED_LAUNCH(...)                                                                                      \
@@ -450,37 +504,39 @@ namespace {
     if (ea) hipExtLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(128), 0, st, ea, eb, 0, u);                      \
     else __VA_ARGS__<<<dim3(grid), dim3(128), 0, st>>>(u);                                                         \
   } while (0)
-inline void launch_fused_k(int b, const FusedArgs<double, double> &u, int grid, hipStream_t st, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr) {
+inline void launch_fused_k(int b, const LaunchForm &f, const FusedArgs<double, double> &u, int grid, hipStream_t st, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr) {
   if (b == 6) {
-    if (u.gps) GPS_FUSED_LAUNCH(k_fused_level0<1, double, 6>);      // d = 3 records (kGp3*)
+    if (f.sv == 1) GPS_FUSED_LAUNCH(k_fused_level0<1, double, 6>);      // d = 3 records (kGp3*)
     else GPS_FUSED_LAUNCH(k_fused_level0<0, double, 6>);
     return;
   }
-  if (u.gps && u.rowI) {                     // records + interpolated measurement rows as 16-double lines (round 5)
-    if (u.u_diag) GPS_FUSED_LAUNCH(k_fused_level0<4, double, 12, true>);
-    else GPS_FUSED_LAUNCH(k_fused_level0<4>);
-  } else if (u.gps && u.odd_rows == 2) {     // records + a ring of full-width rows (measurement factors)
-    if (u.u_diag) GPS_FUSED_LAUNCH(k_fused_level0<3, double, 12, true>);
-    else GPS_FUSED_LAUNCH(k_fused_level0<3>);
-  } else if (u.gps && u.odd_rows) GPS_FUSED_LAUNCH(k_fused_level0<2>);
-  else if (u.gps && u.u_diag) GPS_FUSED_LAUNCH(k_fused_level0<1, double, 12, true>);   // diagonal chol(Qc^-1)
-  else if (u.gps) GPS_FUSED_LAUNCH(k_fused_level0<1>);
-  else GPS_FUSED_LAUNCH(k_fused_level0<0>);
+  switch (f.sv) {
+    case 4:                                  // records + interpolated measurement rows as 16-double lines (round 5)
+      if (f.dg) GPS_FUSED_LAUNCH(k_fused_level0<4, double, 12, true>);
+      else GPS_FUSED_LAUNCH(k_fused_level0<4>);
+      break;
+    case 3:                                  // records + a ring of full-width rows (measurement factors)
+      if (f.dg) GPS_FUSED_LAUNCH(k_fused_level0<3, double, 12, true>);
+      else GPS_FUSED_LAUNCH(k_fused_level0<3>);
+      break;
+    case 2: GPS_FUSED_LAUNCH(k_fused_level0<2>); break;
+    case 1:
+      if (f.dg) GPS_FUSED_LAUNCH(k_fused_level0<1, double, 12, true>);   // diagonal chol(Qc^-1)
+      else GPS_FUSED_LAUNCH(k_fused_level0<1>);
+      break;
+    default: GPS_FUSED_LAUNCH(k_fused_level0<0>);
+  }
 }
 // fp32 handles: fp32 row tables straight into the fused kernel's fp64 accumulation (round 3: the unfused assembly had cost the
 // fp32 mode more than its halved row traffic saved)
-inline void launch_fused_k(int b, const FusedArgs<double, float> &u, int grid, hipStream_t st, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr) {
+inline void launch_fused_k(int b, const LaunchForm &, const FusedArgs<double, float> &u, int grid, hipStream_t st, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr) {
   if (b == 6) GPS_FUSED_LAUNCH(k_fused_level0<0, float, 6>);
   else GPS_FUSED_LAUNCH(k_fused_level0<0, float>);
 }
-// GPInterpolatedGPSFactorPose3 as 16-double lines: fp64 only (compile(): irow_ok)
+// GPInterpolatedGPSFactorPose3 as 16-double lines: fp64 only (Plan::lines)
 inline void launch_gps_lines_k(const MeasArgs<double> &a, int nb, hipStream_t st) {
-#if GPS_GPS_LINES_WAVES > 0
-  if (a.aidx != nullptr) k_gps_lines<GPS_GPS_LINES_WAVES, true><<<dim3(nb), dim3(128), 0, st>>>(a);   // (round 6: a kernel written for its register count)
-  else k_gps_lines<GPS_GPS_LINES_WAVES, false><<<dim3(nb), dim3(128), 0, st>>>(a);
-#else
-  k_meas<double, POSE3, FK_INTERP_GPS, true, true><<<dim3(nb), dim3(128), 0, st>>>(a);
-#endif
+  if (a.aidx != nullptr) k_gps_lines<kGpsLinesWaves, true><<<dim3(nb), dim3(128), 0, st>>>(a);   // (round 6: a kernel written for its register count)
+  else k_gps_lines<kGpsLinesWaves, false><<<dim3(nb), dim3(128), 0, st>>>(a);
 }
 inline void launch_gps_lines_k(const MeasArgs<float> &, int, hipStream_t) {}
 inline void launch_rows_k(int b, const FwdArgs<double> &a, int grid, hipStream_t st) {

@@ -34,7 +34,7 @@ GpArgs<RowT> gp_args(gpslam_hip_handle *h, const LaunchMode &m, RowT *partial, b
     }
   }
   a.vw = h->vw;
-  a.gps = (kIsF64 && (m.se3_rec || (h->struct3_ok && !m.d3_rows))) ? h->gps.as<RowT>() : nullptr;
+  a.gps = gp_form(h, m) != GpForm::Rows ? h->gps.as<RowT>() : nullptr;
   return a;
 }
 int gp_ngroups(const gpslam_hip_handle *h) { return (int)h->gp_groups.size() / 3; }
@@ -101,11 +101,8 @@ int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot);
 // iteration): Plaza2 (4091 states) 0.152 / 0.192; config 5's SO(3) mix 3e4 0.100 / 0.117, 1e5 0.208 / 0.213, 1e6 1.518 / 1.540;
 // config 4's mix 1e5 0.885 / 0.916, 3e5 1.388 / 1.411, 1e6 3.019 / 2.997 -- joining two streams costs more idle time (12 us and up)
 // than the shorter of two concurrent kernels saves, and two kernels side by side slow each other down: only the segmented
-// landmark path (config 4's mix) at 1e6 states gains (0.7 %), and only it forks.  (-DGPS_FORK_MIN=... for the A/B.)
-#ifndef GPS_FORK_MIN
-#define GPS_FORK_MIN 524288
-#endif
-constexpr int kForkMinStates = GPS_FORK_MIN;
+// landmark path (config 4's mix) at 1e6 states gains (0.7 %), and only it forks.
+constexpr int kForkMinStates = 524288;
 int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot, bool e32 = false) {
   if (!kIsF64 && pass == 1) return impl64::launch_factors(h, m, 1, slot, false);   // an fp32 handle's error is an fp64 error
   RowT *part = h->partial.as<RowT>();
@@ -119,14 +116,15 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
   // GP priors, priors and between factors: ONE launch (k_lin) in the Jacobian pass.  Measurement factors, where a graph
   // has them, are light streaming kernels: they go to a second stream and run underneath (fork / join with events).
   const bool merged = (pass == 0) && !h->gp_left.empty() && gp_ngroups(h) <= 1;
-  if (h->pend_upd && !(merged && kIsF64 && (m.se3_rec || (h->struct3_ok && !m.d3_rows)))) {   // (defensive: an update is pending and this launch cannot apply it)
+  const LaunchForm form = launch_form(h, m);
+  if (h->pend_upd && !(merged && form.gp != GpForm::Rows)) {   // (defensive: an update is pending and this launch cannot apply it)
     h->pend_upd = false;
     int rcp = launch_retract(h, LaunchMode{}, 2);
     if (rcp) return rcp;
   }
   // SE(3) chains whose GP priors travel as structured records: the interpolated measurement factors read their interval's record
   // (Jinv, Jinv Ad, the finite-difference block: MeasArgs::gps) instead of forming the same blocks again, so they run BEHIND k_lin
-  const bool meas_rec = (pass == 0) && kIsF64 && m.se3_rec && h->mf == POSE3 && any_meas;
+  const bool meas_rec = (pass == 0) && form.gp == GpForm::Se3Rec && any_meas;
   // (round 6: only on large graphs, kForkMinStates -- Plaza2's timeline: k_lin 7 us beside k_meas 10 us, then 12 us of nothing before
   //  the reduction starts)
   const bool fork = (pass == 0) && !h->gp_left.empty() && h->aux_stream != nullptr && (merged ? any_meas : true) && !meas_rec && h->N >= kForkMinStates && h->fs.active;
@@ -146,7 +144,7 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
     a.rowLR = compact ? h->rowC.as<RowT>() : h->rowLR.as<RowT>(); a.rowE = compact ? h->rowCE.as<RowT>() : h->rowE.as<RowT>();
     a.partial = partial; a.rowE32 = e32 ? (compact ? h->rowCE.as<float>() : h->rowE.as<float>()) : nullptr;
     // BetweenFactor<Pose3> of a launch whose consumer is the structured fused kernel: records instead of compact rows
-    a.rec = (kind == 2 && kIsF64 && m.se3_rec && h->btw_rec_ok) ? h->brec.as<RowT>() : nullptr;
+    a.rec = (kind == 2 && form.btw_rec) ? h->brec.as<RowT>() : nullptr;
     return a;
   };
   // the previous retraction's maxima, if their reduction was deferred: into this launch (k_lin), or a launch of their own
@@ -192,7 +190,7 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
       constexpr int MF = decltype(tag)::value;
       const bool vp = la.nb[1] > 0;
       if constexpr ((MF == POSE3 || MF == POSE2 || MF == ROT3 || MF == LINEAR3) && kIsF64) {
-        if (la.gp.gps != nullptr) {      // structured GP records (never on a world-velocity chain: struct_ok)
+        if (la.gp.gps != nullptr) {      // structured GP records (never on a world-velocity chain: make_plan)
           if (vp) k_lin<RowT, MF, false, true, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la);
           else k_lin<RowT, MF, false, false, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la);
           if (pend) {                    // the launch wrote every state into the other buffer: that one is current from here on
@@ -267,7 +265,7 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
     }
     const int nb = nblocks(a.count, 128);
     if constexpr (kIsF64) {
-      if (meas_rec && h->irow_ok && fk == FK_INTERP_GPS) {   // 16-double lines for k_fused_level0<4> instead of 24-column rows
+      if (meas_rec && form.lines && fk == FK_INTERP_GPS) {   // 16-double lines for k_fused_level0<4> instead of 24-column rows
         a.rowI = h->rowI.as<RowT>(); a.row0 = s.d_irow0.as<int>();
         a.rowLR = nullptr; a.rowE = nullptr; a.rowM = nullptr; a.rowLm = nullptr;
         launch_gps_lines_k(a, nb, side);
@@ -338,13 +336,11 @@ int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g) {
   a.blk = h->lv[0].blk.as<Real>();
   a.gsave = save_g ? h->gsave.as<Real>() : nullptr;
   a.halo_add = has_right_rank(h) ? h->halo_add.as<Real>() : nullptr;
-  const bool rec3 = kIsF64 && h->struct3_ok && !m.d3_rows;
+  const bool rec3 = gp_form(h, m) == GpForm::D3Rec;
+  int rc;
+  if (rec3 && (rc = refresh_dU(h))) return rc;
   a.gps3 = rec3 ? h->gps.as<Real>() : nullptr;
   a.gpidx = h->gpidx.as<int>(); a.gp_count = (int)h->gp_left.size(); a.Ud = h->dU.as<Real>();
-  if (rec3 && h->gp_single_q == 0 && h->dU_version != h->U_version) {   // set_qc after compile()
-    (void)hipMemcpyAsync(h->dU.p, h->U, 36 * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    h->dU_version = h->U_version;
-  }
   const int nstates = h->N + (a.halo_add ? 1 : 0);
   dispatch_b(h->b, [&](auto tag) {
     constexpr int BB = decltype(tag)::value;
@@ -360,33 +356,7 @@ int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g) {
   return 0;
 }
 
-// Round 4: kernel selection is per handle and visible -- gpslam_hip_config_v2.plan (v1: reserved[6]) is a mask of GPSLAM_PLAN_* bits (the
-// process-environment switches of rounds 2 / 3 are gone).  The fallback families a bit selects are the ones chains with
-// landmark columns, pinned hierarchy shapes or wide borders need anyway; the bits keep them tested on plain chains.
-bool plan(const gpslam_hip_handle *h, int bit) { return (h->cfg.plan & bit) != 0; }
-// k_chunk_forward_rows covers every block size with a single right-hand side (round 3: 6 and 4 as well;
-// GPSLAM_PLAN_COLUMN_LEVEL0 keeps the column-layout kernel)
-bool rows_kernel_applies(const gpslam_hip_handle *h) {
-  if (plan(h, GPSLAM_PLAN_COLUMN_LEVEL0)) return false;
-  return (h->b == 12 || h->b == 6 || h->b == 4) && h->R == 1;
-}
-// k_fused_level0 (assembly inside the level-0 elimination): chains of block size 12 or 6 (round 3: SE(2), SO(3), 3-D linear)
-// without landmark columns (GPSLAM_PLAN_UNFUSED_LEVEL0 keeps k_assemble_ghost + k_chunk_forward_rows); on a sharded handle
-// the rows of the last local state carry their R^T R to the next rank inside the addend the last chunk sends upward,
-// which is what k_assemble_ghost's halo addend used to hold
-bool fused_kernel_applies(const gpslam_hip_handle *h) {
-  const bool off = plan(h, GPSLAM_PLAN_UNFUSED_LEVEL0);
-  // Block size 6: a block step is a fifth of the SE(3) step's arithmetic but keeps its LDS hand-overs and row-ring round trips, so
-  // the fused kernel is latency bound -- it wins while the launch it saves and the chip's ramp matter (1e5 states: C2 0.209 ->
-  // 0.177 ms, C5 SO(3) 0.330 -> 0.296) and loses to the two streaming kernels at scale (1e6: C2 1.35 -> 1.57 ms).  Hence the
-  // size rule.
-  // Round 4: a block-size-6 chain whose full-width rows are (all but a handful) GP priors that travel as d = 3 records (pure6, set by compile()) has
-  // next to nothing left to fetch per block step -- fused at every size (1e6 states: C2 0.99 -> 0.94 ms, 3e5: 0.334 -> 0.321);
-  // with measurement rows in the ring the rule stands (C5 SO(3) + attitude at 1e6: 1.74 unfused, 1.86 fused).
-  const bool b6 = h->b == 6 && (h->N <= 131072 || h->pure6);
-  return (h->b == 12 || b6) && rows_kernel_applies(h) && h->nl == 0 && !off;   // (fp32 rows are widened as the assembly wave reads them)
-}
-void launch_fwd(gpslam_hip_handle *h, const LaunchMode &m, const FwdArgs<Real> &a, int grid) {
+int launch_fwd(gpslam_hip_handle *h, const LaunchMode &m, const FwdArgs<Real> &a, int grid) {
   const bool fast = (4 * h->b + 2 * h->R <= 64);   // room for the separator sums in spare lanes
   // level 0 of a Pose3 chain without landmark columns: four chunks per wave, panel rows in lanes
   if (m.fused && !a.no_sep && !a.add) {
@@ -394,53 +364,46 @@ void launch_fwd(gpslam_hip_handle *h, const LaunchMode &m, const FwdArgs<Real> &
     u.f = a;
     u.rowptr = h->rowptr.as<int>(); u.rowLR = h->rowLR.as<RowT>(); u.rowE = h->rowE.as<RowT>();
     u.crowptr = h->crowptr.as<int>(); u.rowC = h->rowC.as<RowT>(); u.rowCE = h->rowCE.as<RowT>();
-    // SE(3): structured records when the launch says so; d = 3 manifolds: whenever the graph has them (every consumer decodes them)
-    u.gps = (m.se3_rec || (kIsF64 && h->b == 6 && h->struct3_ok && !m.d3_rows)) ? h->gps.as<Real>() : nullptr;
+    int rc;
+    if (gp_form(h, m) != GpForm::Rows && (rc = refresh_dU(h))) return rc;   // (set_qc after compile(): the diagonal form may come or go)
+    const LaunchForm form = launch_form(h, m);
+    u.gps = form.gp != GpForm::Rows ? h->gps.as<Real>() : nullptr;
     u.gp_count = (int)h->gp_left.size();
     u.gpidx = h->gpidx.as<int>();
-    u.brec = (m.se3_rec && h->btw_rec_ok) ? h->brec.as<Real>() : nullptr;
+    u.brec = form.btw_rec ? h->brec.as<Real>() : nullptr;
     u.btwidx = h->btwidx.as<int>(); u.btw_count = h->btw.count();
-    u.odd_rows = (h->M != (int)h->gp_left.size() * h->b) ? (h->odd_many ? 2 : 1) : 0;
+    u.odd_rows = h->plan.odd_rows;
     if constexpr (kIsF64) {
-      if (m.se3_rec && h->irow_ok) { u.rowI = h->rowI.as<Real>(); u.irowptr = h->irowptr.as<int>(); }   // k_fused_level0<4>
+      if (form.lines) { u.rowI = h->rowI.as<Real>(); u.irowptr = h->irowptr.as<int>(); }   // k_fused_level0<4>
     }
     u.gsave = m.gsave ? h->gsave.as<Real>() : nullptr;
     u.gsave2 = m.gsave ? h->gsave2.as<Real>() : nullptr;
     u.simd_cnt = h->simd_cnt.as<int>();
-    if (u.gps != nullptr && h->gp_single_q == 0 && h->dU_version != h->U_version) {   // (36 doubles, stream-ordered: set_qc was called after compile())
-      (void)hipMemcpyAsync(h->dU.p, h->U, 36 * sizeof(double), hipMemcpyHostToDevice, h->stream);
-      h->dU_version = h->U_version;
-    }
     u.Ud = h->dU.as<Real>();
-    {   // a diagonal chol_upper(Qc^-1) (isotropic / diagonal Qc) takes the assembly wave's shorter form
-      const double *Uh = h->gp_single_q > 0 ? &h->gp_Utab[(size_t)(h->gp_single_q - 1) * 36] : h->U;
-      bool dg = h->b == 12 && m.se3_rec && !plan(h, GPSLAM_PLAN_GENERIC_QC);
-      for (int i = 0; i < 6 && dg; i++)
-        for (int j = i + 1; j < 6; j++) dg = dg && Uh[i * 6 + j] == 0.0;
-      u.u_diag = dg ? 1 : 0;
-    }
+    u.u_diag = form.dg ? 1 : 0;   // a diagonal chol_upper(Qc^-1) (isotropic / diagonal Qc) takes the assembly wave's shorter form
 #ifdef GPS_TRACE_FUSED
     h->dbg_trace_waves = nblocks(grid, 4) * 2;
     (void)h->dbg_trace.reserve((size_t)h->dbg_trace_waves * 64 * 8);
     (void)hipMemsetAsync(h->dbg_trace.p, 0, (size_t)h->dbg_trace_waves * 64 * 8, h->stream);
     u.trace = h->dbg_trace.as<unsigned long long>();
 #endif
-    launch_fused_k(h->b, u, nblocks(grid, 4), h->stream, m.l0_events ? h->ev_l0a : nullptr, m.l0_events ? h->ev_l0b : nullptr);
-    return;
+    launch_fused_k(h->b, form, u, nblocks(grid, 4), h->stream, m.l0_events ? h->ev_l0a : nullptr, m.l0_events ? h->ev_l0b : nullptr);
+    return 0;
   }
-  if (rows_kernel_applies(h) && !a.no_sep && !a.add) {
+  if (h->plan.rows() && !a.no_sep && !a.add) {
     launch_rows_k(h->b, a, nblocks(grid, 4), h->stream);
-    return;
+    return 0;
   }
   dispatch_b(h->b, [&](auto tag) {
     constexpr int BB = decltype(tag)::value;
     if (fast) k_chunk_forward<Real, BB, true><<<dim3(grid), dim3(64), 0, h->stream>>>(a);
     else k_chunk_forward<Real, BB, false><<<dim3(grid), dim3(64), 0, h->stream>>>(a);
   });
+  return 0;
 }
 void launch_bwd(gpslam_hip_handle *h, const BwdArgs<Real> &a, int grid) {
   // chains without landmark columns: the row-layout kernel, four chunks per wave (the column-layout plan keeps the generic one)
-  if (a.R == 1 && rows_kernel_applies(h)) { launch_bwd_rows_k(h->b, a, nblocks(grid, 4), h->stream); return; }
+  if (a.R == 1 && h->plan.rows()) { launch_bwd_rows_k(h->b, a, nblocks(grid, 4), h->stream); return; }
   dispatch_b(h->b, [&](auto tag) {
     constexpr int BB = decltype(tag)::value;
     // 16-byte pieces per lane per record: 3 wave loads cover 2 b^2 + b R <= 384 doubles, 5 cover every admissible R
@@ -449,28 +412,57 @@ void launch_bwd(gpslam_hip_handle *h, const BwdArgs<Real> &a, int grid) {
   });
 }
 
-// The levels above level 0 as LDS-resident cyclic reduction, 32 blocks per workgroup and launch (upper.hip): chains
-// without landmark columns (sharded or not), unless the caller pinned the old hierarchy's shape (upper_chunk / top_blocks).
-// GPSLAM_PLAN_LEVELS_OF_FOUR keeps one launch per level of chunks of four.
-bool upper_applies(const gpslam_hip_handle *h) {
-  const bool off = plan(h, GPSLAM_PLAN_LEVELS_OF_FOUR);
-  return !off && h->R == 1 && h->cfg.upper_chunk <= 1 && h->cfg.top_blocks <= 0;
+// Level 1 as groups of four (Plan::tail_fold): a fused level 0 reduces its four chunk separators in its own tail; the unfused
+// level-0 kernels leave that level to a launch of upper.hip's kernel with G = 4.
+bool tail_now(const gpslam_hip_handle *h, const LaunchMode &m) { return h->plan.tail_fold && m.fused; }
+
+// The forward elimination of level l as one of the chunk kernels of this file runs it, and its grid.  Unsharded: the last level is
+// the top solve.  Sharded: every level keeps its first block as separator; the last level reduces to the interface record.
+FwdArgs<Real> fwd_args(gpslam_hip_handle *h, const LaunchMode &m, int l, double lambda, int &grid) {
+  const size_t BS = (size_t)2 * h->b * h->b + (size_t)h->b * h->R, AS = (size_t)h->b * h->b + (size_t)h->b * h->R;
+  Level &v = h->lv[l];
+  const bool last = (l == (int)h->lv.size() - 1);
+  FwdArgs<Real> a;
+  a.blk = v.blk.as<Real>();
+  a.add = (l > 0) ? v.add.as<Real>() : nullptr;
+  a.n = v.n; a.R = h->R;
+  a.m = last ? v.n : v.m;
+  a.lambda = (l == 0) ? (Real)lambda : Real(0);
+  a.flag = h->flag.as<int>();
+  a.remote_add = nullptr;
+  a.l1_blk = nullptr; a.tail = 0;
+  grid = last ? 1 : v.nch;
+  if (!sharded(h)) {
+    a.up_blk = last ? nullptr : h->lv[l + 1].blk.as<Real>();
+    a.up_add = last ? nullptr : h->lv[l + 1].add.as<Real>();
+    a.no_sep = last ? 1 : 0;
+    a.last_has_right = 0;
+    if (l == 0 && tail_now(h, m)) {   // the fused kernel reduces its four separators itself: its output is level 2's input
+      a.tail = 1;
+      a.l1_blk = h->lv[1].blk.as<Real>();
+      a.up_blk = h->lv[2].blk.as<Real>();
+      a.up_add = h->lv[2].add.as<Real>();
+    }
+  } else {
+    a.up_blk = last ? h->iface_send.as<Real>() : h->lv[l + 1].blk.as<Real>();
+    // the interface record is [blk (BS) | addend slot 1 (AS)]; addend slot 0 is unused, so point one slot back
+    a.up_add = last ? h->iface_send.as<Real>() + BS - AS : h->lv[l + 1].add.as<Real>();
+    a.no_sep = 0;
+    a.last_has_right = has_right_rank(h) ? 1 : 0;
+    if (a.last_has_right) a.remote_add = (l == 0) ? h->halo_add.as<Real>() : v.add.as<Real>() + (size_t)v.n * AS;
+  }
+  return a;
 }
-// Level 1 as groups of four (compile()): k_fused_level0 then reduces its four chunk separators in its own tail; the
-// unfused level-0 kernels leave that level to a launch of upper.hip's kernel with G = 4.
-bool tail_now(const gpslam_hip_handle *h, const LaunchMode &m) {
-  return h->upper_ok && m.fused && h->lv.size() >= 3 && h->lv[1].m == 4;
-}
-// Forward elimination through the local levels.  Unsharded: the last level is the top solve.
-// Sharded: every level keeps its first block as separator; the last level reduces to the interface record.
+// Forward elimination through the local levels.
 int launch_forward(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
   const int nl = (int)h->lv.size();
   const bool sh = sharded(h);
   const size_t BS = (size_t)2 * h->b * h->b + (size_t)h->b * h->R, AS = (size_t)h->b * h->b + (size_t)h->b * h->R;
+  int rc;
   for (int l = 0; l < nl; l++) {
     Level &v = h->lv[l];
     const bool last = (l == nl - 1);
-    if (h->upper_ok && l >= 1) {   // (the last level also solves and back-substitutes itself)
+    if (h->plan.upper_cr && l >= 1) {   // (the last level also solves and back-substitutes itself)
       if (l == 1 && tail_now(h, m)) continue;   // done in the tail of the level-0 kernel
       UpFwdArgs u;
       u.blk = v.blk.as<double>(); u.add = v.add.as<double>();
@@ -485,39 +477,9 @@ int launch_forward(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
       if (e) { h->err = std::string("upper_forward: ") + hipGetErrorString((hipError_t)e); return GPSLAM_E_HIP; }
       continue;
     }
-    FwdArgs<Real> a;
-    a.blk = v.blk.as<Real>();
-    a.add = (l > 0) ? v.add.as<Real>() : nullptr;
-    a.n = v.n; a.R = h->R;
-    a.lambda = (l == 0) ? (Real)lambda : Real(0);
-    a.flag = h->flag.as<int>();
-    a.remote_add = nullptr;
-    a.l1_blk = nullptr; a.tail = 0;
     int grid;
-    if (!sh) {
-      a.up_blk = last ? nullptr : h->lv[l + 1].blk.as<Real>();
-      a.up_add = last ? nullptr : h->lv[l + 1].add.as<Real>();
-      a.m = last ? v.n : v.m;
-      a.no_sep = last ? 1 : 0;
-      a.last_has_right = 0;
-      grid = last ? 1 : v.nch;
-      if (l == 0 && tail_now(h, m)) {   // the fused kernel reduces its four separators itself: its output is level 2's input
-        a.tail = 1;
-        a.l1_blk = h->lv[1].blk.as<Real>();
-        a.up_blk = h->lv[2].blk.as<Real>();
-        a.up_add = h->lv[2].add.as<Real>();
-      }
-    } else {
-      a.up_blk = last ? h->iface_send.as<Real>() : h->lv[l + 1].blk.as<Real>();
-      // the interface record is [blk (BS) | addend slot 1 (AS)]; addend slot 0 is unused, so point one slot back
-      a.up_add = last ? h->iface_send.as<Real>() + BS - AS : h->lv[l + 1].add.as<Real>();
-      a.m = last ? v.n : v.m;
-      a.no_sep = 0;
-      a.last_has_right = has_right_rank(h) ? 1 : 0;
-      if (a.last_has_right) a.remote_add = (l == 0) ? h->halo_add.as<Real>() : v.add.as<Real>() + (size_t)v.n * AS;
-      grid = last ? 1 : v.nch;
-    }
-    launch_fwd(h, m, a, grid);
+    const FwdArgs<Real> a = fwd_args(h, m, l, lambda, grid);
+    if ((rc = launch_fwd(h, m, a, grid))) return rc;
     if (l == 0 && m.stamp_l0) HIPCHK(hipEventRecord(h->ev[5], h->stream));
   }
   HIPCHK(hipGetLastError());
@@ -526,16 +488,32 @@ int launch_forward(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
 
 // Back-substitution through the local levels; xtop = separator solutions for the last level (sharded) or null
 // Level 1 as groups of four whose groups are exactly the waves of the row-layout level-0 back-substitution (four chunks per wave):
-// that kernel then solves its group itself and the launch of k_multi_backward<B, 4> is dropped (unsharded fp64 chains; A/B on one
-// box: 0.3066 vs 0.3118 ms per iteration at 1e5 Pose3 states, 2.43-2.45 vs 2.45-2.46 ms at 1e6).
+// that kernel then solves its group itself and the launch of k_multi_backward<B, 4> is dropped (Plan::fold_tail_bwd: unsharded fp64
+// chains; A/B on one box: 0.3066 vs 0.3118 ms per iteration at 1e5 Pose3 states, 2.43-2.45 vs 2.45-2.46 ms at 1e6).
 // Layout contract (ADVICE r4): whichever kernel reduces the level of groups of four -- the tail of k_fused_level0 (default) or
 // upper.hip's k_multi_forward<B, 4> (GPSLAM_PLAN_UNFUSED_LEVEL0, the Levenberg-Marquardt trials of the unfused pair) -- leaves that
 // level's factor records in lv[1].blk as column-major [V | U | Y] (the one record layout of the solver: BwdArgs::blk, UpBwdArgs::blk)
 // and the solutions of the groups' first blocks in lv[2].x; k_chunk_backward_rows reads exactly those two through BwdArgs::l1_blk /
 // l1_xup.  tests/test_gpu_switches.py runs both producers against the oracle (chains whose lv[1].n % 4 is 1, 2 and 3 included).
-bool fold_tail_bwd(const gpslam_hip_handle *h) {
-  return kIsF64 && h->upper_ok && !sharded(h) && h->R == 1 && rows_kernel_applies(h) && h->lv.size() >= 3 && h->lv[1].m == 4 &&
-         h->lv[1].n == h->lv[0].nch;
+BwdArgs<Real> bwd_args(gpslam_hip_handle *h, int l, const Real *xtop, int &grid) {
+  Level &v = h->lv[l];
+  const bool last = (l == (int)h->lv.size() - 1);
+  BwdArgs<Real> a;
+  a.blk = v.blk.as<Real>(); a.x = v.x.as<Real>();
+  a.n = v.n; a.R = h->R;
+  a.m = last ? v.n : v.m;
+  grid = last ? 1 : v.nch;
+  if (!sharded(h)) {
+    a.xup = last ? nullptr : h->lv[l + 1].x.as<Real>();
+    a.no_sep = last ? 1 : 0; a.last_has_right = 0;
+    if (l == 0 && h->plan.fold_tail_bwd) {
+      a.l1_blk = h->lv[1].blk.as<Real>(); a.l1_xup = h->lv[2].x.as<Real>(); a.l1_n = h->lv[1].n;
+    }
+  } else {
+    a.xup = last ? xtop : h->lv[l + 1].x.as<Real>();
+    a.no_sep = 0; a.last_has_right = has_right_rank(h) ? 1 : 0;
+  }
+  return a;
 }
 int launch_backward(gpslam_hip_handle *h, const Real *xtop) {
   const int nl = (int)h->lv.size();
@@ -543,9 +521,9 @@ int launch_backward(gpslam_hip_handle *h, const Real *xtop) {
   for (int l = nl - 1; l >= 0; l--) {
     Level &v = h->lv[l];
     const bool last = (l == nl - 1);
-    if (h->upper_ok && l >= 1) {
+    if (h->plan.upper_cr && l >= 1) {
       if (last && !sh) continue;   // solved inside its forward launch
-      if (l == 1 && fold_tail_bwd(h)) continue;   // the level of groups of four: k_chunk_backward_rows solves its own group
+      if (l == 1 && h->plan.fold_tail_bwd) continue;   // the level of groups of four: k_chunk_backward_rows solves its own group
       UpBwdArgs u;
       u.blk = v.blk.as<double>(); u.x = v.x.as<double>(); u.n = v.n;
       u.xup = last ? xtop : h->lv[l + 1].x.as<double>();
@@ -554,20 +532,9 @@ int launch_backward(gpslam_hip_handle *h, const Real *xtop) {
       if (e) { h->err = std::string("upper_backward: ") + hipGetErrorString((hipError_t)e); return GPSLAM_E_HIP; }
       continue;
     }
-    BwdArgs<Real> a;
-    a.blk = v.blk.as<Real>(); a.x = v.x.as<Real>();
-    a.n = v.n; a.R = h->R;
-    if (!sh) {
-      a.xup = last ? nullptr : h->lv[l + 1].x.as<Real>();
-      a.m = last ? v.n : v.m; a.no_sep = last ? 1 : 0; a.last_has_right = 0;
-      if (l == 0 && fold_tail_bwd(h)) {
-        a.l1_blk = h->lv[1].blk.as<Real>(); a.l1_xup = h->lv[2].x.as<Real>(); a.l1_n = h->lv[1].n;
-      }
-    } else {
-      a.xup = last ? xtop : h->lv[l + 1].x.as<Real>();
-      a.m = last ? v.n : v.m; a.no_sep = 0; a.last_has_right = has_right_rank(h) ? 1 : 0;
-    }
-    launch_bwd(h, a, last ? 1 : v.nch);
+    int grid;
+    const BwdArgs<Real> a = bwd_args(h, l, xtop, grid);
+    launch_bwd(h, a, grid);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -930,7 +897,7 @@ int fs_build(gpslam_hip_handle *h, const std::vector<int> &touch_lo, const std::
   HIPCHK(p.fac.reserve((size_t)N * 2 * b * b * sizeof(Real)));
   {   // k_fs_sweep_syrk: planar chains (block size 6), borders up to 112 columns.  GPSLAM_PLAN_FS_TWO_LAUNCHES: the two launches
       // through the Y buffer (N x B x NCP doubles) that wider borders and other block sizes take
-    const bool off = plan(h, GPSLAM_PLAN_FS_TWO_LAUNCHES);
+    const bool off = plan_bit(h, GPSLAM_PLAN_FS_TWO_LAUNCHES);
     p.fused_sweep = !off && b == 6 && p.NCP <= 112 && p.NC <= 128 && p.NCP >= 32;
   }
   if (p.fused_sweep) {
@@ -1034,19 +1001,30 @@ int launch_solve(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
   return launch_landmarks(h, lambda);
 }
 
-// x <- x (+) delta for the local states (and landmarks); scal[slot] = |delta|_inf
-int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot) {
+// k_retract over the local states: its arguments and its grid (one workgroup more when this iteration's error partial sums are
+// still waiting in `partial`: the launch takes them along)
+RetractArgs<Real> retract_args(gpslam_hip_handle *h, int &grid) {
   RetractArgs<Real> a;
   a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride; a.N = h->N; a.R = h->R;
   a.chart = h->cfg.chart; a.first = 0; a.x = h->lv[0].x.as<Real>(); a.partial = h->partial2.as<Real>(); a.flag = h->flag.as<int>();
-  const int nb = nblocks(h->N, 128);
-  const bool red = h->pend_err_n > 0;                 // this iteration's error partial sums are still waiting in `partial`
+  const bool red = h->pend_err_n > 0;
   a.red_in = red ? h->partial.as<double>() : nullptr; a.red_n = h->pend_err_n; a.red_out = h->scal.as<double>() + h->pend_err_slot;
+  grid = nblocks(h->N, 128) + (red ? 1 : 0);
+  return a;
+}
+void launch_retract_k(gpslam_hip_handle *h) {
+  int grid;
+  const RetractArgs<Real> a = retract_args(h, grid);
   h->pend_err_n = 0;
   dispatch_mf(h->mf, [&](auto tag) {
     constexpr int MF = decltype(tag)::value;
-    k_retract<Real, MF><<<dim3(nb + (red ? 1 : 0)), dim3(128), 0, h->stream>>>(a);
+    k_retract<Real, MF><<<dim3(grid), dim3(128), 0, h->stream>>>(a);
   });
+}
+// x <- x (+) delta for the local states (and landmarks); scal[slot] = |delta|_inf
+int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot) {
+  const int nb = nblocks(h->N, 128);
+  launch_retract_k(h);
   if (m.defer_maxima && h->nl == 0) { h->pend_dmax_n = nb; h->pend_dmax_slot = slot; }   // reduced by the next linearisation's launch
   else k_final_reduce<Real><<<dim3(1), dim3(256), 0, h->stream>>>(h->partial2.as<Real>(), nb, h->scal.as<double>() + slot, 1);
   if (h->nl > 0 && h->fs.active) {
@@ -1114,32 +1092,36 @@ int launch_dot3(gpslam_hip_handle *h, const Real *x, const Real *y0, const Real 
   return 0;
 }
 
-int gpslam_hip_compile(gpslam_hip_handle *h) {
-  if (!h || h->N <= 0) return GPSLAM_E_INVALID;
-  (void)hipSetDevice(h->cfg.device);
+// ---- compile(): its steps, in the order gpslam_hip_compile calls them
+
+// factors were range-checked against the N and L of the moment they were added; set_states / set_landmarks may
+// have shrunk either since (ADVICE r1): re-validate every stored index before it is used to size or index anything
+int check_stored_indices(gpslam_hip_handle *h) {
+  const int N = h->N, ml = max_left(h);
+  auto bad = [](const std::vector<int32_t> &v, int hi) { for (int32_t i : v) if (i < 0 || i > hi) return true; return false; };
+  if (bad(h->gp_left, ml) || bad(h->btw.idx, ml) || bad(h->pri.idx, N - 1) || bad(h->vpri.idx, N - 1) || bad(h->lpri.idx, h->L - 1))
+    return fail(h, GPSLAM_E_INVALID, "a stored factor refers to a state / landmark that no longer exists (set_states / set_landmarks shrank the problem)");
+  for (const MeasSet &s : h->ms)
+    if (bad(s.idx, s.two ? ml : N - 1) || (s.haslm && bad(s.lm, h->L - 1)))
+      return fail(h, GPSLAM_E_INVALID, "a stored measurement factor refers to a state / landmark that no longer exists");
+  return 0;
+}
+
+// The right-hand sides of the chain solver, R = [update | landmark columns | closure columns], and where the landmarks go.
+// Up to kMaxRhs - 1 landmark columns ride through the whole chain solver as extra right-hand sides (the dense border, Plaza's
+// handful of beacons).  More than that -- config 4's 5e4 locally visible landmarks -- go through the segmented elimination with
+// fat separators (fatsep.hpp); force_segmented = 1 forces that path for any landmark count.
+int choose_landmark_path(gpslam_hip_handle *h, bool &segmented) {
   const int N = h->N, d = h->d, b = h->b;
-  {   // factors were range-checked against the N and L of the moment they were added; set_states / set_landmarks may
-      // have shrunk either since (ADVICE r1): re-validate every stored index before it is used to size or index anything
-    const int ml = max_left(h);
-    auto bad = [](const std::vector<int32_t> &v, int hi) { for (int32_t i : v) if (i < 0 || i > hi) return true; return false; };
-    if (bad(h->gp_left, ml) || bad(h->btw.idx, ml) || bad(h->pri.idx, N - 1) || bad(h->vpri.idx, N - 1) || bad(h->lpri.idx, h->L - 1))
-      return fail(h, GPSLAM_E_INVALID, "a stored factor refers to a state / landmark that no longer exists (set_states / set_landmarks shrank the problem)");
-    for (const MeasSet &s : h->ms)
-      if (bad(s.idx, s.two ? ml : N - 1) || (s.haslm && bad(s.lm, h->L - 1)))
-        return fail(h, GPSLAM_E_INVALID, "a stored measurement factor refers to a state / landmark that no longer exists");
-  }
   h->nl = h->L * h->ld;
   h->nclo = h->clo.count();
   h->nc = h->nclo * d;
   for (int k = 0; k < h->nclo; k++)
     if (h->clo.idx[k] >= N || h->clo_second[k] >= N)
       return fail(h, GPSLAM_E_INVALID, "a stored loop closure refers to a state that no longer exists (set_states shrank the problem)");
-  h->R = 1 + h->nl + h->nc;      // [update | landmark columns | closure columns]
+  h->R = 1 + h->nl + h->nc;
   h->fs.active = false;
-  // Landmark columns: up to kMaxRhs - 1 of them ride through the whole chain solver as extra right-hand sides (the dense
-  // border, Plaza's handful of beacons).  More than that -- config 4's 5e4 locally visible landmarks -- go through the
-  // segmented elimination with fat separators (fatsep.hpp); force_segmented = 1 forces that path for any landmark count.
-  const bool segmented = h->nl > 0 && (h->cfg.force_segmented == 1 || h->fs.split || 3 * b + h->R > 64 || h->R > kMaxRhs);
+  segmented = h->nl > 0 && (h->cfg.force_segmented == 1 || h->fs.split || 3 * b + h->R > 64 || h->R > kMaxRhs);
   if (h->fs.split) {
     if (!segmented) return fail(h, GPSLAM_E_INVALID, "a piece of a split chain (fs_set_split) needs landmarks: chains without them shard with nranks > 1");
     for (const std::vector<int> *v : {&h->fs.first_lm, &h->fs.last_lm})
@@ -1157,65 +1139,89 @@ int gpslam_hip_compile(gpslam_hip_handle *h) {
     if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "the segmented landmark elimination splits across GPUs through gpslam_hip_fs_set_split (pieces joined at shared cut states), not through nranks > 1");
     h->R = 1;   // no landmark columns inside the chain solver
   }
-  // ---- row layout: rows grouped by left state; inside a state: GP, pose prior, velocity prior, between, measurements
-  std::vector<int> rows_in(N + 1, 0);
+  return 0;
+}
+
+// Where every factor's rows sit in the two row tables, and what the record forms need to know about that placement
+struct RowLayout {
+  std::vector<int> rowptr, crowptr;                                        // N + 2 row pointers: full-width table, compact table
+  std::vector<int> gp_row0, r_pri, r_vpri, r_btw, r_ms[kNumMeasKinds];    // first row of every factor
+  std::vector<int> gpidx, btwidx;          // N + 2 entries: the GP prior / between factor whose left state is s, or -1
+  bool one_gp = true, one_btw = true;      // at most one GP prior / between factor per left state
+  bool gp_rows_lead = true, btw_rows_trail = true;
+};
+bool index_by_left(const std::vector<int32_t> &left, int N, std::vector<int> &idx) {
+  idx.assign(N + 2, -1);
+  bool one = true;
+  for (size_t f = 0; f < left.size(); f++) {
+    if (idx[left[f]] >= 0) one = false;
+    idx[left[f]] = (int)f;
+  }
+  return one;
+}
+// rows grouped by left state; inside a state: GP, pose prior, velocity prior, between, measurements.  Pose priors and between
+// factors are velocity-free: their rows go to the compact table.
+void layout_rows(gpslam_hip_handle *h, RowLayout &lay) {
+  const int N = h->N, d = h->d, b = h->b;
+  std::vector<int> rows_in(N + 1, 0), crows_in(N + 1, 0);
   for (int32_t l : h->gp_left) rows_in[l] += b;
   for (int32_t i : h->vpri.idx) rows_in[i] += d;
-  std::vector<int> crows_in(N + 1, 0);       // compact rows: pose priors, between factors
   for (int32_t i : h->pri.idx) crows_in[i] += d;
   for (int32_t i : h->btw.idx) crows_in[i] += d;
   for (MeasSet &s : h->ms) for (int32_t i : s.idx) rows_in[i] += s.rows;
-  std::vector<int> rowptr(N + 2, 0);
-  for (int s = 0; s <= N; s++) rowptr[s + 1] = rowptr[s] + rows_in[s];
-  h->M = rowptr[N + 1];
-  std::vector<int> cursor(rowptr.begin(), rowptr.end() - 1);
-  std::vector<int> gp_row0(h->gp_left.size());
-  for (size_t f = 0; f < h->gp_left.size(); f++) { gp_row0[f] = cursor[h->gp_left[f]]; cursor[h->gp_left[f]] += b; }
-  auto place = [&](const std::vector<int32_t> &idx, int rows, std::vector<int> &row0) {
+  lay.rowptr.assign(N + 2, 0);
+  lay.crowptr.assign(N + 2, 0);
+  for (int s = 0; s <= N; s++) { lay.rowptr[s + 1] = lay.rowptr[s] + rows_in[s]; lay.crowptr[s + 1] = lay.crowptr[s] + crows_in[s]; }
+  h->M = lay.rowptr[N + 1];
+  h->Mc = lay.crowptr[N + 1];
+  std::vector<int> cursor(lay.rowptr.begin(), lay.rowptr.end() - 1), ccursor(lay.crowptr.begin(), lay.crowptr.end() - 1);
+  auto place = [](std::vector<int> &cur, const std::vector<int32_t> &idx, int rows, std::vector<int> &row0) {
     row0.resize(idx.size());
-    for (size_t f = 0; f < idx.size(); f++) { row0[f] = cursor[idx[f]]; cursor[idx[f]] += rows; }
+    for (size_t f = 0; f < idx.size(); f++) { row0[f] = cur[idx[f]]; cur[idx[f]] += rows; }
   };
-  std::vector<int> crowptr(N + 2, 0);
-  for (int s = 0; s <= N; s++) crowptr[s + 1] = crowptr[s] + crows_in[s];
-  h->Mc = crowptr[N + 1];
-  std::vector<int> ccursor(crowptr.begin(), crowptr.end() - 1);
-  auto cplace = [&](const std::vector<int32_t> &idx, int rows, std::vector<int> &row0) {
-    row0.resize(idx.size());
-    for (size_t f = 0; f < idx.size(); f++) { row0[f] = ccursor[idx[f]]; ccursor[idx[f]] += rows; }
-  };
-  std::vector<int> r_pri, r_vpri, r_btw, r_ms[kNumMeasKinds];
-  cplace(h->pri.idx, d, r_pri);
-  place(h->vpri.idx, d, r_vpri);
-  cplace(h->btw.idx, d, r_btw);
-  for (int fk = 0; fk < kNumMeasKinds; fk++) place(h->ms[fk].idx, h->ms[fk].rows, r_ms[fk]);
+  place(cursor, h->gp_left, b, lay.gp_row0);
+  place(ccursor, h->pri.idx, d, lay.r_pri);
+  place(cursor, h->vpri.idx, d, lay.r_vpri);
+  place(ccursor, h->btw.idx, d, lay.r_btw);
+  for (int fk = 0; fk < kNumMeasKinds; fk++) place(cursor, h->ms[fk].idx, h->ms[fk].rows, lay.r_ms[fk]);
   // What the record decoders assume about this placement (k_assemble_ghost's `rp_s += B`, k_fused_level0's `p0 += B` / `q1 -= Dh`):
   // a state's GP-prior rows LEAD its range of the full-width table and its between factor's rows END its range of the compact
   // table.  True by the order of the calls above; checked here so that a change of that order turns the record paths off
-  // (struct_ok / struct3_ok / btw_rec_ok below) instead of silently skipping or double-counting rows (ADVICE r4).
-  h->gp_rows_lead = true;
-  for (size_t f = 0; f < h->gp_left.size(); f++) h->gp_rows_lead = h->gp_rows_lead && gp_row0[f] == rowptr[h->gp_left[f]];
-  h->btw_rows_trail = true;
-  for (size_t f = 0; f < h->btw.idx.size(); f++) h->btw_rows_trail = h->btw_rows_trail && r_btw[f] + d == crowptr[h->btw.idx[f] + 1];
+  // (make_plan) instead of silently skipping or double-counting rows (ADVICE r4).
+  for (size_t f = 0; f < h->gp_left.size(); f++) lay.gp_rows_lead = lay.gp_rows_lead && lay.gp_row0[f] == lay.rowptr[h->gp_left[f]];
+  for (size_t f = 0; f < h->btw.idx.size(); f++) lay.btw_rows_trail = lay.btw_rows_trail && lay.r_btw[f] + d == lay.crowptr[h->btw.idx[f] + 1];
+  lay.one_gp = index_by_left(h->gp_left, N, lay.gpidx);
+  lay.one_btw = index_by_left(h->btw.idx, N, lay.btwidx);
+}
+
+// GP priors with more than one distinct Qc: the device-side arrays are ordered by Qc, one launch per group (host side only)
+void group_gp_by_qc(gpslam_hip_handle *h) {
+  const size_t F = h->gp_left.size();
+  if (h->gp_q.size() != F) h->gp_q.assign(F, 0);
+  h->gp_perm.resize(F);
+  for (size_t f = 0; f < F; f++) h->gp_perm[f] = (int32_t)f;
+  std::stable_sort(h->gp_perm.begin(), h->gp_perm.end(), [&](int32_t x, int32_t y) { return h->gp_q[x] < h->gp_q[y]; });
+  h->gp_groups.clear();
+  for (size_t k = 0; k < F; k++) {
+    const int q = h->gp_q[h->gp_perm[k]];
+    if (h->gp_groups.empty() || h->gp_groups[h->gp_groups.size() - 3] != q) { h->gp_groups.push_back(q); h->gp_groups.push_back((int32_t)k); h->gp_groups.push_back(0); }
+    h->gp_groups.back()++;
+  }
+  if (h->gp_groups.size() == 3 && h->gp_groups[0] == 0) h->gp_groups.clear();   // the common case: everything shares set_qc's Qc
+  // every prior added with its own Qc_model, all of them the same matrix (what the host classes and the GTSAM adapter
+  // produce for a graph with one shared Qc): still ONE launch, and the structured records use that U (ADVICE r3)
+  h->gp_single_q = (h->gp_groups.size() == 3 && h->gp_groups[0] > 0) ? h->gp_groups[0] : 0;
+}
+
+// every factor set and the row pointers to the device, the row tables sized; npart: partial sums the factor kernels of one pass leave
+int upload_factors(gpslam_hip_handle *h, const RowLayout &lay, int &npart) {
+  const int d = h->d, b = h->b;
   int rc;
-  if ((rc = upload(h, h->rowptr, rowptr))) return rc;
-  {   // GP priors with more than one distinct Qc: device-side arrays ordered by Qc, one launch per group
+  if ((rc = upload(h, h->rowptr, lay.rowptr))) return rc;
+  {
     const size_t F = h->gp_left.size();
-    if (h->gp_q.size() != F) h->gp_q.assign(F, 0);
-    h->gp_perm.resize(F);
-    for (size_t f = 0; f < F; f++) h->gp_perm[f] = (int32_t)f;
-    std::stable_sort(h->gp_perm.begin(), h->gp_perm.end(), [&](int32_t x, int32_t y) { return h->gp_q[x] < h->gp_q[y]; });
-    h->gp_groups.clear();
-    for (size_t k = 0; k < F; k++) {
-      const int q = h->gp_q[h->gp_perm[k]];
-      if (h->gp_groups.empty() || h->gp_groups[h->gp_groups.size() - 3] != q) { h->gp_groups.push_back(q); h->gp_groups.push_back((int32_t)k); h->gp_groups.push_back(0); }
-      h->gp_groups.back()++;
-    }
-    if (h->gp_groups.size() == 3 && h->gp_groups[0] == 0) h->gp_groups.clear();   // the common case: everything shares set_qc's Qc
-    // every prior added with its own Qc_model, all of them the same matrix (what the host classes and the GTSAM adapter
-    // produce for a graph with one shared Qc): still ONE launch, and the structured records use that U (ADVICE r3)
-    h->gp_single_q = (h->gp_groups.size() == 3 && h->gp_groups[0] > 0) ? h->gp_groups[0] : 0;
     std::vector<int32_t> pl(F); std::vector<double> pdt(F); std::vector<int> pr(F);
-    for (size_t k = 0; k < F; k++) { pl[k] = h->gp_left[h->gp_perm[k]]; pdt[k] = h->gp_dt[h->gp_perm[k]]; pr[k] = gp_row0[h->gp_perm[k]]; }
+    for (size_t k = 0; k < F; k++) { pl[k] = h->gp_left[h->gp_perm[k]]; pdt[k] = h->gp_dt[h->gp_perm[k]]; pr[k] = lay.gp_row0[h->gp_perm[k]]; }
     if ((rc = upload(h, h->d_gp_left, pl))) return rc;
     if ((rc = upload(h, h->d_gp_dt, pdt))) return rc;
     if ((rc = upload(h, h->d_gp_row0, pr))) return rc;
@@ -1227,27 +1233,27 @@ int gpslam_hip_compile(gpslam_hip_handle *h) {
     if ((r2 = upload(h, s.d_sig, s.sig))) return r2;
     return upload(h, s.d_row0, row0);
   };
-  if ((rc = up_set(h->pri, r_pri))) return rc;
-  if ((rc = up_set(h->vpri, r_vpri))) return rc;
-  if ((rc = up_set(h->btw, r_btw))) return rc;
-  { std::vector<int> none; if ((rc = up_set(h->lpri, none))) return rc; }
+  const std::vector<int> none;
+  if ((rc = up_set(h->pri, lay.r_pri))) return rc;
+  if ((rc = up_set(h->vpri, lay.r_vpri))) return rc;
+  if ((rc = up_set(h->btw, lay.r_btw))) return rc;
+  if ((rc = up_set(h->lpri, none))) return rc;
   if (h->nclo > 0) {
-    std::vector<int> none;
     if ((rc = up_set(h->clo, none))) return rc;
     if ((rc = upload(h, h->d_clo_second, h->clo_second))) return rc;
     HIPCHK(h->clo_A.reserve((size_t)h->nclo * kCloLen(d) * sizeof(double)));
     HIPCHK(h->clo_Y.reserve((size_t)h->nc * (1 + h->nl) * sizeof(double)));
   }
   // (one k_gp launch per distinct Qc, each rounding its factor count up to whole blocks: at most one extra slot per group)
-  int npart = nblocks((int)h->gp_left.size(), 128) + gp_ngroups(h) + nblocks(h->pri.count(), 128) + nblocks(h->vpri.count(), 128) +
-              nblocks(h->btw.count(), 128) + 1 + 256 + 1;   // (+ 1: the loop closures' error)
+  npart = nblocks((int)h->gp_left.size(), 128) + gp_ngroups(h) + nblocks(h->pri.count(), 128) + nblocks(h->vpri.count(), 128) +
+          nblocks(h->btw.count(), 128) + 1 + 256 + 1;   // (+ 1: the loop closures' error)
   for (int fk = 0; fk < kNumMeasKinds; fk++) {
     MeasSet &s = h->ms[fk];
     if ((rc = upload(h, s.d_idx, s.idx))) return rc;
     if ((rc = upload(h, s.d_lm, s.lm))) return rc;
     if ((rc = upload(h, s.d_meas, s.meas))) return rc;
     if ((rc = upload(h, s.d_sig, s.sig))) return rc;
-    if ((rc = upload(h, s.d_row0, r_ms[fk]))) return rc;
+    if ((rc = upload(h, s.d_row0, lay.r_ms[fk]))) return rc;
     std::vector<double> coef((size_t)(s.interp ? s.count() : 0) * 4);
     for (int k = 0; k < (s.interp ? s.count() : 0); k++) interp_coef(s.dt[k], s.tau[k], &coef[4 * (size_t)k]);
     if ((rc = upload(h, s.d_coef, coef))) return rc;
@@ -1264,62 +1270,74 @@ int gpslam_hip_compile(gpslam_hip_handle *h) {
   HIPCHK(h->rowE.reserve((Mrows + 1) * sizeof(RowT)));
   HIPCHK(h->rowC.reserve((size_t)(std::max(h->Mc, 1) + 1) * b * sizeof(RowT)));
   HIPCHK(h->rowCE.reserve((size_t)(std::max(h->Mc, 1) + 1) * sizeof(RowT)));
-  if ((rc = upload(h, h->crowptr, crowptr))) return rc;
-  // ---- landmark border bookkeeping
+  return upload(h, h->crowptr, lay.crowptr);
+}
+
+// landmark columns of the rows, the rows of each landmark (by left state), and -- dense border -- their chunked reduction;
+// touch_lo / touch_hi: first / last state the factors of each landmark touch (what the segmented path cuts the chain by)
+int build_landmark_border(gpslam_hip_handle *h, const RowLayout &lay, bool segmented, std::vector<int> &touch_lo, std::vector<int> &touch_hi) {
+  int rc;
   h->nlmrows = 0;
-  std::vector<int> touch_lo(h->L, -1), touch_hi(h->L, -1);   // first / last state the factors of each landmark touch
-  if (h->nl > 0) {
-    HIPCHK(h->rowM.reserve((Mrows + 1) * h->ld * sizeof(RowT)));
-    HIPCHK(h->rowLm.reserve((Mrows + 1) * sizeof(int)));
-    HIPCHK(hipMemsetAsync(h->rowM.p, 0, Mrows * h->ld * sizeof(RowT), h->stream));
-    HIPCHK(hipMemsetAsync(h->rowLm.p, 0xFF, Mrows * sizeof(int), h->stream));  // -1: row touches no landmark
-    std::vector<std::vector<std::pair<int, int>>> per_lm(h->L);              // (row, state)
-    for (int fk = 0; fk < kNumMeasKinds; fk++) {
-      MeasSet &s = h->ms[fk];
-      if (!s.haslm) continue;
-      for (int f = 0; f < s.count(); f++) {
-        for (int r = 0; r < s.rows; r++) per_lm[s.lm[f]].push_back({r_ms[fk][f] + r, s.idx[f]});
-        int &lo = touch_lo[s.lm[f]], &hi = touch_hi[s.lm[f]];
-        const int last = s.idx[f] + (s.two ? 1 : 0);
-        lo = (lo < 0) ? s.idx[f] : std::min(lo, (int)s.idx[f]);
-        hi = std::max(hi, last);
-      }
+  touch_lo.assign(h->L, -1);
+  touch_hi.assign(h->L, -1);
+  if (h->nl <= 0) return 0;
+  const size_t Mrows = (size_t)std::max(h->M, 1);
+  HIPCHK(h->rowM.reserve((Mrows + 1) * h->ld * sizeof(RowT)));
+  HIPCHK(h->rowLm.reserve((Mrows + 1) * sizeof(int)));
+  HIPCHK(hipMemsetAsync(h->rowM.p, 0, Mrows * h->ld * sizeof(RowT), h->stream));
+  HIPCHK(hipMemsetAsync(h->rowLm.p, 0xFF, Mrows * sizeof(int), h->stream));  // -1: row touches no landmark
+  std::vector<std::vector<std::pair<int, int>>> per_lm(h->L);              // (row, state)
+  for (int fk = 0; fk < kNumMeasKinds; fk++) {
+    MeasSet &s = h->ms[fk];
+    if (!s.haslm) continue;
+    for (int f = 0; f < s.count(); f++) {
+      for (int r = 0; r < s.rows; r++) per_lm[s.lm[f]].push_back({lay.r_ms[fk][f] + r, s.idx[f]});
+      int &lo = touch_lo[s.lm[f]], &hi = touch_hi[s.lm[f]];
+      const int last = s.idx[f] + (s.two ? 1 : 0);
+      lo = (lo < 0) ? s.idx[f] : std::min(lo, (int)s.idx[f]);
+      hi = std::max(hi, last);
     }
-    std::vector<int> lmrow, lmstate, lmptr(h->L + 1, 0);
-    for (int l = 0; l < h->L; l++) {
-      // by left state (stable: equal states keep the order the factors were added in): the segmented path walks a
-      // landmark's rows along the chain, and the dense path's summation order is then independent of the call order
-      std::stable_sort(per_lm[l].begin(), per_lm[l].end(), [](const std::pair<int, int> &x, const std::pair<int, int> &y) { return x.second < y.second; });
-      for (auto &pr : per_lm[l]) { lmrow.push_back(pr.first); lmstate.push_back(pr.second); }
-      lmptr[l + 1] = (int)lmrow.size();
-    }
-    h->nlmrows = (int)lmrow.size();
-    if (segmented) { h->fs.h_lmrow = lmrow; h->fs.h_lmstate = lmstate; h->fs.h_lmptr = lmptr; }
-    if (!segmented) {   // chunks of at most kLmChunk consecutive rows of one landmark
-      std::vector<int> clm, cj0, cj1, cptr(h->L + 1, 0);
-      for (int l = 0; l < h->L; l++) {
-        for (int j = lmptr[l]; j < lmptr[l + 1]; j += kLmChunk) {
-          clm.push_back(l); cj0.push_back(j); cj1.push_back(std::min(j + kLmChunk, lmptr[l + 1]));
-        }
-        cptr[l + 1] = (int)clm.size();
-      }
-      h->nlmchunks = (int)clm.size();
-      if ((rc = upload(h, h->lm_chunk_lm, clm))) return rc;
-      if ((rc = upload(h, h->lm_chunk_j0, cj0))) return rc;
-      if ((rc = upload(h, h->lm_chunk_j1, cj1))) return rc;
-      if ((rc = upload(h, h->lm_chunk_ptr, cptr))) return rc;
-      HIPCHK(h->lm_part.reserve((size_t)std::max(h->nlmchunks, 1) * 2 * h->ld * h->R * sizeof(Real)));
-    }
-    if ((rc = upload(h, h->lmrow, lmrow))) return rc;
-    if ((rc = upload(h, h->lmrow_state, lmstate))) return rc;
-    if ((rc = upload(h, h->lmrow_ptr, lmptr))) return rc;
-    if (!segmented) {
-      HIPCHK(h->lm_t.reserve((size_t)std::max(h->nlmrows, 1) * h->R * sizeof(Real)));
-      HIPCHK(h->lm_S.reserve(((size_t)h->nl * h->R + h->nl) * sizeof(Real)));   // [S (nl x R) | gL (nl)]: one buffer, one all-reduce
-    }
-    HIPCHK(h->lm_dL.reserve((size_t)h->nl * sizeof(Real)));
-    if (!h->lmk.p) return fail(h, GPSLAM_E_INVALID, "set_landmarks() before compile()");
   }
+  std::vector<int> lmrow, lmstate, lmptr(h->L + 1, 0);
+  for (int l = 0; l < h->L; l++) {
+    // by left state (stable: equal states keep the order the factors were added in): the segmented path walks a
+    // landmark's rows along the chain, and the dense path's summation order is then independent of the call order
+    std::stable_sort(per_lm[l].begin(), per_lm[l].end(), [](const std::pair<int, int> &x, const std::pair<int, int> &y) { return x.second < y.second; });
+    for (auto &pr : per_lm[l]) { lmrow.push_back(pr.first); lmstate.push_back(pr.second); }
+    lmptr[l + 1] = (int)lmrow.size();
+  }
+  h->nlmrows = (int)lmrow.size();
+  if (segmented) { h->fs.h_lmrow = lmrow; h->fs.h_lmstate = lmstate; h->fs.h_lmptr = lmptr; }
+  if (!segmented) {   // chunks of at most kLmChunk consecutive rows of one landmark
+    std::vector<int> clm, cj0, cj1, cptr(h->L + 1, 0);
+    for (int l = 0; l < h->L; l++) {
+      for (int j = lmptr[l]; j < lmptr[l + 1]; j += kLmChunk) {
+        clm.push_back(l); cj0.push_back(j); cj1.push_back(std::min(j + kLmChunk, lmptr[l + 1]));
+      }
+      cptr[l + 1] = (int)clm.size();
+    }
+    h->nlmchunks = (int)clm.size();
+    if ((rc = upload(h, h->lm_chunk_lm, clm))) return rc;
+    if ((rc = upload(h, h->lm_chunk_j0, cj0))) return rc;
+    if ((rc = upload(h, h->lm_chunk_j1, cj1))) return rc;
+    if ((rc = upload(h, h->lm_chunk_ptr, cptr))) return rc;
+    HIPCHK(h->lm_part.reserve((size_t)std::max(h->nlmchunks, 1) * 2 * h->ld * h->R * sizeof(Real)));
+  }
+  if ((rc = upload(h, h->lmrow, lmrow))) return rc;
+  if ((rc = upload(h, h->lmrow_state, lmstate))) return rc;
+  if ((rc = upload(h, h->lmrow_ptr, lmptr))) return rc;
+  if (!segmented) {
+    HIPCHK(h->lm_t.reserve((size_t)std::max(h->nlmrows, 1) * h->R * sizeof(Real)));
+    HIPCHK(h->lm_S.reserve(((size_t)h->nl * h->R + h->nl) * sizeof(Real)));   // [S (nl x R) | gL (nl)]: one buffer, one all-reduce
+  }
+  HIPCHK(h->lm_dL.reserve((size_t)h->nl * sizeof(Real)));
+  if (!h->lmk.p) return fail(h, GPSLAM_E_INVALID, "set_landmarks() before compile()");
+  return 0;
+}
+
+// partial sums, gradient copies and the update vector of the optimiser loops
+int size_workspace(gpslam_hip_handle *h, int npart) {
+  const int N = h->N, b = h->b;
   npart = std::max(npart, std::max(nblocks(N, 128), 3 * nblocks(N * b, 256))) + 4200;   // (3 x: launch_dot3's three partial arrays)
   HIPCHK(h->partial.reserve((size_t)npart * sizeof(double)));   // the fp64 error pass of an fp32 handle uses it as well
   HIPCHK(h->partial2.reserve((size_t)(nblocks(N, 128) + 8) * sizeof(double)));
@@ -1328,20 +1346,17 @@ int gpslam_hip_compile(gpslam_hip_handle *h) {
   HIPCHK(h->gsave2.reserve((size_t)(N + 1) * b * sizeof(Real)));   // (LM through the fused kernel: separator parts)
   HIPCHK(hipMemsetAsync(h->gsave2.p, 0, (size_t)(N + 1) * b * sizeof(Real), h->stream));
   HIPCHK(h->dvec.reserve((size_t)N * b * sizeof(Real)));
-  {   // (see fused_kernel_applies) every full-width row but a handful (a velocity prior or two) belongs to a GP prior, one per left
-      // state, one Qc, records not switched off
-    bool one = true;
-    std::vector<char> seen((size_t)N + 1, 0);
-    for (int l : h->gp_left) { if (seen[l]) one = false; seen[l] = 1; }
-    h->pure6 = kIsF64 && b == 6 && (h->mf == POSE2 || h->mf == ROT3 || h->mf == LINEAR3) && one && !h->gp_left.empty() &&
-               h->M - (int)h->gp_left.size() * b <= 4 * b && (gp_ngroups(h) == 0 || h->gp_single_q > 0) && !plan(h, GPSLAM_PLAN_GP_ROWS);
-  }
-  // ---- solver hierarchy: chunks of m0 states at level 0, m1 above.  Unsharded: a single-wave sequential top
-  // level of <= `top` blocks.  Sharded: reduce down to one block per rank (the rank separator).
-  // upper_chunk / top_blocks override the upper-level chunk length and the size of the sequential top level
-  // Level-0 chunk length: `slots` chunks run at once and a launch costs (rounds of slots) x (block steps per chunk);
-  // pick the length that minimises that product (1e5 Pose3 states on 256 CUs: 13 -> 7693 chunks, one round of 12 steps
-  // of the row-layout kernel; the column-layout kernel gets 25 -> 4000 chunks, one round of 24 steps).
+  return 0;
+}
+
+// Solver hierarchy: chunks of m0 states at level 0, m1 above.  Unsharded: a single-wave sequential top
+// level of <= `top` blocks.  Sharded: reduce down to one block per rank (the rank separator).
+// upper_chunk / top_blocks override the upper-level chunk length and the size of the sequential top level
+// Level-0 chunk length: `slots` chunks run at once and a launch costs (rounds of slots) x (block steps per chunk);
+// pick the length that minimises that product (1e5 Pose3 states on 256 CUs: 13 -> 7693 chunks, one round of 12 steps
+// of the row-layout kernel; the column-layout kernel gets 25 -> 4000 chunks, one round of 24 steps).
+int build_hierarchy(gpslam_hip_handle *h, const Plan &p) {
+  const int N = h->N, b = h->b;
   int m0 = 16;
   if (h->cfg.chunk > 1) {
     m0 = h->cfg.chunk;
@@ -1350,16 +1365,15 @@ int gpslam_hip_compile(gpslam_hip_handle *h) {
     const int cus = (hipGetDeviceProperties(&prop, h->cfg.device) == hipSuccess && prop.multiProcessorCount > 0)
                         ? prop.multiProcessorCount : 256;
     // column-layout kernel: one chunk per wave, 4 waves per SIMD; row-layout kernel: four chunks per wave, 2 waves per SIMD
-    const bool rows = rows_kernel_applies(h);
     // (the fused kernel: four two-wave workgroups of four chunks per CU)
-    const long slots = (long)cus * (fused_kernel_applies(h) ? 16 : rows ? 32 : 16);
+    const long slots = (long)cus * (p.fused() ? 16 : p.rows() ? 32 : 16);
     // rounds of resident chunks x block steps per chunk.  Round 3: a chunk of the row-layout kernels costs about three block
     // steps besides its own (the two leading images / the separator's record, the hand-over at the end), which the count of
     // steps alone ignored: at 1e6 states it chose chunks of 8 (31 rounds x 7 steps) where chunks of 32 are 9 % faster
     // (scripts/sweep_chunk.py: 3.86 -> 3.51 ms per iteration; fused level 0 2.11 -> 1.82 ms)
-    const int overhead = rows ? 3 : 0;
+    const int overhead = p.rows() ? 3 : 0;
     long best = -1;
-    for (int m = rows ? 8 : 16; m <= 32; m++) {
+    for (int m = p.rows() ? 8 : 16; m <= 32; m++) {
       const long chunks = (N + m - 1) / m;
       const long cost = ((chunks + slots - 1) / slots) * (m - 1 + overhead);
       if (best < 0 || cost <= best) { best = cost; m0 = m; }   // ties: the longer chunk leaves fewer separators
@@ -1370,19 +1384,18 @@ int gpslam_hip_compile(gpslam_hip_handle *h) {
   for (Level &v : h->lv) { v.blk.release(); v.add.release(); v.x.release(); }
   h->lv.clear();
   const size_t BS = (size_t)2 * b * b + (size_t)b * h->R, AS = (size_t)b * b + (size_t)b * h->R;
-  h->upper_ok = upper_applies(h);
   int n = N;
   for (int l = 0;; l++) {
     Level v;
     v.n = n;
-    v.m = (l == 0) ? m0 : (h->upper_ok ? kUpG : m1);
+    v.m = (l == 0) ? m0 : (p.upper_cr ? kUpG : m1);
     // level 1 of a chain the row-layout level-0 kernels serve (four chunks per wave): groups of four, which
     // k_fused_level0 reduces in its own tail -- when there are enough separators for it to save a launch
     // (not on a sharded handle: the padding of the tail would sit between the last state and the next rank's separator)
-    if (l == 1 && h->upper_ok && rows_kernel_applies(h) && n > kUpG && !sharded(h)) v.m = 4;
+    if (l == 1 && p.upper_cr && p.rows() && n > kUpG && !sharded(h)) v.m = 4;
     v.nch = nblocks(n, v.m);
     h->lv.push_back(v);
-    if (n <= ((l >= 1 && h->upper_ok) ? kUpG : top)) break;
+    if (n <= ((l >= 1 && p.upper_cr) ? kUpG : top)) break;
     n = v.nch;
   }
   for (size_t l = 0; l < h->lv.size(); l++) {
@@ -1408,104 +1421,150 @@ int gpslam_hip_compile(gpslam_hip_handle *h) {
     HIPCHK(hipMemsetAsync(h->iface_recv.p, 0, (size_t)P * (BS + AS) * sizeof(Real), h->stream));
     HIPCHK(hipMemsetAsync(h->top_x.p, 0, (size_t)(P + 1) * b * h->R * sizeof(Real), h->stream));
   }
-  h->fuse_ok = fused_kernel_applies(h);
-  if (h->fuse_ok && !h->simd_cnt.p) {
-    HIPCHK(h->simd_cnt.reserve(8192 * sizeof(int)));
-    HIPCHK(hipMemsetAsync(h->simd_cnt.p, 0, 8192 * sizeof(int), h->stream));
-  }
-  {   // structured GP records for the fused kernel: Pose3 body-velocity chains with at most one GP prior per left state
-    const bool off = plan(h, GPSLAM_PLAN_GP_ROWS);      // plain Jacobian rows for the GP priors as well (the rows path of every chain)
-    std::vector<int> gpidx(N + 2, -1);
-    bool one = true;
-    for (size_t f = 0; f < h->gp_left.size(); f++) {
-      if (gpidx[h->gp_left[f]] >= 0) one = false;
-      gpidx[h->gp_left[f]] = (int)f;
-    }
-    // Other full-width rows: a handful (a velocity prior or two) are fetched where they are used (k_fused_level0<2>, no ring);
-    // more than that -- interpolated measurement factors, a dozen rows per state -- get a ring next to the records (<3>, round 4)
-    h->odd_many = h->M - (int)h->gp_left.size() * b > 4 * b;
-    h->struct_ok = kIsF64 && h->fuse_ok && h->mf == POSE3 && !h->vw && one && !h->gp_left.empty() && !off && h->gp_rows_lead &&
-                   (gp_ngroups(h) == 0 || h->gp_single_q > 0);
-    // block size 6: SE(2), SO(3) and 3-D linear chains with at most one GP prior per left state (any other factors)
-    h->struct3_ok = kIsF64 && (h->mf == POSE2 || h->mf == ROT3 || h->mf == LINEAR3) && one && !h->gp_left.empty() && !off && h->gp_rows_lead &&
-                    (gp_ngroups(h) == 0 || h->gp_single_q > 0);
-    if (!h->struct_ok && !h->struct3_ok) std::fill(gpidx.begin(), gpidx.end(), -1);
-    if ((rc = upload(h, h->gpidx, gpidx))) return rc;
-    if (h->struct3_ok) {
-      HIPCHK(h->gps.reserve((h->gp_left.size() + 1) * (size_t)kGp3Len * sizeof(Real)));
-      HIPCHK(hipMemsetAsync(static_cast<char *>(h->gps.p) + h->gp_left.size() * (size_t)kGp3Len * sizeof(Real), 0, kGp3Len * sizeof(Real), h->stream));
-      std::vector<Real> Uh(36);
-      const double *Usrc = h->gp_single_q > 0 ? &h->gp_Utab[(size_t)(h->gp_single_q - 1) * 36] : h->U;
-      for (int q = 0; q < 36; q++) Uh[q] = (Real)Usrc[q];     // (row-major d x d in the first d * d entries)
-      if ((rc = upload(h, h->dU, Uh))) return rc;
-      h->dU_version = h->U_version;
-    }
-    {   // BetweenFactor<Pose3> records ride with the structured GP records: at most one between factor per left state
-      std::vector<int> btwidx(N + 2, -1);
-      bool one_b = true;
-      for (size_t f = 0; f < h->btw.idx.size(); f++) {
-        if (btwidx[h->btw.idx[f]] >= 0) one_b = false;
-        btwidx[h->btw.idx[f]] = (int)f;
-      }
-      // (chains with other full-width rows besides the GP priors' run k_fused_level0<2>, which keeps compact rows)
-      h->btw_rec_ok = h->struct_ok && one_b && h->btw_rows_trail && h->btw.count() > 0 && h->M == (int)h->gp_left.size() * b;
-      if (!h->btw_rec_ok) std::fill(btwidx.begin(), btwidx.end(), -1);
-      if ((rc = upload(h, h->btwidx, btwidx))) return rc;
-      if (h->btw_rec_ok) {
-        HIPCHK(h->brec.reserve(((size_t)h->btw.count() + 1) * kBtwLen * sizeof(Real)));
-        HIPCHK(hipMemsetAsync(static_cast<char *>(h->brec.p) + (size_t)h->btw.count() * kBtwLen * sizeof(Real), 0, kBtwLen * sizeof(Real), h->stream));
-      }
-    }
-    if (h->struct_ok) {
-      // (one record more than there are factors, all zeros: what the assembly wave reads for a state without a GP prior)
-      HIPCHK(h->gps.reserve((h->gp_left.size() + 1) * (size_t)kGpsLen * sizeof(Real)));
-      HIPCHK(hipMemsetAsync(static_cast<char *>(h->gps.p) + h->gp_left.size() * (size_t)kGpsLen * sizeof(Real), 0, kGpsLen * sizeof(Real), h->stream));
-      std::vector<Real> Uh(36);
-      const double *Usrc = h->gp_single_q > 0 ? &h->gp_Utab[(size_t)(h->gp_single_q - 1) * 36] : h->U;
-      for (int q = 0; q < 36; q++) Uh[q] = (Real)Usrc[q];     // (zero below the diagonal: U is upper triangular)
-      if ((rc = upload(h, h->dU, Uh))) return rc;
-      h->dU_version = h->U_version;
-    }
-  }
+  return 0;
+}
+
+// The plan (api_common.hpp: Plan) of the graph being compiled: every "does this form apply" is decided here, once.  Kernel selection
+// is per handle and visible -- gpslam_hip_config_v2.plan (v1: reserved[6]) is a mask of GPSLAM_PLAN_* bits (the process-environment
+// switches of rounds 2 / 3 are gone).  The fallback families a bit selects are the ones chains with landmark columns, pinned
+// hierarchy shapes or wide borders need anyway; the bits keep them tested on plain chains.
+// The chunk length follows from the level-0 family and the folds from the shape of the hierarchy, so the hierarchy is built here,
+// between the two.
+int make_plan(gpslam_hip_handle *h, const RowLayout &lay) {
+  const int N = h->N, b = h->b;
+  const int ngp = (int)h->gp_left.size();
+  const int other = h->M - ngp * b;       // full-width rows besides the GP priors'
+  Plan p;
+  p.gp_rows_lead = lay.gp_rows_lead;
+  p.btw_rows_trail = lay.btw_rows_trail;
+  // a handful (a velocity prior or two) are fetched where they are used (k_fused_level0<2>, no ring); more than that -- interpolated
+  // measurement factors, a dozen rows per state -- get a ring next to the records (<3>, round 4)
+  p.odd_rows = other == 0 ? 0 : (other > 4 * b ? 2 : 1);
+  // GP priors as records: fp64, at most one per left state, one Qc (the handle's, or the same one on every prior), their rows
+  // leading the state's range; GPSLAM_PLAN_GP_ROWS keeps plain Jacobian rows (the rows path of every chain)
+  const bool rec_ok = kIsF64 && lay.one_gp && ngp > 0 && p.gp_rows_lead && (gp_ngroups(h) == 0 || h->gp_single_q > 0) && !plan_bit(h, GPSLAM_PLAN_GP_ROWS);
+  const bool d3 = h->mf == POSE2 || h->mf == ROT3 || h->mf == LINEAR3;   // block size 6
+  p.pure6 = rec_ok && d3 && other <= 4 * b;
+  // k_chunk_forward_rows covers every block size with a single right-hand side (round 3: 6 and 4 as well;
+  // GPSLAM_PLAN_COLUMN_LEVEL0 keeps the column-layout kernel)
+  const bool rows = !plan_bit(h, GPSLAM_PLAN_COLUMN_LEVEL0) && (b == 12 || b == 6 || b == 4) && h->R == 1;
+  // k_fused_level0 (assembly inside the level-0 elimination): chains of block size 12 or 6 (round 3: SE(2), SO(3), 3-D linear)
+  // without landmark columns (GPSLAM_PLAN_UNFUSED_LEVEL0 keeps k_assemble_ghost + k_chunk_forward_rows); on a sharded handle
+  // the rows of the last local state carry their R^T R to the next rank inside the addend the last chunk sends upward,
+  // which is what k_assemble_ghost's halo addend used to hold.
+  // Block size 6: a block step is a fifth of the SE(3) step's arithmetic but keeps its LDS hand-overs and row-ring round trips, so
+  // the fused kernel is latency bound -- it wins while the launch it saves and the chip's ramp matter (1e5 states: C2 0.209 ->
+  // 0.177 ms, C5 SO(3) 0.330 -> 0.296) and loses to the two streaming kernels at scale (1e6: C2 1.35 -> 1.57 ms).  Hence the
+  // size rule.
+  // Round 4: a block-size-6 chain whose full-width rows are (all but a handful) GP priors that travel as d = 3 records (pure6) has
+  // next to nothing left to fetch per block step -- fused at every size (1e6 states: C2 0.99 -> 0.94 ms, 3e5: 0.334 -> 0.321);
+  // with measurement rows in the ring the rule stands (C5 SO(3) + attitude at 1e6: 1.74 unfused, 1.86 fused).
+  const bool b6 = b == 6 && (N <= 131072 || p.pure6);
+  const bool fused = (b == 12 || b6) && rows && h->nl == 0 && !plan_bit(h, GPSLAM_PLAN_UNFUSED_LEVEL0);   // (fp32 rows are widened as the assembly wave reads them)
+  p.level0 = fused ? Level0::Fused : (rows ? Level0::Rows : Level0::Column);
+  // The levels above level 0 as LDS-resident cyclic reduction, 32 blocks per workgroup and launch (upper.hip): chains
+  // without landmark columns (sharded or not), unless the caller pinned the old hierarchy's shape (upper_chunk / top_blocks).
+  // GPSLAM_PLAN_LEVELS_OF_FOUR keeps one launch per level of chunks of four.
+  p.upper_cr = !plan_bit(h, GPSLAM_PLAN_LEVELS_OF_FOUR) && h->R == 1 && h->cfg.upper_chunk <= 1 && h->cfg.top_blocks <= 0;
+  int rc;
+  if ((rc = build_hierarchy(h, p))) return rc;
+  // level 1 as groups of four (build_hierarchy): the fused kernel's tail reduces them, and where the groups are exactly the waves
+  // of the row-layout back-substitution (launch_backward) that kernel solves them
+  p.tail_fold = p.upper_cr && h->lv.size() >= 3 && h->lv[1].m == 4;
+  p.fold_tail_bwd = kIsF64 && p.tail_fold && !sharded(h) && h->R == 1 && rows && h->lv[1].n == h->lv[0].nch;
+  // SE(3): body-velocity chains under the fused kernel; block size 6: SE(2), SO(3) and 3-D linear chains (any other factors)
+  if (rec_ok && fused && h->mf == POSE3 && !h->vw) p.gp_rec = GpForm::Se3Rec;
+  else if (rec_ok && d3) p.gp_rec = GpForm::D3Rec;
+  const bool se3 = p.gp_rec == GpForm::Se3Rec;
+  // (chains with other full-width rows besides the GP priors' run k_fused_level0<2>, which keeps compact rows)
+  p.btw_rec = se3 && lay.one_btw && p.btw_rows_trail && h->btw.count() > 0 && other == 0;
   {   // the retraction folded into the next K1 inside run_gn (PendUpd): record chains (SE(3), and the d = 3 manifolds: config 2) on
       // one unsharded handle whose every state but the last is the left state of exactly one GP prior (the owner that writes it
       // back), one k_lin launch (a single Qc)
-    bool ok = (h->struct_ok || h->struct3_ok) && h->lv.size() >= 2 && !sharded(h) && h->nl == 0 && h->nclo == 0 && !h->fs.active && gp_ngroups(h) <= 1 &&
-              (int)h->gp_left.size() == N - 1 && N >= 2;      // (lv.size() >= 2: the fused level 0, whose K1 writes the records, runs)
+    bool ok = p.gp_rec != GpForm::Rows && h->lv.size() >= 2 && !sharded(h) && h->nl == 0 && h->nclo == 0 && gp_ngroups(h) <= 1 &&
+              ngp == N - 1 && N >= 2;      // (lv.size() >= 2: the fused level 0, whose K1 writes the records, runs)
     // measurement factors: on SE(3) record chains k_meas runs BEHIND k_lin on the same stream (it reads the interval's record) and
     // so behind the buffer swap -- it sees the updated states; the d = 3 chains run it beside k_lin on a second stream
     // -- those kinds that read two states (the interpolated ones) apply the pending update themselves from the old buffer
-    for (int fk = 0; fk < kNumMeasKinds && ok; fk++) ok = h->ms[fk].count() == 0 || h->struct_ok || (h->struct3_ok && h->ms[fk].two);
-    std::vector<char> seen(N, 0);
-    for (size_t f = 0; f < h->gp_left.size() && ok; f++) { ok = h->gp_left[f] < N - 1 && !seen[h->gp_left[f]]; seen[h->gp_left[f]] = 1; }
-    h->pend_ok = ok && !plan(h, GPSLAM_PLAN_SEPARATE_RETRACT);
-    h->pend_upd = false;
-    if (h->pend_ok && kIsF64) {   // the second state buffer: here, not inside the first run's second iteration (a hipMalloc in a timed region)
-      HIPCHK(h->pose_bak.reserve((size_t)h->pd * h->stride * sizeof(double)));
-      HIPCHK(h->vel_bak.reserve((size_t)h->d * h->stride * sizeof(double)));
-    }
+    for (int fk = 0; fk < kNumMeasKinds && ok; fk++) ok = h->ms[fk].count() == 0 || se3 || h->ms[fk].two;
+    for (int f = 0; f < ngp && ok; f++) ok = h->gp_left[f] < N - 1;     // (one per left state: rec_ok)
+    p.fold_retract = ok && !plan_bit(h, GPSLAM_PLAN_SEPARATE_RETRACT);
   }
-  {   // interpolated measurement rows as 16-double lines next to the records (k_fused_level0<4>, kernels.hpp kIRow*): the chain runs
-      // the structured path and every full-width row that is not a GP prior's belongs to an interpolated GPS factor on an interval
-      // with a GP prior (whose record holds X, J and F of that interval); no landmarks (fuse_ok), no velocity priors
-    bool ok = h->struct_ok && !plan(h, GPSLAM_PLAN_MEAS_ROWS) && h->vpri.count() == 0 && h->ms[FK_INTERP_GPS].count() > 0;
-    for (int fk = 0; fk < kNumMeasKinds && ok; fk++) ok = (fk == FK_INTERP_GPS) || h->ms[fk].count() == 0;
-    std::vector<char> has_gp(N + 1, 0);
-    for (int32_t l : h->gp_left) has_gp[l] = 1;
+  {   // interpolated measurement rows as 16-double lines next to the records (k_fused_level0<4>, kernels.hpp kIRow*): every
+      // full-width row that is not a GP prior's belongs to an interpolated GPS factor on an interval with a GP prior (whose
+      // record holds X, J and F of that interval); no landmarks (fused), no velocity priors
     const MeasSet &g = h->ms[FK_INTERP_GPS];
-    for (size_t f = 0; f < g.idx.size() && ok; f++) ok = has_gp[g.idx[f]] != 0;
-    h->irow_ok = ok;
-    if (ok) {
-      std::vector<int> irowptr(N + 2, 0), irow0(g.idx.size());
-      for (int s = 0; s <= N; s++) irowptr[s + 1] = irowptr[s] + (rowptr[s + 1] - rowptr[s]) - (has_gp[s] ? b : 0);
-      // (the GP prior's rows lead a state's range of the full-width table -- gp_rows_lead, part of struct_ok -- so a measurement
-      //  row keeps its place among the state's other rows)
-      for (size_t f = 0; f < g.idx.size(); f++) irow0[f] = irowptr[g.idx[f]] + (r_ms[FK_INTERP_GPS][f] - rowptr[g.idx[f]] - b);
-      if ((rc = upload(h, h->irowptr, irowptr))) return rc;
-      if ((rc = upload(h, h->ms[FK_INTERP_GPS].d_irow0, irow0))) return rc;
-      HIPCHK(h->rowI.reserve(((size_t)irowptr[N + 1] + 1) * kIRowLen * sizeof(Real)));
-    }
+    bool ok = se3 && !plan_bit(h, GPSLAM_PLAN_MEAS_ROWS) && h->vpri.count() == 0 && g.count() > 0;
+    for (int fk = 0; fk < kNumMeasKinds && ok; fk++) ok = (fk == FK_INTERP_GPS) || h->ms[fk].count() == 0;
+    for (size_t f = 0; f < g.idx.size() && ok; f++) ok = lay.gpidx[g.idx[f]] >= 0;
+    p.lines = ok;
   }
+  h->plan = p;
+  return 0;
+}
+
+// one record more than there are factors, all zeros (what the assembly wave reads for a state without a GP prior), and the U
+// the records are whitened with
+int alloc_gp_records(gpslam_hip_handle *h, int len) {
+  const size_t F = h->gp_left.size();
+  HIPCHK(h->gps.reserve((F + 1) * (size_t)len * sizeof(Real)));
+  HIPCHK(hipMemsetAsync(static_cast<char *>(h->gps.p) + F * (size_t)len * sizeof(Real), 0, len * sizeof(Real), h->stream));
+  h->dU_version = -1;
+  return refresh_dU(h);
+}
+// the buffers and index tables of the forms the plan asks for
+int alloc_records(gpslam_hip_handle *h, const RowLayout &lay) {
+  const Plan &p = h->plan;
+  const int N = h->N, b = h->b;
+  int rc;
+  if (p.fused() && !h->simd_cnt.p) {
+    HIPCHK(h->simd_cnt.reserve(8192 * sizeof(int)));
+    HIPCHK(hipMemsetAsync(h->simd_cnt.p, 0, 8192 * sizeof(int), h->stream));
+  }
+  const std::vector<int> none(N + 2, -1);
+  if ((rc = upload(h, h->gpidx, p.gp_rec != GpForm::Rows ? lay.gpidx : none))) return rc;
+  if (p.gp_rec == GpForm::D3Rec && (rc = alloc_gp_records(h, kGp3Len))) return rc;
+  if ((rc = upload(h, h->btwidx, p.btw_rec ? lay.btwidx : none))) return rc;
+  if (p.btw_rec) {
+    HIPCHK(h->brec.reserve(((size_t)h->btw.count() + 1) * kBtwLen * sizeof(Real)));
+    HIPCHK(hipMemsetAsync(static_cast<char *>(h->brec.p) + (size_t)h->btw.count() * kBtwLen * sizeof(Real), 0, kBtwLen * sizeof(Real), h->stream));
+  }
+  if (p.gp_rec == GpForm::Se3Rec && (rc = alloc_gp_records(h, kGpsLen))) return rc;
+  h->pend_upd = false;
+  if (p.fold_retract) {   // the second state buffer: here, not inside the first run's second iteration (a hipMalloc in a timed region)
+    HIPCHK(h->pose_bak.reserve((size_t)h->pd * h->stride * sizeof(double)));
+    HIPCHK(h->vel_bak.reserve((size_t)h->d * h->stride * sizeof(double)));
+  }
+  if (p.lines) {
+    const MeasSet &g = h->ms[FK_INTERP_GPS];
+    std::vector<int> irowptr(N + 2, 0), irow0(g.idx.size());
+    for (int s = 0; s <= N; s++) irowptr[s + 1] = irowptr[s] + (lay.rowptr[s + 1] - lay.rowptr[s]) - (lay.gpidx[s] >= 0 ? b : 0);
+    // (the GP prior's rows lead a state's range of the full-width table -- gp_rows_lead, part of the record forms -- so a
+    //  measurement row keeps its place among the state's other rows)
+    for (size_t f = 0; f < g.idx.size(); f++) irow0[f] = irowptr[g.idx[f]] + (lay.r_ms[FK_INTERP_GPS][f] - lay.rowptr[g.idx[f]] - b);
+    if ((rc = upload(h, h->irowptr, irowptr))) return rc;
+    if ((rc = upload(h, h->ms[FK_INTERP_GPS].d_irow0, irow0))) return rc;
+    HIPCHK(h->rowI.reserve(((size_t)irowptr[N + 1] + 1) * kIRowLen * sizeof(Real)));
+  }
+  return 0;
+}
+
+int gpslam_hip_compile(gpslam_hip_handle *h) {
+  if (!h || h->N <= 0) return GPSLAM_E_INVALID;
+  (void)hipSetDevice(h->cfg.device);
+  int rc, npart = 0;
+  bool segmented = false;
+  RowLayout lay;
+  std::vector<int> touch_lo, touch_hi;
+  if ((rc = check_stored_indices(h))) return rc;
+  if ((rc = choose_landmark_path(h, segmented))) return rc;
+  layout_rows(h, lay);
+  group_gp_by_qc(h);
+  if ((rc = upload_factors(h, lay, npart))) return rc;
+  if ((rc = build_landmark_border(h, lay, segmented, touch_lo, touch_hi))) return rc;
+  if ((rc = size_workspace(h, npart))) return rc;
+  if ((rc = make_plan(h, lay))) return rc;          // (builds the solver hierarchy on its way)
+  if ((rc = alloc_records(h, lay))) return rc;
   if (segmented && (rc = fs_build(h, touch_lo, touch_hi))) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   h->compiled = true;
@@ -1696,7 +1755,8 @@ int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, do
   if (rc) return rc;
   if (reps <= 0 || !avg_ms || which < 0 || which > 4 || sharded(h)) return GPSLAM_E_INVALID;
   double total = 0.0;
-  // (K1 and the fused elimination are timed in the form an iteration runs them: structured GP records where they apply)
+  // (every kernel is timed in the form an iteration runs it -- the launch helpers build the arguments; the SE(3) records belong to
+  //  K1 and the fused elimination alone)
   LaunchMode m = level0_mode(h);
   m.se3_rec = m.se3_rec && (which == 0 || which == 2);
   for (int r = 0; r < reps; r++) {
@@ -1715,41 +1775,18 @@ int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, do
       if (m.fused) { *avg_ms = 0.0; return 0; }   // no such launch: see the header
       if ((rc = launch_assemble(h, m, false))) return rc;
     } else if (which == 2 || which == 3) {
-      Level &v = h->lv[0];
-      const bool top = (h->lv.size() == 1);
-      FwdArgs<Real> a;
-      a.blk = v.blk.as<Real>(); a.add = nullptr;
-      a.up_blk = top ? nullptr : h->lv[1].blk.as<Real>();
-      a.up_add = top ? nullptr : h->lv[1].add.as<Real>();
-      a.n = v.n; a.m = top ? v.n : v.m; a.R = h->R; a.no_sep = top ? 1 : 0; a.last_has_right = 0;
-      a.remote_add = nullptr; a.lambda = Real(0); a.flag = h->flag.as<int>();
-      a.l1_blk = nullptr; a.tail = 0;
-      const int grid = top ? 1 : v.nch;
-      if (tail_now(h, m)) {    // timed in the form an iteration runs it
-        a.tail = 1; a.l1_blk = h->lv[1].blk.as<Real>();
-        a.up_blk = h->lv[2].blk.as<Real>(); a.up_add = h->lv[2].add.as<Real>();
-      }
-      launch_fwd(h, m, a, grid);
+      int grid;
+      const FwdArgs<Real> a = fwd_args(h, m, 0, 0.0, grid);
+      if ((rc = launch_fwd(h, m, a, grid))) return rc;
       if (which == 3) {  // time the level-0 back-substitution instead (separator solutions = whatever lv[1].x holds)
         HIPCHK(hipEventRecord(h->ev[0], h->stream));
-        BwdArgs<Real> bw;
-        bw.blk = v.blk.as<Real>(); bw.x = v.x.as<Real>(); bw.xup = top ? nullptr : h->lv[1].x.as<Real>();
-        bw.n = v.n; bw.m = top ? v.n : v.m; bw.R = h->R; bw.no_sep = top ? 1 : 0; bw.last_has_right = 0;
-        if (!top && fold_tail_bwd(h)) {   // (timed in the form an iteration runs it)
-          bw.l1_blk = h->lv[1].blk.as<Real>(); bw.l1_xup = h->lv[2].x.as<Real>(); bw.l1_n = h->lv[1].n;
-        }
+        const BwdArgs<Real> bw = bwd_args(h, 0, nullptr, grid);
         launch_bwd(h, bw, grid);
       }
     } else {
       HIPCHK(hipMemsetAsync(h->lv[0].x.p, 0, (size_t)h->N * h->b * h->R * sizeof(Real), h->stream));
       HIPCHK(hipEventRecord(h->ev[0], h->stream));
-      RetractArgs<Real> a;
-      a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride; a.N = h->N; a.R = h->R;
-      a.chart = h->cfg.chart; a.first = 0; a.x = h->lv[0].x.as<Real>(); a.partial = h->partial.as<Real>(); a.flag = h->flag.as<int>();
-      dispatch_mf(h->mf, [&](auto tag) {
-        constexpr int MF = decltype(tag)::value;
-        k_retract<Real, MF><<<dim3(nblocks(h->N, 128)), dim3(128), 0, h->stream>>>(a);
-      });
+      launch_retract_k(h);
     }
     HIPCHK(hipEventRecord(h->ev[1], h->stream));
     HIPCHK(hipEventSynchronize(h->ev[1]));

@@ -152,7 +152,7 @@ int sharded_phase2a(gpslam_hip_handle *h) {
     a.blk = h->top_blk.as<Real>(); a.add = nullptr; a.up_blk = nullptr; a.up_add = nullptr;
     a.n = P; a.m = P; a.R = R; a.no_sep = 1; a.last_has_right = 0; a.remote_add = nullptr; a.lambda = Real(0);
     a.flag = h->flag.as<int>(); a.l1_blk = nullptr; a.tail = 0;
-    launch_fwd(h, LaunchMode{}, a, 1);
+    if ((rc = launch_fwd(h, LaunchMode{}, a, 1))) return rc;
     BwdArgs<Real> bw;
     bw.blk = h->top_blk.as<Real>(); bw.x = h->top_x.as<Real>(); bw.xup = nullptr;
     bw.n = P; bw.m = P; bw.R = R; bw.no_sep = 1; bw.last_has_right = 0;
@@ -368,7 +368,7 @@ int gpslam_hip_run_gn(gpslam_hip_handle *h, int32_t iters, gpslam_hip_stats *st,
     // (round 5) every iteration but the last leaves its retraction to the next iteration's K1 (PendUpd); |delta|_inf and the error
     // are reported for the last iteration, as before
     const LaunchMode m = gn_mode(h, timed, last);
-    if ((rc = enqueue_gn(h, m, 0.0, timed, last, h->pend_ok && !last))) return bail(rc);
+    if ((rc = enqueue_gn(h, m, 0.0, timed, last, h->plan.fold_retract && !last))) return bail(rc);
     if (timed) {
       if (hipEventSynchronize(h->ev[4]) != hipSuccess) { h->err = "hipEventSynchronize failed inside run_gn"; return bail(GPSLAM_E_HIP); }
       if ((rc = collect_timing(h, m, acc))) return bail(rc);

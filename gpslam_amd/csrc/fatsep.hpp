@@ -655,10 +655,7 @@ constexpr int fs_tri_row(int p) { int t = 0; while ((t + 1) * (t + 2) / 2 <= p) 
 // kFsSweepTiles tiles cost on the matrix cores (measured: ~2700 cycles against 6 x 64 per tile -- on MI355X the fp64 MFMA and
 // the fp64 vector multiply-adds of one SIMD do not overlap, the matrix peak equals the vector peak), so the tiles are dealt
 // greedily to the least loaded wave with that head start: every wave, hence every SIMD, carries the same work.
-#ifndef GPS_FS_SWEEP_TILES
-#define GPS_FS_SWEEP_TILES 7
-#endif
-constexpr int kFsSweepTiles = GPS_FS_SWEEP_TILES;
+constexpr int kFsSweepTiles = 7;
 // (round 4: a border of at most 64 columns -- T16 <= 4, what the segment-length search now finds for config 4 -- is ONE sweep
 //  wave's worth of columns: wave 1 then only multiplies, instead of walking the sweep's instruction stream with no column to own)
 constexpr int fs_sweep_waves(int T16) { return T16 > 4 ? 2 : 1; }
@@ -749,9 +746,6 @@ __device__ __forceinline__ void fs_mfma_role(const double *ring, int nchunks, in
   tl.store(out, NCP, lane);
 }
 
-#ifndef GPS_FS_PRIO
-#define GPS_FS_PRIO 3
-#endif
 // the sweep wave SWV (0 / 1: border columns 64 SWV ..) of k_fs_sweep_syrk, including the few tiles fs_tile_owner deals to it
 template <int B, int T16, int SWV, typename TR>
 __device__ __forceinline__ void fs_sweep_role(const FsArgs<double, TR> &a, double *ring, double *FsAll, int seg, int lane, int cutL, int j0, int n,
@@ -831,9 +825,7 @@ __device__ __forceinline__ void fs_sweep_role(const FsArgs<double, TR> &a, doubl
   }
 #pragma unroll 1
   for (int i = 0; i <= nchunks; i++) {
-#if GPS_FS_PRIO
-    __builtin_amdgcn_s_setprio(GPS_FS_PRIO);   // the sweep is what the workgroup's other waves wait for at the chunk barrier
-#endif
+    __builtin_amdgcn_s_setprio(3);   // the sweep is what the workgroup's other waves wait for at the chunk barrier
     if (i < nchunks) {
       double *slot = ring + (i & 1) * KC * LSP;
       // ---- the chunk's right-hand sides: zero the column, then the staged values and the entries
@@ -923,9 +915,7 @@ __device__ __forceinline__ void fs_sweep_role(const FsArgs<double, TR> &a, doubl
         }
       }
     }
-#if GPS_FS_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     if (i >= 1) tl.chunk(ring + ((i - 1) & 1) * KC * LSP, lane);
     lds_barrier();
   }

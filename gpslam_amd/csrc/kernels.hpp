@@ -234,9 +234,7 @@ template <typename T> struct GpArgs {
 //   [64..75] whitened error,  [76] k2 = -(sa dt + sb), [77] sb, [78] sc, [79] sa
 // K1 stages 16 doubles per lane and wave and writes whole 128-byte lines (wave_store_part): the order above is the order in
 // which it produces the blocks.  Record F (one past the last factor) is all zeros: states without a GP prior read it.
-#ifndef GPS_KLIN_WAVES
-#define GPS_KLIN_WAVES 2   /* two K1 waves per SIMD (<= 256 VGPRs): linearise phase 87.8 vs 93.3 us with structured records */
-#endif
+constexpr int kLinWaves = 2;   // two K1 waves per SIMD (<= 256 VGPRs): linearise phase 87.8 vs 93.3 us with structured records
 // The same idea for the d = 3 manifolds (SE(2), SO(3), 3-D linear: block size 6; round 4).  There H1 = [J1; 0], H3 = [J3; 0] and
 // H2 = [h2t I; h2b I], H4 = [0; h4b I] with constants (GaussianProcessPriorPose2.h:76-79, GaussianProcessPriorRot3.h:73-76,
 // GaussianProcessPriorLinear.h:72-81), so of the whitened 6 x 12 Jacobian only two 3 x 3 blocks are data:
@@ -952,7 +950,7 @@ template <typename T> struct LinArgs {
 // prior writes its rows in halves, pose priors / between factors have compact rows): 14 KB of LDS instead of 27 KB, so that
 // every workgroup of a 1e5-state launch is resident at once.
 template <typename T, int MF, bool VW, bool VP, bool REC = false>
-__global__ void __launch_bounds__(128, GPS_KLIN_WAVES) k_lin(LinArgs<T> a) {
+__global__ void __launch_bounds__(128, kLinWaves) k_lin(LinArgs<T> a) {
   constexpr int LS = (MF == POSE3 && !VP) ? 20 : (4 * MTraits<MF>::d + 2 > 20 || !REC ? 4 * MTraits<MF>::d + 2 : 20);
   __shared__ T stage[2 * 64 * LS];
   __shared__ int srow[128];
@@ -1007,7 +1005,7 @@ template <typename T> struct MeasArgs {
   // interval from there instead of forming them again for every measurement factor on it.  Null: it forms them.
   const T *gps = nullptr;
   const int *gpidx = nullptr;
-  T *rowI = nullptr;   // k_meas<..., IROW = true>: the table of 16-double interpolated rows (kIRow*); row0 then counts rows of THAT table
+  T *rowI = nullptr;   // k_gps_lines: the table of 16-double interpolated rows (kIRow*); row0 then counts rows of THAT table
   const int *row0;
   T *rowLR, *rowE, *rowM;
   int *rowLm;
@@ -1028,25 +1026,18 @@ template <typename T> __device__ __forceinline__ void put_v6(V6<T> a, T *row) { 
 // GPInterpolatedRangeFactorPose2/Pose3/2DLinear, RangeFactorPose2 / RangeFactor2DLinear,
 // GPInterpolatedAttitudeFactorRot3, GPInterpolatedGPSFactorPose3, OdometryFactor2DLinear, RangeBearingFactor2DLinear
 // (gpslam/slam/*.h, see the per-branch citations).  One thread per factor.
-// IROW (round 5; SE(3), fp64, GPInterpolatedGPSFactorPose3): the rows leave as 16-double lines [Lp | mu | e, p11, p12, l12] (kIRow*)
-// for k_fused_level0<4>, which forms the right halves from mu and the interval's GP record
-template <typename T, int MF, int FK, bool JAC, bool IROW = false>
+// (GPInterpolatedGPSFactorPose3 as 16-double lines for k_fused_level0<4>: k_gps_lines below)
+template <typename T, int MF, int FK, bool JAC>
 __global__ void __launch_bounds__(128) k_meas(MeasArgs<T> a) {
-  static_assert(!IROW || (FK == FK_INTERP_GPS && MF == POSE3 && JAC && std::is_same<T, double>::value), "interpolated rows: SE(3) GPS factors, fp64");
   constexpr int d = MTraits<MF>::d, pd = MTraits<MF>::pd, b = 2 * d, rows = FKRows<FK>::rows;
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   T err = T(0);
   if constexpr (MeasValid<MF, FK>::v) {
     // whitened Jacobian rows leave through the per-wave staging buffer (wave_store_rows), like the GP prior's
     T JL[JAC ? rows * b : 1], JR[JAC ? rows * b : 1], wgt[rows];
-    T ew_[IROW ? rows : 1];            // IROW: the whitened errors, staged with the rows
     int row0v = -1;
 #pragma unroll
     for (int r = 0; r < rows; r++) wgt[r] = T(0);
-    if constexpr (IROW) {
-#pragma unroll
-      for (int r = 0; r < rows; r++) ew_[r] = T(0);
-    }
     if (f < a.count) {
       const int i = a.idx[f];
       constexpr bool two = (FK == FK_INTERP_RANGE || FK == FK_INTERP_ATT || FK == FK_INTERP_GPS || FK == FK_ODOM2D || FK == FK_INTERP_PROJ || FK == FK_AHRS);
@@ -1232,24 +1223,11 @@ __global__ void __launch_bounds__(128) k_meas(MeasArgs<T> a) {
       } else if constexpr (FK == FK_INTERP_GPS) {
         // GPInterpolatedGPSFactorPose3::evaluateError, gpslam/slam/GPInterpolatedGPSFactorPose3.h:66-95
         Interp6Out<T, JAC> o;
-        BL6<T> He, Hc21, s1;
-        SE3<T> pose;
-        if constexpr (IROW) pose = interp_pose3_parts<T>(p1, v1, p2, v2, kc, gprec, He, Hc21, s1);
-        else pose = interp_pose3<T, JAC>(p1, v1, p2, v2, kc, o, gprec);
+        const SE3<T> pose = interp_pose3<T, JAC>(p1, v1, p2, v2, kc, o, gprec);
         const SE3<T> S = as_se3(sens);
         const SE3<T> sp = has_sensor ? se3_compose(pose, S) : pose;
         e[0] = sp.t.x - ms[0]; e[1] = sp.t.y - ms[1]; e[2] = sp.t.z - ms[2];
-        if constexpr (IROW) {
-          // JL row r = [Lp | mu] (the left half of the Jacobian is [Lp | l12 mu]); JR stays zero: the consumer forms it
-          const BL6<T> AdS = se3_adjoint(se3_inverse(S));
-#pragma unroll
-          for (int r = 0; r < 3; r++) {
-            V6<T> Hp = {{T(0), T(0), T(0)}, {sp.R.m[3 * r], sp.R.m[3 * r + 1], sp.R.m[3 * r + 2]}};   // translation(H) = [0, R]
-            if (has_sensor) Hp = rowmul(Hp, AdS);
-            const V6<T> mu = rowmul(Hp, He);
-            put_v6(rowmul(Hp, Hc21) + rowmul(mu, s1), JL + r * b); put_v6(mu, JL + r * b + 6);
-          }
-        } else if (JAC) {
+        if (JAC) {
           const BL6<T> AdS = se3_adjoint(se3_inverse(S));
 #pragma unroll
           for (int r = 0; r < 3; r++) {
@@ -1393,7 +1371,6 @@ __global__ void __launch_bounds__(128) k_meas(MeasArgs<T> a) {
         const T we = e[r] * w;
         err += we * we;
         wgt[r] = w;
-        if constexpr (IROW) ew_[r] = we;
         if (!JAC && a.rowE32) a.rowE32[row0 + r] = (float)we;
         if (JAC && a.rowLR) {      // (rowLR == null: the inspection call, gpslam_hip_linearize_meas, leaves the row tables alone)
           a.rowE[row0 + r] = we;
@@ -1404,22 +1381,7 @@ __global__ void __launch_bounds__(128) k_meas(MeasArgs<T> a) {
         }
       }
     }
-    if constexpr (IROW) {
-      __shared__ T istage[2 * 64 * 20];
-      __shared__ int isrow[128];
-      const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-      T *st = istage + wv * 64 * 20, *mine = st + lane * 20;
-      isrow[threadIdx.x] = row0v;
-      const bool live = f < a.count;
-      const T p11 = live ? T(a.coef[4 * (size_t)f + 2]) : T(0), p12 = live ? T(a.coef[4 * (size_t)f + 3]) : T(0), l12 = live ? T(a.coef[4 * (size_t)f + 1]) : T(0);
-#pragma unroll
-      for (int r = 0; r < rows; r++) {
-#pragma unroll
-        for (int c = 0; c < 12; c++) mine[c] = wgt[r] * JL[r * b + c];
-        mine[kIRowE] = ew_[r]; mine[kIRowP11] = p11; mine[kIRowP12] = p12; mine[kIRowL12] = l12;
-        wave_store_part<T, kIRowLen, 16, 20, true>(st, isrow + wv * 64, lane, r, 0, a.rowI);
-      }
-    } else if constexpr (JAC) {
+    if constexpr (JAC) {
       constexpr int LS = 2 * b + 2;
       __shared__ T stage[2 * 64 * LS];
       __shared__ int srow[128];
@@ -1440,21 +1402,20 @@ __global__ void __launch_bounds__(128) k_meas(MeasArgs<T> a) {
   if (threadIdx.x == 0) a.partial[blockIdx.x] = tot;
 }
 
-// GPInterpolatedGPSFactorPose3 on the structured path, as 16-double lines (kIRow*) -- the kernel k_meas<double, POSE3, FK_INTERP_GPS,
-// true, true> is, written for its register count (round 6).  The general kernel keeps every row of the factor (rows x 24 doubles), the
+// GPInterpolatedGPSFactorPose3 on the structured path, as 16-double lines [Lp | mu | e, p11, p12, l12] (kIRow*) for k_fused_level0<4>,
+// which forms the right halves from mu and the interval's GP record -- written for its register count (round 6).  Round 5's form, a
+// branch of the general kernel k_meas, kept every row of the factor (rows x 24 doubles), the
 // interpolator's three 6 x 6 blocks and the interval's record alive at once: 256 VGPRs + AGPR spill space, ONE wave per SIMD, 0.88 ms
 // for 4e6 factors at 0.37 of the HBM roof -- a latency chain nobody covers.  Here the whitening enters through Hp (the rows are
 // linear in it: diag(1 / sigma) or the square-root information R of a Gaussian model), so a row is final the moment it is formed;
 // the interval's Jinv is dead once xi exists, the record's J and F blocks are requested when the lines are half done, and the pose's
 // 12 numbers are the only thing that lives from the first load to the last row.  Same device functions on the same operands as
-// interp_pose3_parts (GaussianProcessInterpolatorPose3.h:57-105, GPInterpolatedGPSFactorPose3.h:66-95): products with the weight
-// commute by one rounding.  The interval must carry a GP prior (compile(): irow_ok), body-frame velocities (struct_ok).
+// interp_pose3 (GaussianProcessInterpolatorPose3.h:57-105, GPInterpolatedGPSFactorPose3.h:66-95): products with the weight
+// commute by one rounding.  The interval must carry a GP prior (Plan::lines), body-frame velocities (GpForm::Se3Rec).
 // materialise values HERE: an empty volatile asm that "modifies" them keeps the compiler from sinking their computation towards the
 // use (and, on a pointer, from hoisting the loads behind it) -- the phases of k_gps_lines below stay phases
 template <typename P> __device__ __forceinline__ void pin_ptr(P *&p) { asm volatile("" : "+v"(p)); }
-#ifndef GPS_GPS_LINES_WAVES
-#define GPS_GPS_LINES_WAVES 2   /* 0: the general k_meas<..., IROW> kernel (round 5) */
-#endif
+constexpr int kGpsLinesWaves = 2;   // waves per SIMD k_gps_lines is compiled for
 // se3_Q (lie.hpp; Pose3utils.cpp:92-113) term by term: the same products and the same order of every sum, each term folded into
 // the result before the next one's operands exist (the expression as one statement keeps eight 3 x 3 temporaries alive)
 __device__ __forceinline__ M3<double> se3_Q_seq(V3<double> w, V3<double> rho) {
@@ -3016,7 +2977,7 @@ template <typename T, typename TR = T> struct FusedArgs {
   int odd_rows;           // the structured chain has other full-width rows as well: 1 = a few (k_fused_level0<2>), 2 = many (<3>: a ring)
   int u_diag;             // Ud is diagonal (SE(3) records: k_fused_level0<1, double, 12, true>)
   const T *Ud;            // chol_upper(Qc^-1), row-major 6 x 6, in device memory: the structured velocity columns are multiples of its rows
-  int *simd_cnt = nullptr;       // round 6 (GPS_ROLE_SWAP): wave-0 count per SIMD of the chip (8192 ints, zero between launches), or null
+  int *simd_cnt = nullptr;       // round 6 (role swap): wave-0 count per SIMD of the chip (8192 ints, zero between launches), or null
   T *gsave, *gsave2;      // Levenberg-Marquardt: the gradient g = -J^T e per state (gsave) and, for a chunk's separator, the part of
                           // it that the PREVIOUS chunk's last rows contribute (gsave2; zero elsewhere); null: not wanted
 #ifdef GPS_TRACE_FUSED
@@ -3045,60 +3006,39 @@ template <typename T, typename TR = T> struct FusedArgs {
 // (L's velocity block is [k2 U; -sc U]): D and O need 7 instead of 12 multiply-adds per Jacobian row, and U Z is six products per
 // six-vector instead of 21 multiply-adds -- 204 of the assembly wave's ~1170 instructions per block step.  What is skipped are
 // products with exact zeros: the same values as the general kernel.
-#ifndef GPS_FUSED_WAVES
-#define GPS_FUSED_WAVES 2
-#endif
+constexpr int kFusedWaves = 2;   // waves per SIMD k_fused_level0 is compiled for (two workgroups' worth: see "Wave priority" below)
 // Wave priority inside k_fused_level0 (round 6).  The two waves a SIMD holds belong to two different workgroups, and the
 // instruction arbiter serves the OLDER wave first: in a launch of one resident set (1e5 states: 1000 workgroups) the workgroups whose
 // waves were placed first run at the speed of a wave that has its SIMD to itself and end at 115 us, those placed second take what is
-// left and end at 145-154 us -- the launch lasts as long as the slowest (scripts/trace_fused.py, HW_ID wave slots).  GPS_PRIO = 1
-// (the default): every block step a wave sets its priority to 3 - (step mod 4), so the wave that is BEHIND on its SIMD is the one
+// left and end at 145-154 us -- the launch lasts as long as the slowest (scripts/trace_fused.py, HW_ID wave slots).  So
+// every block step a wave sets its priority to 3 - (step mod 4), so the wave that is BEHIND on its SIMD is the one
 // that is served first and the workgroups of a CU advance together: the spread of a CU's workgroups falls from ~30 us to 4 us, the
 // launch from 154 to 142-145 us at the same median (132 us: the work is what it was), 1e6 states unchanged (workgroups come and go
-// there).  Measured and not kept: 2 / 3 (one role always first: no gain), 4 (two-step quantum: half the gain), 5 (half-step
-// quantum: no better than 1).  0: no s_setprio (rounds 1-5).  HISTORY.md "Round 6" has the tables.
-#ifndef GPS_PRIO
-#define GPS_PRIO 1
-#endif
-// c: progress in half steps (2 t at the top of block step t, 2 t + 1 in its middle)
-// Which wave of a workgroup eliminates (round 6, GPS_ROLE_SWAP).  The hardware puts wave 0 of a two-wave workgroup on SIMD a and wave 1
+// there).  Measured and not kept: one role always first (no gain), a two-step quantum (half the gain), a half-step
+// quantum (no better).  Rounds 1-5 set no priority.  HISTORY.md "Round 6" has the tables.
+// Which wave of a workgroup eliminates (round 6).  The hardware puts wave 0 of a two-wave workgroup on SIMD a and wave 1
 // on sigma(a), sigma the 4-cycle 3 -> 0 -> 2 -> 1 -> 3 (HW_ID of 1000 workgroups, scripts/trace_fused.py); a CU's four workgroups then
 // either start on four different SIMDs -- every SIMD holds one wave 0 and one wave 1 -- or two by two on the same pair, and with
 // "wave 0 eliminates" two SIMDs of that CU hold two elimination waves (5.4 us per block step instead of 4.8) and two hold two assembly
-// waves: 27-76 of the chip's 1024 SIMDs per launch, and their workgroups are the launch's last.  With the switch on, wave 0 counts
+// waves: 27-76 of the chip's 1024 SIMDs per launch, and their workgroups are the launch's last.  So wave 0 counts
 // itself into a per-SIMD word (one returning atomic per workgroup, undone on exit): the SECOND wave 0 of a SIMD trades roles with its
 // wave 1, which puts an elimination wave on sigma(a) -- where the first workgroup's assembly wave sits -- and every SIMD of every CU
 // holds one wave of each kind.  (Exact for a launch of one resident set, where it matters: 1e5 states.  Where workgroups come and go the
 // word counts wave 0s, not elimination waves -- a newcomer next to a workgroup that traded sees the count and trades as well -- and
 // the launch's duration does not depend on the placement: 1e6 states 1.27 ms with or without.)
-#ifndef GPS_ROLE_SWAP
-#define GPS_ROLE_SWAP 1
-#endif
 // (block size 12 only: the three-waves-per-SIMD kernel of the d = 3 chains gains nothing at 1e5 states and loses 2 % at 1e6)
-template <int B> __device__ __forceinline__ void fused_step_prio(int c, int role) {
+// c: progress in half steps (2 t at the top of block step t, 2 t + 1 in its middle); the priority changes at whole steps
+template <int B> __device__ __forceinline__ void fused_step_prio(int c) {
   if constexpr (B != 12) return;
-#if GPS_PRIO == 5
-  const int t = c;
-#else
   if (c & 1) return;
-  const int t = c >> 1;
-#endif
-#if GPS_PRIO == 1 || GPS_PRIO == 4 || GPS_PRIO == 5
-  const int q = (GPS_PRIO == 4 ? (t >> 1) : t) & 3;
+  const int q = (c >> 1) & 3;
   if (q == 0) __builtin_amdgcn_s_setprio(3);
   else if (q == 1) __builtin_amdgcn_s_setprio(2);
   else if (q == 2) __builtin_amdgcn_s_setprio(1);
   else __builtin_amdgcn_s_setprio(0);
-#elif GPS_PRIO == 2
-  if (t == 0) { if (role == 0) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0); }
-#elif GPS_PRIO == 3
-  if (t == 0) { if (role == 0) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(3); }
-#else
-  (void)t; (void)role;
-#endif
 }
 template <int SV, typename TR = double, int B = 12, bool DG = false>
-__global__ void __launch_bounds__(128, GPS_FUSED_WAVES) k_fused_level0(FusedArgs<double, TR> u) {
+__global__ void __launch_bounds__(128, kFusedWaves) k_fused_level0(FusedArgs<double, TR> u) {
   static_assert(SV == 0 || std::is_same<TR, double>::value, "structured GP records are fp64");
   static_assert(!DG || ((SV == 1 || SV == 3 || SV == 4) && B == 12), "the diagonal-U form belongs to the SE(3) record variants");
   // SV = 3 (round 4): records AND a ring of full-width rows -- SE(3) chains with interpolated measurement factors (GPS, range,
@@ -3121,7 +3061,6 @@ __global__ void __launch_bounds__(128, GPS_FUSED_WAVES) k_fused_level0(FusedArgs
   //  SIMD gets one wave of each kind changes nothing: 0.303-0.307 ms per iteration at 1e5 states for all four assignments)
   const int lane = threadIdx.x & 63, grp = lane >> 4, r = lane & 15;
   int role = threadIdx.x >> 6;
-#if GPS_ROLE_SWAP
   // (the variants that sit at 256 VGPRs -- a ring of full-width rows next to the records, the general-Qc line form -- keep "wave 0
   //  eliminates": the role bookkeeping costs them 16-20 bytes of scratch, and a scratch reload drains the loads in flight)
   // (block size 6 runs three waves per SIMD, six workgroups per CU: the two-by-two argument above is about two)
@@ -3138,9 +3077,6 @@ __global__ void __launch_bounds__(128, GPS_FUSED_WAVES) k_fused_level0(FusedArgs
     role ^= __builtin_amdgcn_readfirstlane(swap_s);
   }
   auto leave = [&]() { if (simd_slot >= 0 && lane == 0) atomicSub(u.simd_cnt + simd_slot, 1); };
-#else
-  auto leave = [&]() {};
-#endif
   const int c = blockIdx.x * 4 + grp;
   const int nch = (a.n + a.m - 1) / a.m;
   const bool valid = c < nch;
@@ -3173,9 +3109,6 @@ __global__ void __launch_bounds__(128, GPS_FUSED_WAVES) k_fused_level0(FusedArgs
   int tc = grp * BS + rr;         // ... its column r: OUTR[tc + k * BP]
   asm volatile("" : "+v"(ro), "+v"(co), "+v"(po), "+v"(oc), "+v"(tr), "+v"(tc));
   const int steps = __builtin_amdgcn_readfirstlane(max(ep - j0, 0));   // lane 0: the wave's first (never shorter) chunk
-#ifdef GPS_PROBE_ONLY_ROLE
-  if (role != GPS_PROBE_ONLY_ROLE) return;      // (register probes: one role's code alone; never a product build)
-#endif
   GPS_TR(0);
 #ifdef GPS_TRACE_FUSED
   if (u.trace && lane == 0) {
@@ -3523,7 +3456,7 @@ __global__ void __launch_bounds__(128, GPS_FUSED_WAVES) k_fused_level0(FusedArgs
         });
       }
       GPS_TRA(43);
-      if (kimg >= 3) fused_step_prio<B>(2 * (kimg - 3) + 1, 1);   // (image t + 3 is assembled under block step t: its middle)
+      if (kimg >= 3) fused_step_prio<B>(2 * (kimg - 3) + 1);   // (image t + 3 is assembled under block step t: its middle)
       if constexpr (ST12) {                              // the state's BetweenFactor<Pose3> record: six compact rows from its columns
         if (btw_on) {
           int rq = r;
@@ -3675,7 +3608,7 @@ __global__ void __launch_bounds__(128, GPS_FUSED_WAVES) k_fused_level0(FusedArgs
     assemble(2);
     write_img(0, 2);
     for (int t = 0; t < steps; t++) {
-      fused_step_prio<B>(2 * t, 1);
+      fused_step_prio<B>(2 * t);
       GPS_TR(3 + min(t, 50));
       lds_barrier();                     // step t: image t + 2 is there; image t + 1 is dead from here on
       if (t + 1 < steps) { assemble(t + 3); write_img((t + 1) & 1, t + 3); }
@@ -3718,102 +3651,10 @@ __global__ void __launch_bounds__(128, GPS_FUSED_WAVES) k_fused_level0(FusedArgs
     }
   }
   for (int t = 0; t < steps; t++) {
-    fused_step_prio<B>(2 * t, 0);
+    fused_step_prio<B>(2 * t);
     const int j = j0 + t;
     const bool live = j < e, lastb = (j == e - 1);
     const double *cur = IMG + ((t + 1) & 1) * 4 * IS, *nxt = IMG + (t & 1) * 4 * IS;   // images t + 1 and t + 2
-#ifdef GPS_ELIM_R5
-    double invs = 1.0;
-    static_for<0, B>([&](auto kk) {
-      constexpr int k = decltype(kk)::value;
-      const double piv = row_bcast<k>(Dr[k]);
-      const double inv = fast_rcp(piv);
-      const bool isk = (r == k);
-      invs = isk ? inv : invs;
-      const double nmp = isk ? 0.0 : -(Dr[k] * inv);
-      // row r -= (D~[r][k] / pivot) * row k, the pivot row fused into the multiply-add (fmac_self*): of D~ only the columns
-      // right of the pivot still matter, in blocks of four (entries at or left of the pivot inside a block become garbage
-      // that nothing reads again)
-      if constexpr (B == 12) {
-        if (k < 3) fmac_self4<k>(Dr, nmp);
-        if (k < 7) fmac_self4<k>(Dr + 4, nmp);
-        if (k < 11) fmac_self4<k>(Dr + 8, nmp);
-      } else {
-        fmac_self_n<k, B>(Dr, nmp);
-      }
-      fmac_self_n<k, B>(Or, nmp);
-      fmac_self_n<k, B>(Fr, nmp);
-      fmac_self1<k>(gr, nmp);
-    });
-    // a pivot that is not positive (or not a number) leaves a reciprocal that is not positive in its own lane: one test per
-    // block step instead of one per pivot (lanes without a row keep 1)
-    if (!(invs > 0.0) && live) *a.flag = 1;
-    __builtin_amdgcn_sched_barrier(0);
-    double Ol[B];
-#pragma unroll
-    for (int k = 0; k < B; k++) Ol[k] = cur[ro + B * BP + k];         // row r of O_j
-#pragma unroll
-    for (int k = 0; k < B; k++) { Or[k] *= invs; Fr[k] *= invs; }
-    gr *= invs;
-    if (rowlane) {
-#pragma unroll
-      for (int k = 0; k < B; k++) {
-        OUTR[oc + k * B] = Fr[k];
-        OUTR[oc + B * B + k * B] = Or[k];
-      }
-      OUTR[oc + 2 * B * B] = gr;
-    }
-    GPS_TR(3 + min(t, 50));
-    lds_barrier();                       // step t
-    if (live) {
-      V2 *dst = reinterpret_cast<V2 *>(a.blk + (size_t)j * BS);
-#pragma unroll
-      for (int q = 0; q < NV; q++) {
-        const int idx = q * 16 + r;
-        if (idx < NPC) dst[idx] = *reinterpret_cast<const V2 *>(&OUTR[po + 32 * q]);   // (nontemporal: the iteration +3 us at 1e5 states)
-      }
-    }
-    double Dn[B], Fn[B], gn;
-#pragma unroll
-    for (int k = 0; k < B; k++) Dn[k] = nxt[ro + k];
-    gn = nxt[co + 2 * B * BP];
-    __builtin_amdgcn_sched_barrier(0);
-    static_for<0, B>([&](auto ii) {
-      constexpr int i = decltype(ii)::value;
-      const double ol = Ol[i], gg = Gr[i];          // subtracted: the negation is the instructions' source modifier
-      fmac_bcast_n<i, B, true>(Dn, Or, ol);
-      fmac_bcast2<i, true>(gn, as_, gr, ol, gg);
-    });
-#pragma unroll
-    for (int k = 0; k < B; k++) asm volatile("" : "+v"(Dn[k]));
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k = 0; k < B; k++) Fn[k] = 0.0;
-    static_for<0, B>([&](auto ii) {
-      constexpr int i = decltype(ii)::value;
-      const double ol = Ol[i], gg = Gr[i];          // subtracted: the negation is the instructions' source modifier
-      fmac_bcast_n<i, B, true>(Fn, Fr, ol);        // F_{j+1} -= O_j[r][i] * (row i of V_j)
-      fmac_bcast_n<i, B, true>(Ar, Fr, gg);        // D_sep   -= G_j[r][i] * (row i of V_j)
-    });
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k = 0; k < B; k++) asm volatile("" : "+v"(Fn[k]), "+v"(Ar[k]));
-    // G_{j+1} = F_{j+1}^T by a transpose through LDS (the V area of the factor image, copied out long ago) instead of
-    // the recurrence G_{j+1} = -G_j U_j: 24 LDS operations for 144 multiply-adds
-    if (rowlane) {
-#pragma unroll
-      for (int k = 0; k < B; k++) OUTR[tr + k] = Fn[k];
-    }
-    wave_lds_sync();
-#pragma unroll
-    for (int k = 0; k < B; k++) {
-      Dr[k] = Dn[k]; Fr[k] = Fn[k]; Gr[k] = OUTR[tc + k * BP];
-      Or[k] = nxt[co + B * BP + k * BP];
-    }
-    gr = gn;
-    wave_lds_sync();
-    __builtin_amdgcn_sched_barrier(0);
-#else
     // Round 6: the elimination wave is the wave a block step waits for (scripts/trace_fused.py: the assembly wave sits at the
     // barrier 0.65-1.0 us of a 4.6-5.6 us step), and alone on a SIMD it issued one instruction per 8 cycles -- it waited for its own
     // dependent chains.  Same arithmetic, same operands, same order of every sum (bit-identical), rearranged so that no latency is
@@ -3865,7 +3706,7 @@ __global__ void __launch_bounds__(128, GPS_FUSED_WAVES) k_fused_level0(FusedArgs
     // block step instead of one per pivot (lanes without a row keep 1)
     if (!(invs > 0.0) && live) *a.flag = 1;
     __builtin_amdgcn_sched_barrier(0);
-    fused_step_prio<B>(2 * t + 1, 0);
+    fused_step_prio<B>(2 * t + 1);
     GPS_TRE(49);
 #pragma unroll
     for (int k = 0; k < B; k++) { Or[k] *= invs; Fr[k] *= invs; }
@@ -3941,7 +3782,6 @@ __global__ void __launch_bounds__(128, GPS_FUSED_WAVES) k_fused_level0(FusedArgs
     wave_lds_sync();
     __builtin_amdgcn_sched_barrier(0);
     GPS_TRE(53);
-#endif
     if (!tail && live && lastb && rowlane) {
       double *ub = a.up_blk + (size_t)c * BS;
 #pragma unroll

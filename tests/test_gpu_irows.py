@@ -1,4 +1,4 @@
-"""Interpolated measurement rows of an SE(3) chain as 16-double lines (round 5; kernels.hpp kIRow*, k_meas<..., IROW>,
+"""Interpolated measurement rows of an SE(3) chain as 16-double lines (round 5; kernels.hpp kIRow*, k_gps_lines,
 k_fused_level0<4>): GPInterpolatedGPSFactorPose3 (gpslam/slam/GPInterpolatedGPSFactorPose3.h:66-95) on a chain whose GP priors
 travel as structured records.  A row [Lp | mu | e, p11, p12, l12] stands for the 24 whitened columns
 [Lp | l12 mu | mu (p11 X + p12 F X) | p12 mu X] (GaussianProcessInterpolatorPose3.h:82-98); the assembly wave forms the right half

@@ -23,7 +23,7 @@ def _rerun(env, files, k=None):
 
 def test_block6_chains_through_the_unfused_row_layout_kernels():
     """Chains of block size 6 take k_fused_level0<.., 6> up to 131072 states and k_assemble_ghost + k_chunk_forward_rows<6> beyond
-    (api_impl.inc: fused_kernel_applies); GPSLAM_PLAN_UNFUSED_LEVEL0 sends the small parity cases through the latter -- where the GP
+    (api_impl.inc: make_plan); GPSLAM_PLAN_UNFUSED_LEVEL0 sends the small parity cases through the latter -- where the GP
     priors of the d = 3 manifolds travel as structured records (round 4)."""
     _rerun({"GPSLAM_PY_DEFAULT_PLAN": "1"}, ["test_gpu_parity.py", "test_gpu_upper.py"])
 

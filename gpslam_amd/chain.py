@@ -43,10 +43,23 @@ ABI_SYMBOLS = [
     "gpslam_hip_lm_decide", "gpslam_hip_set_collectives", "gpslam_hip_create_v2", "gpslam_hip_abi_version", "gpslam_hip_struct_size",
     "gpslam_hip_add_between_pairs", "gpslam_hip_set_level0_stamps",
     "gpslam_hip_marginals", "gpslam_hip_get_marginals", "gpslam_hip_interpolate_covariances",
+    "gpslam_hip_launch_census",
 ]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
-ABI_MAJOR, ABI_MINOR = 2, 3
+ABI_MAJOR, ABI_MINOR = 2, 4
 STRUCT_CONFIG, STRUCT_CONFIG_V2, STRUCT_STATS, STRUCT_PARAMS = 0, 1, 2, 3
+# gpslam_hip_launch_census: the GPSLAM_CENSUS_* entries of include/gpslam_hip.h, in order
+CENSUS_KEYS = (
+    "l0_fused", "l0_rows", "l0_column", "l0_column_fast", "top_chunk",
+    "sv", "dg", "block", "fp32", "gsave", "gp", "btw_rec", "lines", "odd_rows", "tail",
+    "gsave_launches", "tail_launches",
+    "upper_cr", "upper_chunk",
+    "bwd_rows", "bwd_rows_fold", "bwd_chunk", "upper_bwd",
+    "lin_rec", "lin_rec_vp", "lin_rows", "lin_rows_vp", "lin_vw", "lin_vw_vp", "lin_groups", "lin_pend", "flush",
+    "gps_lines", "meas_rec", "meas_self",
+    "retract",
+)
+CENSUS_GP_ROWS, CENSUS_GP_D3_RECORDS, CENSUS_GP_SE3_RECORDS = 0, 1, 2
 
 
 class GpslamHipError(RuntimeError):
@@ -441,6 +454,16 @@ class ChainSolver:
         out = (C.c_int32 * 8)()
         self._chk(self.lib.gpslam_hip_plan_info(self._h, out), "plan_info")
         return dict(zip(("levels", "chunk0", "chunk_upper", "fused", "structured_gp", "rows_full", "rows_compact", "R"), list(out)))
+
+    def launch_census(self, reset=True):
+        """What this handle's launchers did since the last reset: dict of CENSUS_KEYS (GPSLAM_CENSUS_* of include/gpslam_hip.h).
+        Launch counts, and for the last k_fused_level0 launch its instantiation (sv, dg, block, fp32) and inputs (gsave, gp, btw_rec,
+        lines, odd_rows, tail), -1 where there was none.  Written by the launch statements themselves, not derived from plan_info()."""
+        out = (C.c_int32 * len(CENSUS_KEYS))()
+        n = self._chk(self.lib.gpslam_hip_launch_census(self._h, out, len(CENSUS_KEYS), 1 if reset else 0), "launch_census")
+        if n != len(CENSUS_KEYS):
+            raise GpslamHipError("launch_census: the library reports %d entries, this binding names %d" % (n, len(CENSUS_KEYS)))
+        return dict(zip(CENSUS_KEYS, (int(v) for v in out)))
 
     def segment_plan(self):
         """dict of the segmented landmark elimination's plan (active, C, K, NB, NC, NCP, levels, links)."""

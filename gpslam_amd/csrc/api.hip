@@ -504,6 +504,13 @@ int gpslam_hip_plan_info(gpslam_hip_handle *h, int32_t out8[8]) {
   return 0;
 }
 
+int gpslam_hip_launch_census(gpslam_hip_handle *h, int32_t *out, int32_t n, int32_t reset) {
+  if (!h || n < 0 || (n > 0 && !out)) return GPSLAM_E_INVALID;
+  for (int i = 0; i < n && i < GPSLAM_CENSUS_N; i++) out[i] = h->census.v[i];
+  if (reset) h->census.clear();
+  return GPSLAM_CENSUS_N;
+}
+
 int gpslam_hip_segment_plan(gpslam_hip_handle *h, int32_t out8[8]) {
   int rc = need_compiled(h);
   if (rc) return rc;

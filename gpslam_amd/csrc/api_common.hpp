@@ -85,6 +85,17 @@ struct Plan {
 
 }  // namespace
 
+// gpslam_hip_launch_census: what the launchers did since the last reset (GPSLAM_CENSUS_*).  Host-side integers, written at the launch
+// statements from the branch taken -- never derived from the plan or from launch_form()
+struct LaunchCensus {
+  int32_t v[GPSLAM_CENSUS_N];
+  LaunchCensus() { clear(); }
+  void clear() {   // counts to 0, the entries that describe the last k_fused_level0 launch to "none"
+    for (int i = 0; i < GPSLAM_CENSUS_N; i++) v[i] = (i >= GPSLAM_CENSUS_FUSED_SV && i <= GPSLAM_CENSUS_FUSED_TAIL) ? -1 : 0;
+  }
+  int32_t &operator[](int i) { return v[i]; }
+};
+
 struct gpslam_hip_handle {
   gpslam_hip_config_v2 cfg;   // (gpslam_hip_create maps a v1 config onto it)
   int mf = 0, d = 0, pd = 0, b = 0, ld = 0;
@@ -142,6 +153,7 @@ struct gpslam_hip_handle {
   FatSepPlan fs;
   DevBuf lm_gL;             // undamped landmark gradient of the segmented path (the dense path keeps it behind lm_S)
   Plan plan;                // compile(): which kernels serve this graph, in which form
+  LaunchCensus census;      // gpslam_hip_launch_census
   DevBuf gps, gpidx, dU, gsave2;
   DevBuf simd_cnt;          // k_fused_level0 (role swap): wave-0 count per SIMD of the chip, zero between launches
   DevBuf rowI, irowptr;     // Plan::lines
@@ -499,12 +511,49 @@ int refresh_dU(gpslam_hip_handle *h) {
 // host code never selects them (make_plan), these overloads only keep it compiling
 namespace {
 // ea / eb != null: the launch carries its own start / stop events (a timed iteration: the dispatch's own time stamps)
+// (expands inside launch_fused_k only: grid, st, ea, eb, u and the census array `cen` are that function's parameters)
+// (the census takes the instantiation from the text of the launch statement itself, at compile time: it cannot drift from it)
+struct FusedId { int sv = 0, b = 12; bool fp32 = false, dg = false; };
+constexpr FusedId fused_id(const char *s) {   // "k_fused_level0<SV[, TR[, B[, DG]]]>", the template's defaults where the text stops early
+  FusedId id;
+  while (*s != '<') ++s;
+  id.sv = s[1] - '0';
+  for (int field = 0; *s != '>'; ++s) {
+    if (*s != ',') continue;
+    while (s[1] == ' ') ++s;
+    field++;
+    if (field == 1) id.fp32 = s[1] == 'f';
+    if (field == 2) { id.b = 0; for (const char *t = s + 1; *t >= '0' && *t <= '9'; ++t) id.b = id.b * 10 + (*t - '0'); }
+    if (field == 3) id.dg = s[1] == 't';
+  }
+  return id;
+}
+static_assert(fused_id("k_fused_level0<4>").sv == 4 && fused_id("k_fused_level0<4>").b == 12 && !fused_id("k_fused_level0<4>").dg, "fused_id");
+static_assert(fused_id("k_fused_level0<1,double,6>").sv == 1 && fused_id("k_fused_level0<1,double,6>").b == 6 && !fused_id("k_fused_level0<1,double,6>").fp32 &&
+              fused_id("k_fused_level0<2,float,12,true>").dg && fused_id("k_fused_level0<2,float,12,true>").fp32 && fused_id("k_fused_level0<2,float,12,true>").b == 12, "fused_id");
+static_assert(fused_id("k_fused_level0<3, double, 12, true>").dg && fused_id("k_fused_level0<0, float, 6>").fp32 && fused_id("k_fused_level0<0, float, 6>").b == 6, "fused_id");
 #define GPS_FUSED_LAUNCH(...)                                                                                      \
   do {                                                                                                             \
+    constexpr FusedId id_ = fused_id(#__VA_ARGS__);                                                                \
+    cen[GPSLAM_CENSUS_L0_FUSED]++;                                                                                 \
+    cen[GPSLAM_CENSUS_FUSED_SV] = id_.sv; cen[GPSLAM_CENSUS_FUSED_DG] = id_.dg; cen[GPSLAM_CENSUS_FUSED_B] = id_.b; \
+    cen[GPSLAM_CENSUS_FUSED_FP32] = id_.fp32;                                                                      \
     if (ea) hipExtLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(128), 0, st, ea, eb, 0, u);                      \
     else __VA_ARGS__<<<dim3(grid), dim3(128), 0, st>>>(u);                                                         \
   } while (0)
-inline void launch_fused_k(int b, const LaunchForm &f, const FusedArgs<double, double> &u, int grid, hipStream_t st, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr) {
+// the inputs of a k_fused_level0 launch as its arguments carry them (census)
+template <typename TR> inline void census_fused_inputs(int32_t *cen, int b, const FusedArgs<double, TR> &u) {
+  cen[GPSLAM_CENSUS_FUSED_GP] = u.gps == nullptr ? 0 : (b == 6 ? 1 : 2);
+  cen[GPSLAM_CENSUS_FUSED_BTW_REC] = u.brec != nullptr;
+  cen[GPSLAM_CENSUS_FUSED_LINES] = u.rowI != nullptr;
+  cen[GPSLAM_CENSUS_FUSED_ODD_ROWS] = u.odd_rows;
+  cen[GPSLAM_CENSUS_FUSED_GSAVE] = u.gsave != nullptr;
+  cen[GPSLAM_CENSUS_FUSED_TAIL] = u.f.tail != 0;
+  cen[GPSLAM_CENSUS_FUSED_GSAVE_LAUNCHES] += u.gsave != nullptr;
+  cen[GPSLAM_CENSUS_FUSED_TAIL_LAUNCHES] += u.f.tail != 0;
+}
+inline void launch_fused_k(int32_t *cen, int b, const LaunchForm &f, const FusedArgs<double, double> &u, int grid, hipStream_t st, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr) {
+  census_fused_inputs(cen, b, u);
   if (b == 6) {
     if (f.sv == 1) GPS_FUSED_LAUNCH(k_fused_level0<1, double, 6>);      // d = 3 records (kGp3*)
     else GPS_FUSED_LAUNCH(k_fused_level0<0, double, 6>);
@@ -529,28 +578,33 @@ inline void launch_fused_k(int b, const LaunchForm &f, const FusedArgs<double, d
 }
 // fp32 handles: fp32 row tables straight into the fused kernel's fp64 accumulation (round 3: the unfused assembly had cost the
 // fp32 mode more than its halved row traffic saved)
-inline void launch_fused_k(int b, const LaunchForm &, const FusedArgs<double, float> &u, int grid, hipStream_t st, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr) {
+inline void launch_fused_k(int32_t *cen, int b, const LaunchForm &, const FusedArgs<double, float> &u, int grid, hipStream_t st, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr) {
+  census_fused_inputs(cen, b, u);
   if (b == 6) GPS_FUSED_LAUNCH(k_fused_level0<0, float, 6>);
   else GPS_FUSED_LAUNCH(k_fused_level0<0, float>);
 }
 // GPInterpolatedGPSFactorPose3 as 16-double lines: fp64 only (Plan::lines)
-inline void launch_gps_lines_k(const MeasArgs<double> &a, int nb, hipStream_t st) {
+inline void launch_gps_lines_k(int32_t *cen, const MeasArgs<double> &a, int nb, hipStream_t st) {
+  cen[GPSLAM_CENSUS_GPS_LINES]++;
   if (a.aidx != nullptr) k_gps_lines<kGpsLinesWaves, true><<<dim3(nb), dim3(128), 0, st>>>(a);   // (round 6: a kernel written for its register count)
   else k_gps_lines<kGpsLinesWaves, false><<<dim3(nb), dim3(128), 0, st>>>(a);
 }
-inline void launch_gps_lines_k(const MeasArgs<float> &, int, hipStream_t) {}
-inline void launch_rows_k(int b, const FwdArgs<double> &a, int grid, hipStream_t st) {
+inline void launch_gps_lines_k(int32_t *, const MeasArgs<float> &, int, hipStream_t) {}
+inline void launch_rows_k(int32_t *cen, int b, const FwdArgs<double> &a, int grid, hipStream_t st) {
+  cen[GPSLAM_CENSUS_L0_ROWS]++;
   if (b == 12) k_chunk_forward_rows<12><<<dim3(grid), dim3(64), 0, st>>>(a);
   else if (b == 6) k_chunk_forward_rows<6><<<dim3(grid), dim3(64), 0, st>>>(a);
   else k_chunk_forward_rows<4><<<dim3(grid), dim3(64), 0, st>>>(a);
 }
-inline void launch_rows_k(int, const FwdArgs<float> &, int, hipStream_t) {}
-inline void launch_bwd_rows_k(int b, const BwdArgs<double> &a, int grid, hipStream_t st) {
+inline void launch_rows_k(int32_t *, int, const FwdArgs<float> &, int, hipStream_t) {}
+inline void launch_bwd_rows_k(int32_t *cen, int b, const BwdArgs<double> &a, int grid, hipStream_t st) {
+  cen[GPSLAM_CENSUS_BWD_ROWS]++;
+  cen[GPSLAM_CENSUS_BWD_ROWS_FOLD] += a.l1_blk != nullptr;
   if (b == 12) k_chunk_backward_rows<12><<<dim3(grid), dim3(64), 0, st>>>(a);
   else if (b == 6) k_chunk_backward_rows<6><<<dim3(grid), dim3(64), 0, st>>>(a);
   else k_chunk_backward_rows<4><<<dim3(grid), dim3(64), 0, st>>>(a);
 }
-inline void launch_bwd_rows_k(int, const BwdArgs<float> &, int, hipStream_t) {}
+inline void launch_bwd_rows_k(int32_t *, int, const BwdArgs<float> &, int, hipStream_t) {}
 // segment interiors of the segmented landmark elimination: planar fp64 chains take the cooperative row-layout kernel (four
 // segments per wave), everything else the wave-per-segment kernel
 template <int BB, typename T, typename TR> inline void fs_launch_factor(const FsArgs<T, TR> &a, int nseg, hipStream_t st) {

@@ -119,6 +119,7 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
   const LaunchForm form = launch_form(h, m);
   if (h->pend_upd && !(merged && form.gp != GpForm::Rows)) {   // (defensive: an update is pending and this launch cannot apply it)
     h->pend_upd = false;
+    h->census[GPSLAM_CENSUS_FLUSH]++;
     int rcp = launch_retract(h, LaunchMode{}, 2);
     if (rcp) return rcp;
   }
@@ -191,9 +192,10 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
       const bool vp = la.nb[1] > 0;
       if constexpr ((MF == POSE3 || MF == POSE2 || MF == ROT3 || MF == LINEAR3) && kIsF64) {
         if (la.gp.gps != nullptr) {      // structured GP records (never on a world-velocity chain: make_plan)
-          if (vp) k_lin<RowT, MF, false, true, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la);
-          else k_lin<RowT, MF, false, false, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la);
+          if (vp) { h->census[GPSLAM_CENSUS_LIN_REC_VP]++; k_lin<RowT, MF, false, true, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
+          else { h->census[GPSLAM_CENSUS_LIN_REC]++; k_lin<RowT, MF, false, false, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
           if (pend) {                    // the launch wrote every state into the other buffer: that one is current from here on
+            h->census[GPSLAM_CENSUS_LIN_PEND]++;
             std::swap(h->pose, h->pose_bak);
             std::swap(h->vel, h->vel_bak);
             h->pend_upd = false;
@@ -202,11 +204,11 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
         }
       }
       if (MF == POSE3 && h->vw) {
-        if (vp) k_lin<RowT, MF, true, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la);
-        else k_lin<RowT, MF, true, false><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la);
+        if (vp) { h->census[GPSLAM_CENSUS_LIN_VW_VP]++; k_lin<RowT, MF, true, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
+        else { h->census[GPSLAM_CENSUS_LIN_VW]++; k_lin<RowT, MF, true, false><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
       } else {
-        if (vp) k_lin<RowT, MF, false, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la);
-        else k_lin<RowT, MF, false, false><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la);
+        if (vp) { h->census[GPSLAM_CENSUS_LIN_ROWS_VP]++; k_lin<RowT, MF, false, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
+        else { h->census[GPSLAM_CENSUS_LIN_ROWS]++; k_lin<RowT, MF, false, false><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
       }
     });
   } else {
@@ -216,6 +218,7 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
     dispatch_mf(h->mf, [&](auto tag) {
       constexpr int MF = decltype(tag)::value;
       if (pass == 0) {
+        h->census[GPSLAM_CENSUS_LIN_GROUPS]++;
         launch_gp_rows<MF>(h, a, nb);
       } else {
         k_gp<RowT, MF, 1><<<dim3(nb), dim3(128), 0, h->stream>>>(a);
@@ -268,7 +271,7 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
       if (meas_rec && form.lines && fk == FK_INTERP_GPS) {   // 16-double lines for k_fused_level0<4> instead of 24-column rows
         a.rowI = h->rowI.as<RowT>(); a.row0 = s.d_irow0.as<int>();
         a.rowLR = nullptr; a.rowE = nullptr; a.rowM = nullptr; a.rowLm = nullptr;
-        launch_gps_lines_k(a, nb, side);
+        launch_gps_lines_k(h->census.v, a, nb, side);
         off += nb;
         continue;
       }
@@ -277,7 +280,10 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
       constexpr int MF = decltype(tag)::value;
       dispatch_fk(fk, [&](auto ftag) {
         constexpr int FK = decltype(ftag)::value;
-        if (pass == 0) k_meas<RowT, MF, FK, true><<<dim3(nb), dim3(128), 0, side>>>(a);
+        if (pass == 0) {
+          if (FK == FK_INTERP_GPS) h->census[a.gps != nullptr ? GPSLAM_CENSUS_MEAS_REC : GPSLAM_CENSUS_MEAS_SELF]++;
+          k_meas<RowT, MF, FK, true><<<dim3(nb), dim3(128), 0, side>>>(a);
+        }
         else k_meas<RowT, MF, FK, false><<<dim3(nb), dim3(128), 0, side>>>(a);
       });
     });
@@ -387,15 +393,18 @@ int launch_fwd(gpslam_hip_handle *h, const LaunchMode &m, const FwdArgs<Real> &a
     (void)hipMemsetAsync(h->dbg_trace.p, 0, (size_t)h->dbg_trace_waves * 64 * 8, h->stream);
     u.trace = h->dbg_trace.as<unsigned long long>();
 #endif
-    launch_fused_k(h->b, form, u, nblocks(grid, 4), h->stream, m.l0_events ? h->ev_l0a : nullptr, m.l0_events ? h->ev_l0b : nullptr);
+    launch_fused_k(h->census.v, h->b, form, u, nblocks(grid, 4), h->stream, m.l0_events ? h->ev_l0a : nullptr, m.l0_events ? h->ev_l0b : nullptr);
     return 0;
   }
   if (h->plan.rows() && !a.no_sep && !a.add) {
-    launch_rows_k(h->b, a, nblocks(grid, 4), h->stream);
+    launch_rows_k(h->census.v, h->b, a, nblocks(grid, 4), h->stream);
     return 0;
   }
   dispatch_b(h->b, [&](auto tag) {
     constexpr int BB = decltype(tag)::value;
+    // (census: a level with addends is a level above 0; without them, the top solve where no separator is kept, else level 0)
+    h->census[a.add ? GPSLAM_CENSUS_UPPER_CHUNK : (a.no_sep ? GPSLAM_CENSUS_TOP_CHUNK : GPSLAM_CENSUS_L0_COLUMN)]++;
+    if (fast && !a.add && !a.no_sep) h->census[GPSLAM_CENSUS_L0_COLUMN_FAST]++;
     if (fast) k_chunk_forward<Real, BB, true><<<dim3(grid), dim3(64), 0, h->stream>>>(a);
     else k_chunk_forward<Real, BB, false><<<dim3(grid), dim3(64), 0, h->stream>>>(a);
   });
@@ -403,9 +412,10 @@ int launch_fwd(gpslam_hip_handle *h, const LaunchMode &m, const FwdArgs<Real> &a
 }
 void launch_bwd(gpslam_hip_handle *h, const BwdArgs<Real> &a, int grid) {
   // chains without landmark columns: the row-layout kernel, four chunks per wave (the column-layout plan keeps the generic one)
-  if (a.R == 1 && h->plan.rows()) { launch_bwd_rows_k(h->b, a, nblocks(grid, 4), h->stream); return; }
+  if (a.R == 1 && h->plan.rows()) { launch_bwd_rows_k(h->census.v, h->b, a, nblocks(grid, 4), h->stream); return; }
   dispatch_b(h->b, [&](auto tag) {
     constexpr int BB = decltype(tag)::value;
+    h->census[GPSLAM_CENSUS_BWD_CHUNK]++;
     // 16-byte pieces per lane per record: 3 wave loads cover 2 b^2 + b R <= 384 doubles, 5 cover every admissible R
     if (2 * BB * BB + BB * h->R <= 384) k_chunk_backward<Real, BB, 3><<<dim3(grid), dim3(64), 0, h->stream>>>(a);
     else k_chunk_backward<Real, BB, 5><<<dim3(grid), dim3(64), 0, h->stream>>>(a);
@@ -473,6 +483,7 @@ int launch_forward(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
         u.ext = has_right_rank(h) ? 1 : 0;     // [blk (BS) | addend slot 1 (AS)]: slot 0 is unused, so point one slot back
         if (last) { u.up_blk = h->iface_send.as<double>(); u.up_add = h->iface_send.as<double>() + BS - AS; }
       }
+      h->census[GPSLAM_CENSUS_UPPER_CR]++;
       const int e = upper_forward(h->b, v.m, last && !sh, u, h->stream);
       if (e) { h->err = std::string("upper_forward: ") + hipGetErrorString((hipError_t)e); return GPSLAM_E_HIP; }
       continue;
@@ -528,6 +539,7 @@ int launch_backward(gpslam_hip_handle *h, const Real *xtop) {
       u.blk = v.blk.as<double>(); u.x = v.x.as<double>(); u.n = v.n;
       u.xup = last ? xtop : h->lv[l + 1].x.as<double>();
       u.ext = (sh && has_right_rank(h)) ? 1 : 0;
+      h->census[GPSLAM_CENSUS_UPPER_BWD]++;
       const int e = upper_backward(h->b, v.m, u, h->stream);
       if (e) { h->err = std::string("upper_backward: ") + hipGetErrorString((hipError_t)e); return GPSLAM_E_HIP; }
       continue;
@@ -1016,6 +1028,7 @@ void launch_retract_k(gpslam_hip_handle *h) {
   int grid;
   const RetractArgs<Real> a = retract_args(h, grid);
   h->pend_err_n = 0;
+  h->census[GPSLAM_CENSUS_RETRACT]++;
   dispatch_mf(h->mf, [&](auto tag) {
     constexpr int MF = decltype(tag)::value;
     k_retract<Real, MF><<<dim3(grid), dim3(128), 0, h->stream>>>(a);

@@ -78,10 +78,10 @@ enum {
  * last_trial_error; GPSLAM_E_COMM; plan bits 64, 128) -- shipped without a version symbol; 2.0 this header: gpslam_hip_config_v2 +
  * gpslam_hip_create_v2 (named fields, struct_size first), gpslam_hip_abi_version, gpslam_hip_struct_size.  The v1 config and
  * gpslam_hip_create stay, bit for bit; 2.1 gpslam_hip_add_between_pairs (loop closures); 2.2 gpslam_hip_set_level0_stamps; 2.3
- * gpslam_hip_marginals, gpslam_hip_get_marginals, gpslam_hip_interpolate_covariances.  A MAJOR bump changes a struct or a
+ * gpslam_hip_marginals, gpslam_hip_get_marginals, gpslam_hip_interpolate_covariances; 2.4 gpslam_hip_launch_census.  A MAJOR bump changes a struct or a
  * signature, a MINOR bump only adds. */
 #define GPSLAM_HIP_ABI_MAJOR 2
-#define GPSLAM_HIP_ABI_MINOR 3
+#define GPSLAM_HIP_ABI_MINOR 4
 #define GPSLAM_HIP_ABI_VERSION ((GPSLAM_HIP_ABI_MAJOR << 16) | GPSLAM_HIP_ABI_MINOR)
 uint32_t gpslam_hip_abi_version(void);
 enum { GPSLAM_STRUCT_CONFIG = 0, GPSLAM_STRUCT_CONFIG_V2 = 1, GPSLAM_STRUCT_STATS = 2, GPSLAM_STRUCT_PARAMS = 3 };
@@ -400,6 +400,62 @@ int gpslam_hip_body_centric_velocity(gpslam_hip_handle *h, int32_t which, int32_
  * 16-double lines whose right halves the assembly wave forms from the interval's record -- round 5), rows in the
  * full-width table, rows in the compact table, right-hand-side columns R}. */
 int gpslam_hip_plan_info(gpslam_hip_handle *h, int32_t out8[8]);
+/* What the launchers of this handle DID since the last reset (introspection for tests; no reference counterpart).  plan_info above
+ * is computed from the plan; these are host-side integers the launchers write at their launch statements, each from the branch it
+ * took, so a handle that quietly takes another form than the plan promises shows here.  Recording costs a few integer stores per
+ * launch: no device work, no synchronisation, no allocation.  out receives min(n, GPSLAM_CENSUS_N) entries, indexed by
+ * GPSLAM_CENSUS_*; reset != 0 clears the counts (and the "last launch" entries to -1) after reading.  Returns GPSLAM_CENSUS_N of
+ * the library, or an error code.  Counts cover the iteration launchers (linearisation, level 0, the levels above, back-substitution,
+ * retraction) from whichever call reached them. */
+enum {
+  /* level-0 forward elimination, launches per family */
+  GPSLAM_CENSUS_L0_FUSED = 0,       /* k_fused_level0 */
+  GPSLAM_CENSUS_L0_ROWS,            /* k_chunk_forward_rows */
+  GPSLAM_CENSUS_L0_COLUMN,          /* k_chunk_forward on a level without addends that keeps its separators ... */
+  GPSLAM_CENSUS_L0_COLUMN_FAST,     /* ... of which the variant with the separator sums in spare lanes */
+  GPSLAM_CENSUS_TOP_CHUNK,          /* k_chunk_forward as the sequential top solve of blocks without addends (a chain of a single level,
+                                     * the reduced system of a sharded solve, gpslam_hip_block_tridiag_solve) */
+  /* the LAST k_fused_level0 launch (-1: none since the reset): its instantiation <SV, TR, B, DG> ... */
+  GPSLAM_CENSUS_FUSED_SV,
+  GPSLAM_CENSUS_FUSED_DG,
+  GPSLAM_CENSUS_FUSED_B,
+  GPSLAM_CENSUS_FUSED_FP32,         /* TR: 0 double, 1 float */
+  GPSLAM_CENSUS_FUSED_GSAVE,        /* the gradient was stored (a Levenberg-Marquardt trial) */
+  /* ... and its inputs as passed */
+  GPSLAM_CENSUS_FUSED_GP,           /* GP priors consumed as 0 rows, 1 d = 3 records, 2 SE(3) records */
+  GPSLAM_CENSUS_FUSED_BTW_REC,      /* between records attached */
+  GPSLAM_CENSUS_FUSED_LINES,        /* interpolated GPS lines attached */
+  GPSLAM_CENSUS_FUSED_ODD_ROWS,     /* FusedArgs::odd_rows */
+  GPSLAM_CENSUS_FUSED_TAIL,         /* level 1 reduced in the kernel's tail (FwdArgs::tail) */
+  GPSLAM_CENSUS_FUSED_GSAVE_LAUNCHES,   /* k_fused_level0 launches that stored the gradient */
+  GPSLAM_CENSUS_FUSED_TAIL_LAUNCHES,    /* k_fused_level0 launches with the tail on */
+  /* levels above level 0, forward */
+  GPSLAM_CENSUS_UPPER_CR,           /* upper_forward launches (LDS-resident cyclic reduction) */
+  GPSLAM_CENSUS_UPPER_CHUNK,        /* k_chunk_forward launches on a level with addends */
+  /* back-substitution */
+  GPSLAM_CENSUS_BWD_ROWS,           /* k_chunk_backward_rows launches ... */
+  GPSLAM_CENSUS_BWD_ROWS_FOLD,      /* ... of which solved their group of four of level 1 themselves (BwdArgs::l1_blk) */
+  GPSLAM_CENSUS_BWD_CHUNK,          /* k_chunk_backward launches */
+  GPSLAM_CENSUS_UPPER_BWD,          /* upper_backward launches */
+  /* K1, Jacobian pass: one counter per k_lin statement */
+  GPSLAM_CENSUS_LIN_REC,            /* merged k_lin writing records, no velocity priors */
+  GPSLAM_CENSUS_LIN_REC_VP,         /* ... with velocity priors */
+  GPSLAM_CENSUS_LIN_ROWS,           /* merged k_lin writing rows, body velocities, no velocity priors */
+  GPSLAM_CENSUS_LIN_ROWS_VP,
+  GPSLAM_CENSUS_LIN_VW,             /* merged k_lin writing rows, world velocities */
+  GPSLAM_CENSUS_LIN_VW_VP,
+  GPSLAM_CENSUS_LIN_GROUPS,         /* k_gp launches of the Jacobian pass, one per Qc group */
+  GPSLAM_CENSUS_LIN_PEND,           /* k_lin launches that applied a pending update (run_gn's folded retraction) */
+  GPSLAM_CENSUS_FLUSH,              /* a pending update met a launch that could not apply it: retracted on the spot */
+  /* interpolated GPS, Jacobian pass */
+  GPSLAM_CENSUS_GPS_LINES,          /* k_gps_lines launches */
+  GPSLAM_CENSUS_MEAS_REC,           /* k_meas launches with the intervals' GP records attached (a factor whose interval has none forms
+                                     * its blocks itself inside the kernel: not visible to the host) */
+  GPSLAM_CENSUS_MEAS_SELF,          /* k_meas launches without records: every factor forms its blocks itself */
+  GPSLAM_CENSUS_RETRACT,            /* k_retract launches over the local states */
+  GPSLAM_CENSUS_N
+};
+int gpslam_hip_launch_census(gpslam_hip_handle *h, int32_t *out, int32_t n, int32_t reset);
 /* the plan of the segmented landmark elimination chosen by compile(): out = {active (0 / 1), segment length C, fat
  * blocks K, fat block size NB, border columns NC per segment, NC rounded up to MFMA tiles, cyclic-reduction levels,
  * link blocks} */

@@ -10,6 +10,7 @@ from test_gpu_parity import gpu, build_pair, random_chain
 pytestmark = pytest.mark.gpu
 
 KW = {O.POSE2: dict(chart=1)}
+FP32_STATE_REL = 1e-5     # north_star's fp32 tolerance: converged states against the fp64 fixed point, relative
 
 
 def _converge(s, iters):
@@ -67,7 +68,7 @@ def test_fp32_converges_to_the_fp64_fixed_point(kind):
     h = _converge(dev32, 12)
     rel = _rel_state_diff(kind, orc, dev32)
     print("fp32 vs fp64 oracle, kind %d: relative state difference %.3e, |delta| history %s" % (kind, rel, ["%.1e" % x for x in h]))
-    assert rel <= 1e-5, rel
+    assert rel <= FP32_STATE_REL, rel
     assert abs(dev32.error() - orc.error()) <= 1e-7 * max(1.0, orc.error())
 
 
@@ -94,7 +95,7 @@ def test_fp32_c3_mix_matches_the_oracle():
     h = _converge(dev, 10)
     rel = _rel_state_diff(O.POSE3, orc, dev)
     print("C3 mix fp32: relative state difference %.3e, |delta| %s" % (rel, ["%.1e" % x for x in h]))
-    assert rel <= 1e-5, rel
+    assert rel <= FP32_STATE_REL, rel
     assert abs(dev.error() - orc.error()) <= 1e-9 * orc.error()
 
 
@@ -110,14 +111,14 @@ def test_fp32_c5_mix_matches_the_oracle():
     h0, h1 = _lm_converge(orc, 25), _lm_converge(dev, 25)
     rel = _rel_state_diff(O.ROT3, orc, dev)
     print("C5 rot3 mix fp32 (LM): relative state difference %.3e, errors %.9e / %.9e, last |delta| %.1e / %.1e" % (rel, h0[-1][0], h1[-1][0], h0[-1][1], h1[-1][1]))
-    assert rel <= 1e-5, rel
+    assert rel <= FP32_STATE_REL, rel
     p = S.pose3_gps_chain(1200)
     orc = S.apply(p, O.Chain(O.POSE3))
     dev = S.apply(p, gp.ChainSolver(O.POSE3, precision=gp.FP32))
     h0, h1 = _lm_converge(orc, 20), _lm_converge(dev, 20)
     rel = _rel_state_diff(O.POSE3, orc, dev)
     print("C5 pose3+gps mix fp32 (LM): relative state difference %.3e, errors %.9e / %.9e, last |delta| %.1e / %.1e" % (rel, h0[-1][0], h1[-1][0], h0[-1][1], h1[-1][1]))
-    assert rel <= 1e-5, rel
+    assert rel <= FP32_STATE_REL, rel
 
 
 def test_fp32_2dlinear_factors_with_nonzero_headings():
@@ -134,4 +135,4 @@ def test_fp32_2dlinear_factors_with_nonzero_headings():
     h = _converge(dev32, 12)
     rel = _rel_state_diff(O.LINEAR3, orc, dev32)
     print("fp32 2D-linear factors: relative state difference %.3e, |delta| history %s" % (rel, ["%.1e" % x for x in h]))
-    assert rel <= 1e-5, rel
+    assert rel <= FP32_STATE_REL, rel

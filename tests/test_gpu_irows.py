@@ -72,7 +72,14 @@ def test_line_form_agrees_with_the_oracle_and_with_the_row_form(N, per, sensor, 
     rows = feed(gp.ChainSolver(gp.POSE3, plan=plan | gp.PLAN_MEAS_ROWS))
     assert line.plan_info()["structured_gp"] == 2 and rows.plan_info()["structured_gp"] == 1     # 2: records + interpolated lines
     assert abs(orc.error() - line.error()) <= 1e-10 * orc.error()
+    line.launch_census(); rows.launch_census()
     lockstep_gn([orc, line, rows], O.POSE3, 5, 1e-9)
+    # what the five iterations launched: k_gps_lines into k_fused_level0<4> on the one handle, k_meas (reading the intervals' records)
+    # into <3> on the other
+    cl, cr = line.launch_census(), rows.launch_census()
+    assert (cl["gps_lines"], cl["meas_rec"], cl["meas_self"], cl["sv"], cl["lines"], cl["l0_fused"]) == (5, 0, 0, 4, 1, 5), cl
+    assert (cr["gps_lines"], cr["meas_rec"], cr["meas_self"], cr["sv"], cr["lines"], cr["l0_fused"]) == (0, 5, 0, 3, 0, 5), cr
+    assert cl["dg"] == cr["dg"] == (0 if generic else 1), (cl, cr)     # (gps_graph's Qc is isotropic)
     for s in (line, rows):
         s.close()
 
@@ -103,7 +110,10 @@ def test_an_interval_without_a_gp_prior_keeps_the_row_form():
     feed, p = gps_graph(200, seed=5, skip_gp=(77,))
     orc, dev = feed(O.Chain(O.POSE3)), feed(gp.ChainSolver(gp.POSE3))
     assert dev.plan_info()["structured_gp"] == 1
+    dev.launch_census()
     lockstep_gn([orc, dev], O.POSE3, 4, 1e-9)
+    c = dev.launch_census()
+    assert (c["gps_lines"], c["meas_rec"], c["sv"], c["lines"], c["l0_fused"]) == (0, 4, 3, 0, 4), c
     dev.close()
 
 

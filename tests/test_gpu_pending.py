@@ -16,6 +16,15 @@ def gpu():
     return gpslam_amd
 
 
+def _folds_as_expected(census, name, K, foldable):
+    """What the launchers did (gpslam_hip_launch_census), not what the plan promises: a folded run applies K - 1 pending updates inside
+    k_lin and ends with ONE k_retract; the other two launch k_retract K times; and the defensive flush of launch_factors -- which
+    would make a library that never folds bit-identical too -- never runs."""
+    want = dict(lin_pend=K - 1, retract=1) if (name == "folded" and foldable) else dict(lin_pend=0, retract=K)
+    got = {k: census[k] for k in ("lin_pend", "retract", "flush")}
+    assert got == dict(want, flush=0), (name, got, census)
+
+
 @pytest.mark.parametrize("N,chart,vprior", [(64, 0, False), (700, 0, False), (1001, 1, False), (333, 0, True), (2, 0, False), (3, 1, True)],
                          ids=["64", "700", "1001-first-order-chart", "333+velocity-prior", "2-states", "3-states"])
 def test_run_gn_is_bit_identical_to_single_iterations(N, chart, vprior):
@@ -28,11 +37,13 @@ def test_run_gn_is_bit_identical_to_single_iterations(N, chart, vprior):
     sols = {}
     for name, plan, single in (("folded", 0, False), ("separate", gp.PLAN_SEPARATE_RETRACT, False), ("single", 0, True)):
         s = S.apply(p, gp.ChainSolver(gp.POSE3, chart=chart, plan=plan))
+        s.launch_census()
         if single:
             for _ in range(K):
                 _, st = s.iterate_gn()
         else:
             st, _ = s.run_gn(K)
+        _folds_as_expected(s.launch_census(), name, K, N not in (2, 3))     # (2 and 3 states: one level, the top solve -- no fused level 0 whose K1 writes records, nothing to fold into)
         sols[name] = (s.get_states(), st.error_before, st.error_after, st.delta_inf_norm)
         s.close()
     (x0, v0), eb0, ea0, d0 = sols["single"]
@@ -81,11 +92,13 @@ def test_run_gn_on_the_d3_record_chains_is_bit_identical_to_single_iterations(ki
     sols = {}
     for name, plan, single in (("folded", 0, False), ("separate", gp.PLAN_SEPARATE_RETRACT, False), ("single", 0, True)):
         s = S.apply(p, gp.ChainSolver(kind, chart=chart, plan=plan))
+        s.launch_census()
         if single:
             for _ in range(K):
                 _, st = s.iterate_gn()
         else:
             st, _ = s.run_gn(K)
+        _folds_as_expected(s.launch_census(), name, K, True)
         sols[name] = (s.get_states(), st.error_before, st.error_after, st.delta_inf_norm)
         s.close()
     (x0, v0), eb0, ea0, d0 = sols["single"]

@@ -79,8 +79,11 @@ def test_structured_records_reproduce_the_row_path():
             dev.compile()
         info = dev.plan_info()
         assert info["structured_gp"] == (0 if extra < 0 else 1) and info["rows_full"] == 12 * (N - 1) + 6 * max(extra, 0)
+        dev.launch_census()
         for _ in range(3):
             dev.iterate_gn()
+        cen = dev.launch_census()        # what the three level-0 launches were, not what the plan says they would be
+        assert cen["l0_fused"] == 3 and cen["sv"] == {0: 1, 1: 2, 9: 3, -1: 0}[extra] and cen["btw_rec"] == (1 if extra == 0 else 0), (extra, cen)
         res.append(dev.get_states())
     for k in (1, 2, 3):
         assert np.abs(res[0][0] - res[k][0]).max() <= 1e-11 * max(1.0, np.abs(res[k][0]).max())
@@ -97,7 +100,7 @@ def test_diagonal_qc_takes_the_short_form_of_the_assembly_wave(N):
     rng = np.random.default_rng(5)
     Qc = np.diag(0.01 + 0.02 * rng.random(6))
     c = T.random_chain(O.POSE3, N, 31)
-    out = []
+    out, cen = [], []
     for make in (lambda: O.Chain(O.POSE3, O.CHART_EXPMAP), lambda: gpslam_amd.ChainSolver(O.POSE3, O.CHART_EXPMAP),
                  lambda: gpslam_amd.ChainSolver(O.POSE3, O.CHART_EXPMAP, plan=gpslam_amd.PLAN_GENERIC_QC)):
         s = make()
@@ -113,6 +116,10 @@ def test_diagonal_qc_takes_the_short_form_of_the_assembly_wave(N):
         for _ in range(4):
             s.iterate_gn()
         out.append(s.get_states())
+        if hasattr(s, "launch_census"):
+            cen.append(s.launch_census())
+    assert cen[0]["l0_fused"] == 4 and cen[0]["sv"] == 1 and cen[0]["dg"] == 1, cen[0]      # the default handle: the short form ...
+    assert cen[1]["l0_fused"] == 4 and cen[1]["sv"] == 1 and cen[1]["dg"] == 0, cen[1]      # ... PLAN_GENERIC_QC: the general one
     T.states_close(O.POSE3, out[0][0], out[0][1], out[1][0], out[1][1], 1e-9)
     assert np.array_equal(out[1][0], out[2][0]) and np.array_equal(out[1][1], out[2][1])
 
@@ -122,6 +129,7 @@ def test_set_qc_after_compile_reaches_the_structured_path():
     both must see the new Qc (same problem on the oracle)."""
     orc, dev, c = T.build_pair(O.POSE3, 700, seed=21, vel_priors=False)
     assert dev.plan_info()["structured_gp"] == 1
+    dev.launch_census()
     dev.iterate_gn(); orc.iterate_gn()
     Qc = np.diag([0.05, 0.02, 0.03, 0.04, 0.06, 0.01])
     Qc[0, 2] = Qc[2, 0] = 0.004
@@ -132,6 +140,16 @@ def test_set_qc_after_compile_reaches_the_structured_path():
         assert abs(s0.error_after - s1.error_after) <= 1e-9 * max(1.0, abs(s0.error_after))
     (x0, v0), (x1, v1) = orc.get_states(), dev.get_states()
     T.states_close(O.POSE3, x0, v0, x1, v1, 1e-9)
+    # the form: both Qc so far have an off-diagonal entry (the general assembly); a diagonal one must flip the launch to the short form
+    cen = dev.launch_census()
+    assert cen["l0_fused"] == 4 and cen["sv"] == 1 and cen["dg"] == 0, cen
+    Qd = np.diag([0.05, 0.02, 0.03, 0.04, 0.06, 0.01])
+    dev.set_qc(Qd); orc.set_qc(Qd)
+    _, s0 = orc.iterate_gn()
+    _, s1 = dev.iterate_gn()
+    cen = dev.launch_census()
+    assert cen["l0_fused"] == 1 and cen["sv"] == 1 and cen["dg"] == 1, cen
+    assert abs(s0.error_after - s1.error_after) <= 1e-9 * max(1.0, abs(s0.error_after))
 
 
 def test_pose3_levenberg_marquardt_through_rows_kernel():

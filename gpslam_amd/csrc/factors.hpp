@@ -254,7 +254,8 @@ template <typename S> GD JrK<S> jr_coefs_smooth(V3<S> w) {
     const S th = sqrt(u);
     const S s = sin(th), co = cos(th);
     const S t3 = u * th, t4 = u * u, t5 = t4 * th;
-    k.c = S(1.0) / u - (S(1.0) + co) / (S(2.0) * th * s);
+    // (1 + cos th) / sin th = cot(th / 2): float's 1 + cos th is all rounding towards th = pi
+    k.c = S(1.0) / u - cos(S(0.5) * th) / (S(2.0) * th * sin(S(0.5) * th));
     k.qa = (th - s) / t3;
     k.qb = (S(1.0) - S(0.5) * u - co) / t4;
     k.qc = S(-0.5) * (k.qb - S(3.0) * (th - s - t3 / S(6.0)) / t5);

@@ -115,9 +115,10 @@ template <typename T> struct IsF64 { static constexpr bool v = false; };
 template <> struct IsF64<double> { static constexpr bool v = true; };
 
 // Inputs (states, landmarks, factor parameters) are ALWAYS fp64 in HBM; T is the arithmetic / row-table type.  In the
-// fp32 mode (GPSLAM_FP32) the Jacobian rows, the normal equations and the solver run with T = float, while the residual
-// is evaluated by the T = double error pass of the same kernels, which then also deposits its whitened error as the
-// fp32 right-hand side (rowE32): fp32 linear algebra + fp64 residual = iterative refinement through the Gauss-Newton loop.
+// fp32 mode (GPSLAM_FP32) the Jacobian rows are computed and stored with T = float; the normal equations and the solver stay
+// double (api_impl.inc: Real), and the residual is evaluated by the T = double error pass of the same kernels, which then also
+// deposits its whitened error, rounded once, as the row tables' right-hand side (rowE32): fp32 Jacobians + fp64 residual =
+// iterative refinement through the Gauss-Newton loop.
 // Pending update (round 5).  Inside a fixed-count Gauss-Newton run the retraction of iteration k is folded into the linearisation
 // of iteration k + 1: K1 reads a state, applies the update the previous solve left in the level-0 solution array, linearises at the
 // updated values, and the thread that OWNS the state (the GP prior whose left state it is; the last state rides with the last

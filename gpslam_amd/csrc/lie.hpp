@@ -284,12 +284,61 @@ GD M3<float> se3_Q(V3<float> w, V3<float> rho) {
   const M3<float> XY = X * Y, YX = Y * X, XYX = X * YX;
   return -0.5f * Y + a * (XY + YX - XYX) + b * (X * XY + YX * X - 3.f * XYX) + c * (XYX * X + X * XYX);
 }
+// ((1 + cos th) / sin th as cot(th / 2): towards th = pi float's 1 + cos th is all rounding)
 GD M3<float> so3_jrinv(V3<float> w) {
   const float u = dot(w, w);
   const float c = (u < 0.25f) ? 1.f / 12 + u * (1.f / 720 + u * (1.f / 30240 + u * (1.f / 1209600)))
-                              : 1.f / u - (1.f + cos(sqrt(u))) / (2.f * sqrt(u) * sin(sqrt(u)));
+                              : 1.f / u - cos(0.5f * sqrt(u)) / (2.f * sqrt(u) * sin(0.5f * sqrt(u)));
   const M3<float> X = skew(w);
   return M3<float>::identity() + 0.5f * X + c * (X * X);
+}
+// fp32 coefficients as functions of u = th^2: sin th / th, (1 - cos th) / th^2, (th - sin th) / th^3 -- series below u = 0.25, above it
+// closed forms that subtract nothing from 1 (float's 1 - cos th is all rounding below th = 3e-4 and carries two digits at 0.01)
+GD float f32_sinc(float u) {
+  return (u < 0.25f) ? 1.f - u * (1.f / 6 - u * (1.f / 120 - u * (1.f / 5040 - u * (1.f / 362880)))) : sin(sqrt(u)) / sqrt(u);
+}
+GD float f32_omc(float u) {
+  if (u < 0.25f) return 0.5f - u * (1.f / 24 - u * (1.f / 720 - u * (1.f / 40320 - u * (1.f / 3628800))));
+  const float h = sin(0.5f * sqrt(u));
+  return 2.f * h * h / u;
+}
+GD float f32_tms(float u) {
+  if (u < 0.25f) return 1.f / 6 - u * (1.f / 120 - u * (1.f / 5040 - u * (1.f / 362880 - u * (1.f / 39916800))));
+  const float th = sqrt(u);
+  return (th - sin(th)) / (u * th);
+}
+// fp32 right Jacobian: I - (1 - cos th) / th^2 X + (th - sin th) / th^3 X^2, no threshold (the template's th^2 <= eps branch returns I
+// up to th = 3.4e-4 in float, dropping X / 2, and its closed forms cancel above)
+GD M3<float> so3_jr(V3<float> w) {
+  const float u = dot(w, w);
+  const M3<float> X = skew(w);
+  return M3<float>::identity() - f32_omc(u) * X + f32_tms(u) * (X * X);
+}
+// fp32 SO3 Logmap.  The reference's th = acos((tr - 1) / 2), th / (2 sin th) loses half of float's digits in acos towards th = pi, and
+// the sine of that angle loses all of them (6% at pi - 1e-3).  Here th = atan2(|v|, tr - 1), v = 2 sin(th) a the antisymmetric part
+// of R; the axis a from v below 2 pi / 3, and above, where v vanishes, from the symmetric part R + R^T = 2 cos th I + 2 (1 - cos th) a a^T.
+GD V3<float> so3_log(const M3<float> &R) {
+  const V3<float> v = {R.m[7] - R.m[5], R.m[2] - R.m[6], R.m[3] - R.m[1]};
+  const float tr = R.m[0] + R.m[4] + R.m[8];
+  const float s2 = sqrt(dot(v, v));
+  const float th = atan2(s2, tr - 1.f);
+  if (tr > -0.5f) {
+    const float x2 = 0.25f * s2 * s2;      // sin^2 th; th / sin th = asin(x) / x by its series below th = 0.25
+    const float m = (x2 < 0.06f) ? 1.f + x2 * (1.f / 6 + x2 * (3.f / 40 + x2 * (15.f / 336 + x2 * (105.f / 3456 + x2 * (945.f / 42240)))))
+                                 : 2.f * th / s2;
+    return (0.5f * m) * v;
+  }
+  const float co = 0.5f * (tr - 1.f), q = 1.f / (1.f - co);
+  if (R.m[0] >= R.m[4] && R.m[0] >= R.m[8]) {
+    const float a = ::copysignf(sqrt(fmax((R.m[0] - co) * q, 0.f)), v.x), r = 0.5f * q / a;
+    return {th * a, th * r * (R.m[1] + R.m[3]), th * r * (R.m[2] + R.m[6])};
+  }
+  if (R.m[4] >= R.m[8]) {
+    const float a = ::copysignf(sqrt(fmax((R.m[4] - co) * q, 0.f)), v.y), r = 0.5f * q / a;
+    return {th * r * (R.m[1] + R.m[3]), th * a, th * r * (R.m[5] + R.m[7])};
+  }
+  const float a = ::copysignf(sqrt(fmax((R.m[8] - co) * q, 0.f)), v.z), r = 0.5f * q / a;
+  return {th * r * (R.m[2] + R.m[6]), th * r * (R.m[5] + R.m[7]), th * a};
 }
 
 // rightJacobianPose3inv (Pose3utils.cpp:192-200) = Pose3::LogmapDerivative in terms of xi
@@ -326,6 +375,20 @@ template <typename T> GD SE3<T> se3_exp(V6<T> xi) {
     return {R, (T(1) / th2) * (wxv - R * wxv + tpar)};
   }
   return {R, xi.v};
+}
+
+// fp32 Expmaps: R = I + sin th / th X + (1 - cos th) / th^2 X^2 and t = (I + (1 - cos th) / th^2 X + (th - sin th) / th^3 X^2) v with the
+// coefficients above.  The templates' th^2 > eps branch is th > 3.4e-4 in float: below it they return t = v, dropping w x v / 2 (1e-5 of
+// |v| at 3e-5 rad, which Ad(Exp(xi)^-1) carries into the interpolator's H1), and just above it (w x v - R (w x v)) / th^2 cancels.
+GD M3<float> so3_exp(V3<float> w) {
+  const float u = dot(w, w);
+  const M3<float> X = skew(w);
+  return M3<float>::identity() + f32_sinc(u) * X + f32_omc(u) * (X * X);
+}
+GD SE3<float> se3_exp(V6<float> xi) {
+  const float u = dot(xi.w, xi.w);
+  const V3<float> wv = cross(xi.w, xi.v);
+  return {so3_exp(xi.w), xi.v + f32_omc(u) * wv + f32_tms(u) * cross(xi.w, wv)};
 }
 
 // ------------------------------------------------------------------ SE(2), stored as (x, y, theta)
@@ -396,6 +459,35 @@ template <typename T> GD M3<T> se2_dlog(V3<T> v) {
              v.y * ai - T(0.5) * v.x - v.y * hc, T(0), T(0), T(1)}};
   }
   return M3<T>::identity() + T(0.5) * se2_ad(v);
+}
+
+// fp32: Pose2's maps with the coefficients above.  The reference's forms divide differences of nearly equal numbers by the angle --
+// 1 - sin(a) / a, 1 / a - cot(a / 2) / 2, (c - 1)^2 + s^2 -- which in float leaves three to four digits at the 0.01 .. 0.1 rad of
+// consecutive states; written in sin a / a, (1 - cos a) / a^2, (a - sin a) / a^3 and k = (1 - (a / 2) cot(a / 2)) / a^2 nothing cancels,
+// and the thresholds 1e-10 / 1e-5 play no role.
+GD float f32_hck(float u) {
+  if (u < 0.25f) return 1.f / 12 + u * (1.f / 720 + u * (1.f / 30240 + u * (1.f / 1209600)));
+  const float a = sqrt(u);
+  return (1.f - 0.5f * a / tan(0.5f * a)) / u;
+}
+GD V3<float> se2_log(const SE2<float> &g) {
+  const float w = wrap_pi(g.th);
+  const float hc = 1.f - w * w * f32_hck(w * w);     // (w / 2) cot(w / 2)
+  return {hc * g.x + 0.5f * w * g.y, hc * g.y - 0.5f * w * g.x, w};
+}
+GD SE2<float> se2_exp(V3<float> xi) {
+  const float w = xi.z, a = f32_sinc(w * w), b = w * f32_omc(w * w);
+  return {a * xi.x - b * xi.y, b * xi.x + a * xi.y, wrap_pi(w)};
+}
+GD M3<float> se2_dexp(V3<float> v) {
+  const float al = v.z, u = al * al;
+  const float sZ = f32_sinc(u), b = f32_omc(u), c1Z = -al * b, q = al * f32_tms(u);
+  return {{sZ, -c1Z, v.x * q - v.y * b, c1Z, sZ, v.x * b + v.y * q, 0.f, 0.f, 1.f}};
+}
+GD M3<float> se2_dlog(V3<float> v) {
+  const float al = v.z, u = al * al;
+  const float k = f32_hck(u), hc = 1.f - u * k, q = al * k;
+  return {{hc, -0.5f * al, v.x * q + 0.5f * v.y, 0.5f * al, hc, v.y * q - 0.5f * v.x, 0.f, 0.f, 1.f}};
 }
 
 }  // namespace gps

@@ -4,6 +4,7 @@
 //   2. the fp32 coefficients are accurate to fp32 rounding where the closed forms in fp32 are not
 //   3. the exact derivative d(Jr^-1(xi) x)/d xi (forward-mode duals) == the reference's central difference
 //      (jacobianMethodNumercialDiff, Pose3utils.cpp:167-179) evaluated in fp64
+//   4. the fp32 overloads of so3_log, so3_jr, so3_exp, se3_exp and the Pose2 maps == their fp64 templates, from th = 0 to pi - 1e-3
 #include <cmath>
 #include <cstdio>
 #include <random>
@@ -97,6 +98,58 @@ int main() {
   CHECK(worst64 < 1e-7, "fp64 duals differ from the yardstick by %.3e", worst64);
   CHECK(worst32 < 5e-6, "fp32 exact derivative differs by %.3e", worst32);
   CHECK(worst_ref_large < 1e-7, "reference-style difference at larger angles differs by %.3e", worst_ref_large);
+  // 4. the fp32 overloads of the group maps (lie.hpp) against their fp64 templates: float rounding of O(1) entries at every angle,
+  //    where the templates instantiated for float lose digits (1 - cos th, 1 - sin(a) / a, acos towards pi, th^2 <= eps -> I)
+  {
+    double wl = 0.0, wj = 0.0, w2 = 0.0, we = 0.0;
+    const double PI = 3.14159265358979323846;
+    for (double th : {0.0, 1e-9, 1e-6, 3e-5, 3.4e-4, 1e-3, 0.01, 0.1, 0.24, 0.26, 0.49, 0.51, 1.0, 2.0, 2.09, 2.1, 3.0, PI - 1e-3}) {
+      for (int rep = 0; rep < 6; rep++) {
+        double a[3] = {nd(rng), nd(rng), nd(rng)};
+        if (rep < 3) { a[0] = a[1] = a[2] = 1e-3; a[rep] = 1.0; }       // near a coordinate axis: each branch of the axis recovery
+        const double n = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        const V3<double> w = {th * a[0] / n, th * a[1] / n, th * a[2] / n};
+        const M3<double> R = so3_exp(w);
+        M3<float> Rf;
+        for (int q = 0; q < 9; q++) Rf.m[q] = (float)R.m[q];
+        const V3<float> lf = so3_log(Rf);
+        wl = std::fmax(wl, std::fmax(std::fabs(lf.x - w.x), std::fmax(std::fabs(lf.y - w.y), std::fabs(lf.z - w.z))));
+        const M3<float> Ef = so3_exp(V3<float>{(float)w.x, (float)w.y, (float)w.z});
+        for (int q = 0; q < 9; q++) we = std::fmax(we, std::fabs(Ef.m[q] - R.m[q]));
+        const V6<double> xi = {w, {nd(rng), nd(rng), nd(rng)}};
+        const SE3<double> g = se3_exp(xi);
+        const SE3<float> gf = se3_exp(V6<float>{{(float)w.x, (float)w.y, (float)w.z}, {(float)xi.v.x, (float)xi.v.y, (float)xi.v.z}});
+        const double sc = 1.0 + std::fabs(xi.v.x) + std::fabs(xi.v.y) + std::fabs(xi.v.z);
+        we = std::fmax(we, std::fmax(std::fabs(gf.t.x - g.t.x), std::fmax(std::fabs(gf.t.y - g.t.y), std::fabs(gf.t.z - g.t.z))) / sc);
+        if (th >= 1e-6) {
+          const M3<double> J = so3_jr(w);
+          const M3<float> Jf = so3_jr(V3<float>{(float)w.x, (float)w.y, (float)w.z});
+          for (int q = 0; q < 9; q++) wj = std::fmax(wj, std::fabs(Jf.m[q] - J.m[q]));
+        }
+      }
+    }
+    for (double al : {1e-4, 1e-3, 0.01, 0.03, 0.1, 0.3, 0.49, 0.51, 1.0, 2.0, 3.0, -0.03, -2.5}) {
+      for (int rep = 0; rep < 5; rep++) {
+        const V3<double> v = {nd(rng), nd(rng), al};
+        const V3<float> vf = {(float)v.x, (float)v.y, (float)v.z};
+        const double sc = 1.0 + std::fabs(v.x) + std::fabs(v.y);
+        const M3<double> De = se2_dexp(v), Dl = se2_dlog(v);
+        const M3<float> Def = se2_dexp(vf), Dlf = se2_dlog(vf);
+        for (int q = 0; q < 9; q++) w2 = std::fmax(w2, std::fmax(std::fabs(Def.m[q] - De.m[q]), std::fabs(Dlf.m[q] - Dl.m[q])) / sc);
+        const SE2<double> g = se2_exp(v);
+        const SE2<float> gf = se2_exp(vf);
+        w2 = std::fmax(w2, std::fmax(std::fabs(gf.x - g.x), std::fmax(std::fabs(gf.y - g.y), std::fabs(gf.th - g.th))) / sc);
+        const V3<double> l = se2_log(g);
+        const V3<float> lf = se2_log(SE2<float>{(float)g.x, (float)g.y, (float)g.th});
+        w2 = std::fmax(w2, std::fmax(std::fabs(lf.x - l.x), std::fmax(std::fabs(lf.y - l.y), std::fabs(lf.z - l.z))) / sc);
+      }
+    }
+    std::printf("fp32 group maps vs fp64: so3_log %.2e, so3_jr %.2e, so3 / se3 exp %.2e, se2 exp / log / dexp / dlog %.2e\n", wl, wj, we, w2);
+    CHECK(we < 1e-6, "fp32 so3_exp / se3_exp differ by %.3e", we);
+    CHECK(wl < 1e-6, "fp32 so3_log differs by %.3e", wl);
+    CHECK(wj < 1e-6, "fp32 so3_jr differs by %.3e", wj);
+    CHECK(w2 < 1e-6, "fp32 se2 maps differ by %.3e", w2);
+  }
   if (fails == 0) std::printf("all fp32 math tests passed\n");
   return fails ? 1 : 0;
 }

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""50-digit pins of the SE(3) GP factors' Jacobians, small relative rotations included: tests/golden/se3_jac_pins.json.
+"""50-digit pins of the SE(3) GP factors' Jacobians, small relative rotations included: tests/golden/se3_jac_pins.json
+and, for `H_exact`, tests/golden/se3_jac_pins_exact.json.
 
 The reference's formulas (restated once in tests/se3_bounds.py, generic in the number type) are evaluated in mpmath at
 50 digits, with the reference's branches and constants:
@@ -8,9 +9,10 @@ The reference's formulas (restated once in tests/se3_bounds.py, generic in the n
                                                           gpslam/gp/GaussianProcessInterpolatorPose3.h:57-105
 Each case records its inputs, `e` (the error, or the interpolated pose), `H_ref` (what a rounding-free reference
 returns: the analytic blocks exactly, the jacobianMethodNumercialDiff block -- Pose3utils.cpp:167-179 -- as the h = 1e-6
-quotient with the |th| > 1e-5 branch of rightJacobianPose3Q, Pose3utils.cpp:92-113), `H_ref_minus_exact` (H_ref minus the
-derivative of the same e, central difference at h = 1e-20 under the right perturbations p Exp(d), v + d) and theta = |Log(T1^-1 T2)| of
-the rotation part.  For 5e-6 < th < 2e-3 a case also holds `e64` / `H_ref64`: the same with rightJacobianPose3Q's
+quotient with the |th| > 1e-5 branch of rightJacobianPose3Q, Pose3utils.cpp:92-113), `H_exact` (the derivative of the same
+e, central difference at h = 1e-20 under the right perturbations p Exp(d), v + d, in full float64 precision: the reference
+of the fp32 rows, which do not restate the quotient -- tests/test_gpu_fp32_rows.py), `H_ref_minus_exact` (H_ref minus it, to
+three digits) and theta = |Log(T1^-1 T2)| of the rotation part.  For 5e-6 < th < 2e-3 a case also holds `e64` / `H_ref64`: the same with rightJacobianPose3Q's
 closed-form coefficients as float64 forms them (tests/se3_bounds.py, float64_coefficients), since there those coefficients
 are all rounding and their error is as large as the branch's jump.  Whenever a quotient's rotational +-h straddles th = 1e-5, the perturbed angles stay at least 1e-12
 away from it (checked below), so float64 rounding never decides the branch.
@@ -138,7 +140,7 @@ def gp_case(rng, theta, rho_scale, axis=None, note=""):
     case = dict(family="gp_prior_pose3", src="gpslam/gp/GaussianProcessPriorPose3.h:60-98; Pose3utils.cpp:92-113,167-179",
                 note=note, p1=p1, v1=v1, p2=p2, v2=v2, dt=DT, theta=float(th), straddles=bool(straddles(r)),
                 rho=float(mp.sqrt(sum(x * x for x in r[3:]))),
-                e=f64(e), H_ref=[fmat(h) for h in H], H_ref_minus_exact=diff3(H, Hx))
+                e=f64(e), H_ref=[fmat(h) for h in H], H_ref_minus_exact=diff3(H, Hx), H_exact=[fmat(h) for h in Hx])
     return model64(case, lambda: B.gp_prior(mpv(p1), mpv(v1), mpv(p2), mpv(v2), mp.mpf(DT)))
 
 
@@ -200,7 +202,7 @@ def interp_case(rng, theta, rho_scale, tau_frac, axis=None, note=""):
     case = dict(family="interpolate_pose3", src="gpslam/gp/GaussianProcessInterpolatorPose3.h:57-105; Pose3utils.cpp:92-113,167-179",
                 note=note, p1=p1, v1=v1, p2=p2, v2=v2, dt=DT, tau=tau, theta=float(th), straddles=bool(straddles(r)),
                 rho=float(mp.sqrt(sum(x * x for x in r[3:]))),
-                e=f64(out), H_ref=[fmat(h) for h in H], H_ref_minus_exact=diff3(H, Hx))
+                e=f64(out), H_ref=[fmat(h) for h in H], H_ref_minus_exact=diff3(H, Hx), H_exact=[fmat(h) for h in Hx])
     return model64(case, lambda: B.interpolate(Lam, Psi, mpv(p1), mpv(v1), mpv(p2), mpv(v2)))
 
 
@@ -221,9 +223,20 @@ def main():
     assert any(c["straddles"] for c in gp) and any(c["straddles"] for c in it)
     pins = dict(note="mpmath %s, %d digits; generated by tests/golden/make_se3_jac_pins.py" % (mp.__version__, mp.mp.dps),
                 h_fd=B.H_FD, Qc=QC, gp_prior_pose3=gp, interpolate_pose3=it)
+    # `H_exact` goes to a file of its own, one case per line, so that se3_jac_pins.json stays byte for byte what it was
+    # (a block that equals the case's H_ref block bit for bit -- the GP prior's analytic H2 and H4 -- is written as null)
+    exact = {fam: [[None if hx == h else hx for hx, h in zip(c.pop("H_exact"), c["H_ref"])] for c in pins[fam]]
+             for fam in ("gp_prior_pose3", "interpolate_pose3")}
     path = os.path.join(HERE, "se3_jac_pins.json")
     with open(path, "w") as f:
         json.dump(pins, f, separators=(",", ":"))
+    print("wrote", path, os.path.getsize(path), "bytes")
+    path = os.path.join(HERE, "se3_jac_pins_exact.json")
+    with open(path, "w") as f:
+        f.write('{"note":"H_exact of every case of se3_jac_pins.json, in its order; generated with it; null: the block equals that of H_ref bit for bit"')
+        for fam, hs in exact.items():
+            f.write(',\n"%s":[\n%s\n]' % (fam, ",\n".join(json.dumps(h, separators=(",", ":")) for h in hs)))
+        f.write("}\n")
     print("wrote", path, os.path.getsize(path), "bytes")
 
 

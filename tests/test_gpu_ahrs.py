@@ -25,9 +25,9 @@ def hip_chain(**kw):
     return g.ChainSolver(g.ROT3_BIAS, **kw)
 
 
-def random_pair(N=96, seed=5, coriolis=None):
+def random_pair(N=96, seed=5, coriolis=None, extra_makers=()):
     """random attitude trajectory with biases, pre-integrations of a few noisy gyro samples per interval, accelerometer
-    directions at random times: every factor kind of the recipe, on the oracle and on the device"""
+    directions at random times: every factor kind of the recipe, on the oracle, on the device and on whatever extra_makers make"""
     rng = np.random.default_rng(seed)
     pose, vel = np.zeros((N, 12)), np.zeros((N, 6))
     R = ahrs.rot_from_ypr(0.3, -0.2, 0.1)
@@ -73,7 +73,8 @@ def random_pair(N=96, seed=5, coriolis=None):
         s.compile()
         return s
 
-    return fill(O.Chain(O.ROT3_BIAS)), fill(hip_chain()), N, M
+    pair = fill(O.Chain(O.ROT3_BIAS)), fill(hip_chain()), N, M
+    return pair + ([fill(make()) for make in extra_makers],) if extra_makers else pair
 
 
 def rot_states_close(a, b, tol):

@@ -1,4 +1,4 @@
-"""The fp32 mode (GPSLAM_FP32): fp32 Jacobian rows, normal equations and solver, fp64 states and fp64 residual.
+"""The fp32 mode (GPSLAM_FP32): fp32 Jacobian rows; fp64 normal equations and solver, fp64 states and fp64 residual.
 north_star: final state vector within 1e-5 relative of the fp64 reference -- here the CPU oracle (fp64)."""
 import numpy as np
 import pytest

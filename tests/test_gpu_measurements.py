@@ -41,14 +41,13 @@ def true_range(kind, pose, land, sensor=None):
     return float(np.hypot(land[0] - pose[0], land[1] - pose[1]))
 
 
-def build_meas_pair(kind, N=48, seed=3, sensor=False, chart=None, extra_makers=(), cov_hook=None):
-    """cov_hook(solver, MEAS kind, count): called after each batch of measurement factors (e.g. to give them full covariances)"""
+def meas_graph(kind, N=48, seed=3, sensor=False, cov_hook=None, motion=0.3):
+    """(feed, c): feed(solver) gives any solver-like object the graph of build_meas_pair and compiles it; c: the random_chain behind it.
+    cov_hook(solver, MEAS kind, count): called after each batch of measurement factors (e.g. to give them full covariances)"""
     hook = cov_hook if cov_hook is not None else (lambda s, k, n: None)
     rng = np.random.default_rng(seed + 1000)
     d, ld = O.TANGENT_DIM[kind], LD[kind]
-    if chart is None:
-        chart = O.CHART_FIRST_ORDER if kind == O.POSE2 else O.CHART_EXPMAP
-    c = random_chain(kind, N, seed, noise=0.03)
+    c = random_chain(kind, N, seed, motion=motion, noise=0.03)
     Qc = np.diag(0.01 + 0.02 * rng.random(d))
     L = 3 if ld else 0
     lands_true = rng.uniform(-6, 6, (L, ld)) if L else None
@@ -72,9 +71,8 @@ def build_meas_pair(kind, N=48, seed=3, sensor=False, chart=None, extra_makers=(
         ulm = rng.integers(0, L, size=len(uidx)).astype(np.int32)
         uz = np.array([true_range(kind, c["truth_pose"][i], lands_true[l]) for i, l in zip(uidx, ulm)])
         specs.update(uidx=uidx, ulm=ulm, uz=uz + 0.01 * rng.standard_normal(len(uz)))
-    solvers = []
-    for make in (lambda: O.Chain(kind, chart, ld), lambda: gpu().ChainSolver(kind, chart, ld)) + tuple(extra_makers):
-        s = make()
+
+    def feed(s):
         s.set_qc(Qc)
         s.set_states(c["pose"], c["vel"])
         if L:
@@ -133,7 +131,17 @@ def build_meas_pair(kind, N=48, seed=3, sensor=False, chart=None, extra_makers=(
             s.add_bearing_range(specs["bidx"], specs["blm"], specs["bear"], specs["brng"], np.full((len(specs["bidx"]), 2), 0.05))
             hook(s, 5, len(specs["bidx"]))
         s.compile()
-        solvers.append(s)
+        return s
+    return feed, c
+
+
+def build_meas_pair(kind, N=48, seed=3, sensor=False, chart=None, extra_makers=(), cov_hook=None, motion=0.3):
+    """The same graph on the oracle, on the device and on whatever extra_makers make."""
+    ld = LD[kind]
+    if chart is None:
+        chart = O.CHART_FIRST_ORDER if kind == O.POSE2 else O.CHART_EXPMAP
+    feed, c = meas_graph(kind, N, seed, sensor, cov_hook, motion)
+    solvers = [feed(make()) for make in (lambda: O.Chain(kind, chart, ld), lambda: gpu().ChainSolver(kind, chart, ld)) + tuple(extra_makers)]
     if extra_makers:
         return solvers[0], solvers[1], c, solvers[2:]
     return solvers[0], solvers[1], c

@@ -11,8 +11,8 @@ K2 = [50.0, 50.0, 0.7, 40.0, 30.0]          # a skewed calibration exercises the
 KDS2 = K2 + [0.08, -0.03, 0.004, -0.006]    # gtsam::Cal3DS2: + radial k1, k2 and tangential p1, p2 (round 4)
 
 
-def build_pair(N=24, seed=4, sensor=True, behind=False, K2=K2):
-    c = random_chain(O.POSE3, N, seed, motion=0.2, noise=0.02)
+def build_pair(N=24, seed=4, sensor=True, behind=False, K2=K2, motion=0.2, makers=None):
+    c = random_chain(O.POSE3, N, seed, motion=motion, noise=0.02)
     rng = np.random.default_rng(seed + 9)
     Qc = np.diag(0.01 + 0.02 * rng.random(6))
     body_T_sensor = O.pose3((0.1, -0.2, 0.15), (0.3, 0.6, -0.7)) if sensor else None
@@ -48,7 +48,7 @@ def build_pair(N=24, seed=4, sensor=True, behind=False, K2=K2):
     if behind:
         lm_init[0] = c["pose"][left[0], 9:12] - 5.0 * c["pose"][left[0], :9].reshape(3, 3)[:, 2]   # behind the first camera
     solvers = []
-    for make in (lambda: O.Chain(O.POSE3, landmark_dim=3), lambda: gpu().ChainSolver(O.POSE3, landmark_dim=3)):
+    for make in makers or (lambda: O.Chain(O.POSE3, landmark_dim=3), lambda: gpu().ChainSolver(O.POSE3, landmark_dim=3)):
         s = make()
         s.set_qc(Qc)
         s.set_states(c["pose"], c["vel"])
@@ -61,6 +61,8 @@ def build_pair(N=24, seed=4, sensor=True, behind=False, K2=K2):
         s.add_interp_projection(left, lmi, np.array(meas), np.full((len(left), 2), 0.1), dt, tau, K2, body_T_sensor)
         s.compile()
         solvers.append(s)
+    if makers:          # the caller's own solver-like objects instead of the pair
+        return solvers, len(left)
     return solvers[0], solvers[1], len(left)
 
 

@@ -18,7 +18,7 @@ LIB = os.path.join(LIBDIR, "libgpslam_hip.so")
 # optimiser (both are api_impl.inc -- launchers, compile() -- followed by api_iterate.inc -- the iteration driver; round 3: they
 # were one 3.5-minute translation unit), the upper solver levels, and the marginals (gtsam::Marginals: selected inversion of the chain)
 SOURCES = ["api.hip", "api_impl64.hip", "api_impl32.hip", "upper.hip", "marginals.hip"]
-HEADERS = ["kernels.hpp", "factors.hpp", "lie.hpp", "devbuf.hpp", "fatsep.hpp", "dpp.hpp", "cr_step.hpp", "cr_quad.hpp", "upper.hpp", "api_common.hpp",
+HEADERS = ["kernels.hpp", "factors.hpp", "lie.hpp", "devbuf.hpp", "fatsep.hpp", "dpp.hpp", "cr_step.hpp", "cr_quad.hpp", "upper.hpp", "api_common.hpp", "robust.hpp",
            "api_decl.inc", os.path.join("..", "..", "include", "gpslam_hip.h")]
 # what each translation unit includes (an edit to upper.hip does not recompile the others)
 IMPL = HEADERS + ["api_impl.inc", "api_iterate.inc"]

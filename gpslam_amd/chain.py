@@ -13,6 +13,9 @@ from . import build as _build
 LINEAR2, LINEAR3, POSE2, POSE3, ROT3, ROT3_BIAS = 0, 1, 2, 3, 4, 5
 CHART_EXPMAP, CHART_FIRST_ORDER = 0, 1
 FP64, FP32 = 0, 1
+# noiseModel::Robust: GPSLAM_ROBUST_* (mEstimator::Huber, Cauchy, Tukey, GemanMcClure, Welsh, Fair) and GPSLAM_MEAS_* of include/gpslam_hip.h
+ROBUST_NONE, ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY, ROBUST_GEMAN_MCCLURE, ROBUST_WELSH, ROBUST_FAIR = 0, 1, 2, 3, 4, 5, 6
+MEAS_INTERP_RANGE, MEAS_RANGE, MEAS_INTERP_ATTITUDE, MEAS_INTERP_GPS, MEAS_ODOMETRY2D, MEAS_BEARING_RANGE, MEAS_INTERP_PROJECTION, MEAS_AHRS = range(8)
 # gpslam_hip_config_v2.plan: kernel families compile() is told to use instead of its default choice (include/gpslam_hip.h)
 PLAN_UNFUSED_LEVEL0, PLAN_COLUMN_LEVEL0, PLAN_LEVELS_OF_FOUR, PLAN_FS_TWO_LAUNCHES, PLAN_GP_ROWS, PLAN_GENERIC_QC, PLAN_MEAS_ROWS, PLAN_SEPARATE_RETRACT = 1, 2, 4, 8, 16, 32, 64, 128
 # Test harness hook of this PYTHON mirror (the library itself reads no environment): plan bits OR-ed into every ChainSolver a
@@ -44,6 +47,8 @@ ABI_SYMBOLS = [
     "gpslam_hip_add_between_pairs", "gpslam_hip_set_level0_stamps",
     "gpslam_hip_marginals", "gpslam_hip_get_marginals", "gpslam_hip_interpolate_covariances",
     "gpslam_hip_launch_census",
+    "gpslam_hip_set_meas_robust", "gpslam_hip_set_between_pairs_robust", "gpslam_hip_get_meas_weights",
+    "gpslam_hip_get_between_pairs_weights", "gpslam_hip_robust_eval",
 ]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
@@ -151,6 +156,15 @@ def lm_decide(s6, lam, lambda_factor=10.0, lambda_upper_bound=1e5, lambda_lower_
     return bool(acc.value), bool(done.value), lam_c.value
 
 
+def robust_eval(loss, k, r):
+    """gpslam_hip_robust_eval (host arithmetic, no GPU): (w(r), rho(r)) of one GPSLAM_ROBUST_* loss with parameter k."""
+    w, rho = C.c_double(0.0), C.c_double(0.0)
+    rc = load_library().gpslam_hip_robust_eval(C.c_int32(int(loss)), C.c_double(k), C.c_double(r), C.byref(w), C.byref(rho))
+    if rc:
+        raise GpslamHipError("robust_eval: %d" % rc)
+    return w.value, rho.value
+
+
 def _f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
@@ -243,6 +257,36 @@ class ChainSolver:
         """noiseModel::Gaussian::Covariance (count x rows x rows) on the most recently added factors of one MEAS_* kind."""
         cov = _f64(cov)
         return self._chk(self.lib.gpslam_hip_set_meas_covariance(self._h, int(kind), cov.shape[0], _p(cov)), "set_meas_covariance")
+
+    def _losses(self, loss, k):
+        loss = _i32(loss).reshape(-1)
+        k = _f64(np.broadcast_to(np.asarray(k, dtype=np.float64), loss.shape))
+        return loss, k
+
+    def set_meas_robust(self, kind, loss, k):
+        """noiseModel::Robust on the most recently added factors of one MEAS_* kind: loss = ROBUST_* per factor, k = its parameter
+        (one per factor, or one for all)."""
+        loss, k = self._losses(loss, k)
+        return self._chk(self.lib.gpslam_hip_set_meas_robust(self._h, int(kind), len(loss), _p(loss), _p(k)), "set_meas_robust")
+
+    def set_between_pairs_robust(self, loss, k):
+        """... on the most recently added loop closures (the non-adjacent pairs of add_between_pairs)."""
+        loss, k = self._losses(loss, k)
+        return self._chk(self.lib.gpslam_hip_set_between_pairs_robust(self._h, len(loss), _p(loss), _p(k)), "set_between_pairs_robust")
+
+    def meas_weights(self, kind, count):
+        """The weights w(r) of the `count` factors of one MEAS_* kind at the current states (1 without a loss)."""
+        w = np.zeros(count)
+        n = self._chk(self.lib.gpslam_hip_get_meas_weights(self._h, int(kind), _p(w)), "get_meas_weights")
+        assert n == count, (n, count)
+        return w
+
+    def between_pairs_weights(self, count):
+        """The weights w(r) of the `count` loop closures at the current states."""
+        w = np.zeros(count)
+        n = self._chk(self.lib.gpslam_hip_get_between_pairs_weights(self._h, _p(w)), "get_between_pairs_weights")
+        assert n == count, (n, count)
+        return w
 
     def add_pose_priors(self, idx, prior, sigmas):
         idx, prior, sigmas = _i32(idx), _f64(prior), _f64(sigmas)

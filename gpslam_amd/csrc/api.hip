@@ -151,7 +151,8 @@ int gpslam_hip_destroy(gpslam_hip_handle *h) {
                     &h->lmrow_state, &h->lmrow_ptr, &h->lm_t, &h->lm_S, &h->lm_dL, &h->lm_chunk_lm, &h->lm_chunk_j0, &h->lm_chunk_j1, &h->lm_chunk_ptr, &h->lm_part, &h->gsave, &h->dvec,
                     &h->halo_add, &h->iface_send, &h->iface_recv, &h->top_blk, &h->top_x, &h->scal, &h->flag,
                     &h->api_e, &h->api_H, &h->gps, &h->gpidx, &h->dU, &h->gsave2, &h->partial2, &h->brec, &h->btwidx,
-                    &h->rowI, &h->irowptr, &h->coll_s, &h->coll_r, &h->d_clo_second, &h->clo_A, &h->clo_Y, &h->simd_cnt};
+                    &h->rowI, &h->irowptr, &h->coll_s, &h->coll_r, &h->d_clo_second, &h->clo_A, &h->clo_Y, &h->simd_cnt,
+                    &h->d_clo_rob, &h->clo_w};
   for (DevBuf *b : bufs) b->release();
   marginals_release(h);
   for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri, &h->clo}) s->release();
@@ -352,6 +353,45 @@ int gpslam_hip_set_meas_covariance(gpslam_hip_handle *h, int32_t kind, int32_t c
   h->marg_ok = false;
   return 0;
 }
+// (loss, k) of `count` factors behind `first` of a table of n entries (created on first use; dropped again when no entry is left)
+static int set_robust(gpslam_hip_handle *h, std::vector<double> &tab, int n, int32_t count, const int32_t *loss, const double *k, const char *who) {
+  if (count < 0 || (count > 0 && (!loss || !k))) return GPSLAM_E_INVALID;
+  if (count > n) return fail(h, GPSLAM_E_INVALID, (std::string(who) + ": more losses than factors").c_str());
+  for (int q = 0; q < count; q++) {
+    if (loss[q] < GPSLAM_ROBUST_NONE || loss[q] > GPSLAM_ROBUST_FAIR) return fail(h, GPSLAM_E_INVALID, (std::string(who) + ": unknown loss (GPSLAM_ROBUST_*)").c_str());
+    if (loss[q] != GPSLAM_ROBUST_NONE && !(k[q] > 0.0 && std::isfinite(k[q]))) return fail(h, GPSLAM_E_INVALID, (std::string(who) + ": the loss parameter k must be positive and finite").c_str());
+  }
+  if (count == 0) return 0;
+  tab.resize((size_t)n * 2, 0.0);
+  for (int q = 0; q < count; q++) {
+    const bool on = loss[q] != GPSLAM_ROBUST_NONE;
+    tab[2 * (size_t)(n - count + q)] = on ? (double)loss[q] : 0.0;
+    tab[2 * (size_t)(n - count + q) + 1] = on ? k[q] : 0.0;
+  }
+  bool any = false;
+  for (size_t q = 0; q < tab.size(); q += 2) any = any || tab[q] != 0.0;
+  if (!any) tab.clear();      // nothing but NONE: the handle is what it was before the first call
+  h->compiled = false;
+  h->marg_ok = false;
+  return 0;
+}
+int gpslam_hip_set_meas_robust(gpslam_hip_handle *h, int32_t kind, int32_t count, const int32_t *loss, const double *k) {
+  if (!h || kind < 0 || kind >= kNumMeasKinds) return GPSLAM_E_INVALID;
+  if (kind == FK_AHRS) return fail(h, GPSLAM_E_UNSUPPORTED, "set_meas_robust: AHRSFactor takes no robust noise model (its rows are whitened by the pre-integrated covariance inside the factor)");
+  MeasSet &s = h->ms[kind];
+  return set_robust(h, s.rob, s.count(), count, loss, k, "set_meas_robust");
+}
+int gpslam_hip_set_between_pairs_robust(gpslam_hip_handle *h, int32_t count, const int32_t *loss, const double *k) {
+  if (!h) return GPSLAM_E_INVALID;
+  return set_robust(h, h->clo_rob, h->clo.count(), count, loss, k, "set_between_pairs_robust");
+}
+int gpslam_hip_robust_eval(int32_t loss, double k, double r, double *w, double *rho) {
+  if (!w || !rho || loss < GPSLAM_ROBUST_NONE || loss > GPSLAM_ROBUST_FAIR) return GPSLAM_E_INVALID;
+  if (!(r >= 0.0) || !std::isfinite(r)) return GPSLAM_E_INVALID;
+  if (loss != GPSLAM_ROBUST_NONE && !(k > 0.0 && std::isfinite(k))) return GPSLAM_E_INVALID;
+  robust_eval(loss, k, r, *w, *rho);
+  return 0;
+}
 int gpslam_hip_add_pose_priors(gpslam_hip_handle *h, int32_t count, const int32_t *idx, const double *prior,
                                const double *sigmas) {
   return h ? add_simple(h, h->pri, h->pd, h->d, count, idx, prior, sigmas, h->N - 1) : GPSLAM_E_INVALID;
@@ -386,6 +426,7 @@ int gpslam_hip_add_between_pairs(gpslam_hip_handle *h, int32_t count, const int3
     h->clo_second.push_back(second[k]);
     h->clo.meas.insert(h->clo.meas.end(), m, m + h->pd);
     h->clo.sig.insert(h->clo.sig.end(), sg, sg + h->d);
+    if (!h->clo_rob.empty()) h->clo_rob.insert(h->clo_rob.end(), 2, 0.0);
   }
   h->compiled = false;
   h->marg_ok = false;
@@ -483,7 +524,9 @@ int gpslam_hip_clear_factors(gpslam_hip_handle *h) {
   h->gp_left.clear(); h->gp_dt.clear(); h->gp_q.clear(); h->gp_Utab.clear(); h->gp_perm.clear(); h->gp_groups.clear();
   for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri, &h->clo}) { s->idx.clear(); s->meas.clear(); s->sig.clear(); }
   h->clo_second.clear();
+  h->clo_rob.clear();
   for (MeasSet &s : h->ms) {
+    s.rob.clear();
     s.idx.clear(); s.lm.clear(); s.meas.clear(); s.sig.clear(); s.dt.clear(); s.tau.clear(); s.aux.clear(); s.aidx.clear(); s.sqi.clear();
     s.any_aux = false;
   }
@@ -694,6 +737,8 @@ int gpslam_hip_linearize_meas(gpslam_hip_handle *h, int32_t kind, double *errors
   return GPS_BY_PRECISION(gpslam_hip_linearize_meas, h, kind, errors, jacobians);
 }
 int gpslam_hip_error(gpslam_hip_handle *h, double *err) { return GPS_BY_PRECISION(gpslam_hip_error, h, err); }
+int gpslam_hip_get_meas_weights(gpslam_hip_handle *h, int32_t kind, double *w) { return GPS_BY_PRECISION(gpslam_hip_get_meas_weights, h, kind, w); }
+int gpslam_hip_get_between_pairs_weights(gpslam_hip_handle *h, double *w) { return GPS_BY_PRECISION(gpslam_hip_get_between_pairs_weights, h, w); }
 int gpslam_hip_iterate_gn(gpslam_hip_handle *h, gpslam_hip_stats *st) {
   invalidates_marginals(h);
   return GPS_BY_PRECISION(gpslam_hip_iterate_gn, h, st);

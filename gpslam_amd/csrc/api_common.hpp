@@ -54,10 +54,14 @@ struct MeasSet {  // measurement factors (kernels.hpp FKind)
   // noiseModel::Gaussian on factors of this kind (gpslam_hip_set_meas_covariance): rows x rows square-root information per
   // factor, diag(1 / sigma) for those that kept their diagonal model; empty: every factor is diagonal
   std::vector<double> sqi;
+  // noiseModel::Robust on factors of this kind (gpslam_hip_set_meas_robust): (loss, k) per factor, (0, 0) for those without a loss;
+  // empty: no factor carries one, and the kernels run as they always did
+  std::vector<double> rob;
   DevBuf d_idx, d_lm, d_meas, d_sig, d_coef, d_row0, d_aux, d_aidx, d_sqi;
+  DevBuf d_rob, d_w;                   // the loss table and the weights w(r) of the last pass that was asked for them
   DevBuf d_irow0;                      // first row of each factor in the table of 16-double interpolated rows (Plan::lines)
   int count() const { return (int)idx.size(); }
-  void release() { d_idx.release(); d_lm.release(); d_meas.release(); d_sig.release(); d_coef.release(); d_row0.release(); d_aux.release(); d_aidx.release(); d_sqi.release(); d_irow0.release(); }
+  void release() { d_idx.release(); d_lm.release(); d_meas.release(); d_sig.release(); d_coef.release(); d_row0.release(); d_aux.release(); d_aidx.release(); d_sqi.release(); d_irow0.release(); d_rob.release(); d_w.release(); }
 };
 
 // Which kernels serve a compiled graph, and in which form.  make_plan() (api_impl.inc) fills one per compile(), once the row layout
@@ -130,6 +134,8 @@ struct gpslam_hip_handle {
   SimpleSet clo;
   std::vector<int32_t> clo_second;
   DevBuf d_clo_second, clo_A, clo_Y;
+  std::vector<double> clo_rob;        // noiseModel::Robust on closures (gpslam_hip_set_between_pairs_robust): as MeasSet::rob
+  DevBuf d_clo_rob, clo_w;
   int nclo = 0, nc = 0;       // closures of the compiled graph, their right-hand-side columns (nclo * d)
   MeasSet ms[kNumMeasKinds];
   // row table
@@ -206,6 +212,7 @@ struct LaunchMode {
   // ... and the fused level-0 launch carries its own start / stop events (hipExtLaunchKernelGGL: the dispatch's own time stamps,
   // what rocprofv3's kernel trace reads) -- events recorded AROUND a launch add their marker packets to it (7 us of 149)
   bool l0_events = false;
+  bool weights = false;       // an error-only pass that also stores every robust factor's weight w(r) (MeasArgs::out_w, CloArgs::out_w)
 };
 
 #define HIPCHK(call)                                                                          \
@@ -323,6 +330,13 @@ template <typename F> void dispatch_fk(int fk, F &&f) {
 // force_sharded = 1 forces the sharded code path on a single segment (self-test of the exchange plumbing)
 bool sharded(const gpslam_hip_handle *h) { return h->cfg.nranks > 1 || h->cfg.force_sharded == 1; }
 bool has_right_rank(const gpslam_hip_handle *h) { return sharded(h) && h->cfg.rank < h->cfg.nranks - 1; }
+
+// some measurement factor or closure carries a loss (noiseModel::Robust)
+bool any_robust(const gpslam_hip_handle *h) {
+  bool any = !h->clo_rob.empty();
+  for (const MeasSet &s : h->ms) any = any || !s.rob.empty();
+  return any;
+}
 
 bool plan_bit(const gpslam_hip_handle *h, int bit) { return (h->cfg.plan & bit) != 0; }   // GPSLAM_PLAN_*
 
@@ -443,6 +457,7 @@ int add_meas(gpslam_hip_handle *h, int fk, int rows, int mw, bool two, bool hasl
       for (int r = 0; r < rows; r++)
         for (int q = 0; q < rows; q++) s.sqi.push_back(r == q ? 1.0 / sig[(size_t)k * rows + r] : 0.0);
   }
+  if (!s.rob.empty()) s.rob.insert(s.rob.end(), (size_t)count * 2, 0.0);   // the kind already has robust factors: the newcomers carry no loss
   if (interp) { s.dt.insert(s.dt.end(), dt, dt + count); s.tau.insert(s.tau.end(), tau, tau + count); }
   {   // this call's body_P_sensor / calibration: find it in (or append it to) the kind's table
     double ent[kMeasAux] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0};

@@ -11,6 +11,8 @@ int gpslam_hip_fs_phase1(gpslam_hip_handle *h, double lambda);
 int gpslam_hip_fs_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st);
 int gpslam_hip_fs_set_top(gpslam_hip_handle *h, int32_t nb_top);
 int gpslam_hip_fs_split_info(gpslam_hip_handle *h, int32_t out4[4]);
+int gpslam_hip_get_between_pairs_weights(gpslam_hip_handle *h, double *w);
+int gpslam_hip_get_meas_weights(gpslam_hip_handle *h, int32_t kind, double *w);
 int gpslam_hip_get_rows(gpslam_hip_handle *h, int32_t *n_rows, double *rowLR, double *rowE, double *rowM, int32_t *rowLm);
 int gpslam_hip_interface_recv(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes);
 int gpslam_hip_interface_send(gpslam_hip_handle *h, void **dev_ptr, size_t *bytes);

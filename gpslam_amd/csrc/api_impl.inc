@@ -72,6 +72,7 @@ CloArgs clo_args(gpslam_hip_handle *h) {
   a.first = h->clo.d_idx.as<int>(); a.second = h->d_clo_second.as<int>();
   a.meas = h->clo.d_meas.as<double>(); a.sig = h->clo.d_sig.as<double>();
   a.A = h->clo_A.as<double>(); a.partial = nullptr;
+  a.rob = h->clo_rob.empty() ? nullptr : h->d_clo_rob.as<double>();
   a.blk = h->lv.empty() ? nullptr : h->lv[0].blk.as<double>();
   a.BS = 2 * h->b * h->b + h->b * h->R; a.B = h->b; a.R = h->R; a.col0 = 1 + h->nl;
   a.gsave = nullptr;
@@ -257,6 +258,8 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
     a.sig = s.d_sig.as<double>(); a.coef = s.d_coef.as<double>();
     a.aux = s.any_aux ? s.d_aux.as<double>() : nullptr; a.aidx = s.any_aux ? s.d_aidx.as<int>() : nullptr;
     a.sqi = s.sqi.empty() ? nullptr : s.d_sqi.as<double>();
+    a.rob = s.rob.empty() ? nullptr : s.d_rob.as<double>();
+    a.out_w = (m.weights && a.rob) ? s.d_w.as<RowT>() : nullptr;
     a.vw = h->vw;
     a.row0 = s.d_row0.as<int>();
     a.rowLR = h->rowLR.as<RowT>(); a.rowE = h->rowE.as<RowT>(); a.rowM = h->rowM.as<RowT>(); a.rowLm = h->rowLm.as<int>();
@@ -292,6 +295,7 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
   if (kIsF64 && h->nclo > 0) {   // loop closures: records [A_i | A_j | r] (Jacobian pass) and their error
     CloArgs a = clo_args(h);
     a.partial = reinterpret_cast<double *>(part + off);   // (RowT == double here)
+    a.out_w = (m.weights && a.rob) ? h->clo_w.as<double>() : nullptr;
     dispatch_mf(h->mf, [&](auto tag) {
       constexpr int MF = decltype(tag)::value;
       if (pass == 0) k_clo_eval<MF, true><<<dim3(1), dim3(128), 0, side>>>(a);
@@ -1148,6 +1152,11 @@ int choose_landmark_path(gpslam_hip_handle *h, bool &segmented) {
     if (h->R > kMaxRhs || 3 * b + h->R > 64)
       return fail(h, GPSLAM_E_UNSUPPORTED, "too many loop closures: 1 + landmarks * landmark_dim + closures * d must not exceed 28 right-hand sides");
   }
+  if (any_robust(h)) {   // noiseModel::Robust: the fp64 factor kernels of one unsharded handle
+    if (!kIsF64) return fail(h, GPSLAM_E_UNSUPPORTED, "robust noise models (set_meas_robust / set_between_pairs_robust) on an fp32 handle");
+    if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "robust noise models (set_meas_robust / set_between_pairs_robust) on a sharded handle");
+    if (h->fs.split) return fail(h, GPSLAM_E_UNSUPPORTED, "robust noise models (set_meas_robust / set_between_pairs_robust) on a piece of a split chain");
+  }
   if (segmented) {
     if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "the segmented landmark elimination splits across GPUs through gpslam_hip_fs_set_split (pieces joined at shared cut states), not through nranks > 1");
     h->R = 1;   // no landmark columns inside the chain solver
@@ -1256,6 +1265,8 @@ int upload_factors(gpslam_hip_handle *h, const RowLayout &lay, int &npart) {
     if ((rc = upload(h, h->d_clo_second, h->clo_second))) return rc;
     HIPCHK(h->clo_A.reserve((size_t)h->nclo * kCloLen(d) * sizeof(double)));
     HIPCHK(h->clo_Y.reserve((size_t)h->nc * (1 + h->nl) * sizeof(double)));
+    if ((rc = upload(h, h->d_clo_rob, h->clo_rob))) return rc;
+    if (!h->clo_rob.empty()) HIPCHK(h->clo_w.reserve((size_t)h->nclo * sizeof(double)));
   }
   // (one k_gp launch per distinct Qc, each rounding its factor count up to whole blocks: at most one extra slot per group)
   npart = nblocks((int)h->gp_left.size(), 128) + gp_ngroups(h) + nblocks(h->pri.count(), 128) + nblocks(h->vpri.count(), 128) +
@@ -1273,6 +1284,8 @@ int upload_factors(gpslam_hip_handle *h, const RowLayout &lay, int &npart) {
     if ((rc = upload(h, s.d_aux, s.aux))) return rc;
     if ((rc = upload(h, s.d_aidx, s.aidx))) return rc;
     if ((rc = upload(h, s.d_sqi, s.sqi))) return rc;
+    if ((rc = upload(h, s.d_rob, s.rob))) return rc;
+    if (!s.rob.empty()) HIPCHK(s.d_w.reserve((size_t)s.count() * sizeof(RowT)));
     npart += nblocks(s.count(), 128);
   }
   const size_t Mrows = (size_t)std::max(h->M, 1);
@@ -1507,7 +1520,8 @@ int make_plan(gpslam_hip_handle *h, const RowLayout &lay) {
       // full-width row that is not a GP prior's belongs to an interpolated GPS factor on an interval with a GP prior (whose
       // record holds X, J and F of that interval); no landmarks (fused), no velocity priors
     const MeasSet &g = h->ms[FK_INTERP_GPS];
-    bool ok = se3 && !plan_bit(h, GPSLAM_PLAN_MEAS_ROWS) && h->vpri.count() == 0 && g.count() > 0;
+    // (a robust GPS factor needs |e| over its three rows before any of them is final: the row form through k_meas, as GPSLAM_PLAN_MEAS_ROWS)
+    bool ok = se3 && !plan_bit(h, GPSLAM_PLAN_MEAS_ROWS) && g.rob.empty() && h->vpri.count() == 0 && g.count() > 0;
     for (int fk = 0; fk < kNumMeasKinds && ok; fk++) ok = (fk == FK_INTERP_GPS) || h->ms[fk].count() == 0;
     for (size_t f = 0; f < g.idx.size() && ok; f++) ok = lay.gpidx[g.idx[f]] >= 0;
     p.lines = ok;
@@ -1636,7 +1650,7 @@ int gpslam_hip_linearize_meas(gpslam_hip_handle *h, int32_t kind, double *errors
   a.sig = s.d_sig.as<double>(); a.coef = s.d_coef.as<double>();
   a.aux = s.any_aux ? s.d_aux.as<double>() : nullptr; a.aidx = s.any_aux ? s.d_aidx.as<int>() : nullptr;
   a.sqi = s.sqi.empty() ? nullptr : s.d_sqi.as<double>();
-  a.vw = h->vw; a.row0 = s.d_row0.as<int>();
+  a.vw = h->vw; a.row0 = s.d_row0.as<int>();     // (a.rob stays null: evaluateError knows no noise model)
   // no row tables: on an fp32 handle (this is impl64 answering for it) they hold floats, and a later solve must not find
   // this call's rows in them either way (ADVICE r3)
   a.rowLR = nullptr; a.rowE = nullptr; a.rowM = nullptr; a.rowLm = nullptr;
@@ -1652,6 +1666,38 @@ int gpslam_hip_linearize_meas(gpslam_hip_handle *h, int32_t kind, double *errors
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(errors, h->api_e.p, (size_t)F * s.rows * sizeof(RowT), hipMemcpyDeviceToHost, h->stream));
   if (jacobians) HIPCHK(hipMemcpyAsync(jacobians, h->api_H.p, (size_t)F * s.rows * W * sizeof(RowT), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return F;
+}
+
+// noiseModel::Robust: the weights w(r) of the measurement factors of one kind / of the closures at the current states, in the order
+// they were added -- one error-only pass with MeasArgs::out_w / CloArgs::out_w set; factors without a loss report 1
+int gpslam_hip_get_meas_weights(gpslam_hip_handle *h, int32_t kind, double *w) {
+  int rc = need_local(h);
+  if (rc) return rc;
+  if (kind < 0 || kind >= kNumMeasKinds || !w) return GPSLAM_E_INVALID;
+  MeasSet &s = h->ms[kind];
+  const int F = s.count();
+  if (s.rob.empty()) { for (int f = 0; f < F; f++) w[f] = 1.0; return F; }
+  LaunchMode m;
+  m.weights = true;
+  if ((rc = launch_factors(h, m, 1, 1))) return rc;
+  std::vector<RowT> t((size_t)F);
+  HIPCHK(hipMemcpyAsync(t.data(), s.d_w.p, (size_t)F * sizeof(RowT), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int f = 0; f < F; f++) w[f] = (double)t[f];
+  return F;
+}
+int gpslam_hip_get_between_pairs_weights(gpslam_hip_handle *h, double *w) {
+  int rc = need_local(h);
+  if (rc) return rc;
+  if (!w) return GPSLAM_E_INVALID;
+  const int F = h->nclo;
+  if (h->clo_rob.empty()) { for (int f = 0; f < F; f++) w[f] = 1.0; return F; }
+  LaunchMode m;
+  m.weights = true;
+  if ((rc = launch_factors(h, m, 1, 1))) return rc;
+  HIPCHK(hipMemcpyAsync(w, h->clo_w.p, (size_t)F * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return F;
 }

@@ -27,6 +27,7 @@
 #include "dpp.hpp"
 #include "cr_step.hpp"
 #include "cr_quad.hpp"
+#include "robust.hpp"
 #include <type_traits>
 
 namespace gps {
@@ -1011,6 +1012,10 @@ template <typename T> struct MeasArgs {
   T *rowLR, *rowE, *rowM;
   int *rowLm;
   T *partial;
+  // noiseModel::Robust (gpslam_hip_set_meas_robust, robust.hpp): count x 2 = (loss, k) per factor, or null: no factor of this kind
+  // carries a loss; out_w (count, or null): every factor's weight w(r), 1 without a loss (gpslam_hip_get_meas_weights)
+  const double *rob = nullptr;
+  T *out_w = nullptr;
 };
 
 // valid (manifold, kind) pairs; everything else is rejected on the host and compiles to an empty kernel
@@ -1366,11 +1371,36 @@ __global__ void __launch_bounds__(128) k_meas(MeasArgs<T> a) {
           }
         }
       }
+      // noiseModel::Robust over the base model above (fp64 handles; compile() refuses the others): one weight per factor from
+      // r = |whitened error|_2 (Robust::WhitenSystem, Block reweighting); the cost takes rho(r) in place of r^2 / 2 (Robust::loss).
+      // sw = sqrt(w(r)); a null table leaves the arithmetic below as it was
+      bool robust = false;
+      T sw = T(1);
+      if constexpr (IsF64<T>::v) {
+        if (a.rob) {
+          const int loss = (int)a.rob[2 * (size_t)f];
+          double wr = 1.0;
+          if (loss != ROBUST_NONE) {
+            double r2 = 0.0, rho;
+#pragma unroll
+            for (int r = 0; r < rows; r++) {
+              const double we = e[r] * ((kFullNoise && a.sqi) ? 1.0 : 1.0 / a.sig[(size_t)f * rows + r]);
+              r2 += we * we;
+            }
+            robust_eval(loss, a.rob[2 * (size_t)f + 1], sqrt(r2), wr, rho);
+            robust = true;
+            sw = sqrt(wr);
+            err += 2.0 * rho;      // (halved with the block's sum below)
+          }
+          if (a.out_w) a.out_w[f] = wr;
+        }
+      }
 #pragma unroll
       for (int r = 0; r < rows; r++) {
-        const T w = (kFullNoise && a.sqi) ? T(1) : T(1) / T(a.sig[(size_t)f * rows + r]);
-        const T we = e[r] * w;
-        err += we * we;
+        T w = (kFullNoise && a.sqi) ? T(1) : T(1) / T(a.sig[(size_t)f * rows + r]);
+        T we = e[r] * w;
+        if (robust) { w *= sw; we *= sw; }
+        else err += we * we;
         wgt[r] = w;
         if (!JAC && a.rowE32) a.rowE32[row0 + r] = (float)we;
         if (JAC && a.rowLR) {      // (rowLR == null: the inspection call, gpslam_hip_linearize_meas, leaves the row tables alone)
@@ -1846,6 +1876,8 @@ struct CloArgs {
   int stride, count, chart;
   const int *first, *second;
   const double *meas, *sig;   // count x pose_dim, count x d
+  const double *rob = nullptr;   // noiseModel::Robust (gpslam_hip_set_between_pairs_robust): count x 2 = (loss, k), or null
+  double *out_w = nullptr;       // count: the weights w(r) (gpslam_hip_get_between_pairs_weights), or null
   double *A;              // count records [A_i (d x d) | A_j (d x d) | r (d)]: whitened H1, H2 and right-hand side
   double *partial;        // the closures' 0.5 |R e|^2 (one value)
   double *blk;            // level-0 block records [D | O | G (B x R)]
@@ -1872,11 +1904,32 @@ template <int MF, bool JAC> __global__ void __launch_bounds__(128) k_clo_eval(Cl
     }
     PoseFactors<double, MF, JAC>::between(m, x1, x2, a.chart, e, H1, H2);
     double *rec = a.A + (size_t)f * kCloLen(d);
+    // noiseModel::Robust, as in k_meas: both blocks and r scaled by sqrt(w(|whitened error|)), the cost takes rho
+    bool robust = false;
+    double sw = 1.0;
+    if (a.rob) {
+      const int loss = (int)a.rob[2 * (size_t)f];
+      double wr = 1.0;
+      if (loss != ROBUST_NONE) {
+        double r2 = 0.0, rho;
+#pragma unroll
+        for (int r = 0; r < d; r++) {
+          const double we = (1.0 / a.sig[(size_t)f * d + r]) * e[r];
+          r2 += we * we;
+        }
+        robust_eval(loss, a.rob[2 * (size_t)f + 1], sqrt(r2), wr, rho);
+        robust = true;
+        sw = sqrt(wr);
+        err += 2.0 * rho;
+      }
+      if (a.out_w) a.out_w[f] = wr;
+    }
 #pragma unroll
     for (int r = 0; r < d; r++) {
-      const double w = 1.0 / a.sig[(size_t)f * d + r];
-      const double we = w * e[r];
-      err += we * we;
+      double w = 1.0 / a.sig[(size_t)f * d + r];
+      double we = w * e[r];
+      if (robust) { w *= sw; we *= sw; }
+      else err += we * we;
       if (JAC) {
 #pragma unroll
         for (int c = 0; c < d; c++) { rec[r * d + c] = w * H1[r * d + c]; rec[d * d + r * d + c] = w * H2[r * d + c]; }

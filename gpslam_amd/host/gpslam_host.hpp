@@ -233,6 +233,8 @@ struct Base {
   std::vector<double> sigmas_;   // diagonal models
   Matrix cov_;                   // full Gaussian (used for Qc)
   bool diagonal_ = true;
+  int robust_ = 0;               // noiseModel::Robust: GPSLAM_ROBUST_* of the mEstimator on top of this model (0: none) and its k
+  double robust_k_ = 0.0;
   int dim() const { return dim_; }
   Matrix covariance() const {
     if (!diagonal_) return cov_;
@@ -252,6 +254,34 @@ struct Gaussian { typedef std::shared_ptr<Base> shared_ptr;
     for (int i = 0; i < c.rows; i++) for (int j = 0; j < c.cols; j++) if (i != j && c(i, j) != 0.0) b->diagonal_ = false;
     if (b->diagonal_) { b->sigmas_.resize(c.rows); for (int i = 0; i < c.rows; i++) b->sigmas_[i] = std::sqrt(c(i, i)); }
     return b;
+  } };
+// gtsam/linear/LossFunctions.h: mEstimator::Huber / Cauchy / Tukey / GemanMcClure / Welsh / Fair, each Create(k); w(r) and rho(r) are
+// those of include/gpslam_hip.h (gpslam_hip_robust_eval), Block reweighting (one weight per factor)
+namespace mEstimator {
+struct Base {
+  typedef std::shared_ptr<Base> shared_ptr;
+  int kind_ = 0;
+  double k_ = 0.0;
+  double weight(double r) const { double w = 1.0, rho = 0.0; (void)gpslam_hip_robust_eval(kind_, k_, r, &w, &rho); return w; }
+  double loss(double r) const { double w = 1.0, rho = 0.0; (void)gpslam_hip_robust_eval(kind_, k_, r, &w, &rho); return rho; }
+};
+inline Base::shared_ptr make(int kind, double k) {
+  if (!(k > 0.0) || !std::isfinite(k)) throw std::invalid_argument("mEstimator: the parameter k must be positive and finite");
+  auto b = std::make_shared<Base>(); b->kind_ = kind; b->k_ = k; return b;
+}
+struct Huber { typedef Base::shared_ptr shared_ptr; static shared_ptr Create(double k = 1.345) { return make(GPSLAM_ROBUST_HUBER, k); } };
+struct Cauchy { typedef Base::shared_ptr shared_ptr; static shared_ptr Create(double k = 0.1) { return make(GPSLAM_ROBUST_CAUCHY, k); } };
+struct Tukey { typedef Base::shared_ptr shared_ptr; static shared_ptr Create(double k = 4.6851) { return make(GPSLAM_ROBUST_TUKEY, k); } };
+struct GemanMcClure { typedef Base::shared_ptr shared_ptr; static shared_ptr Create(double k = 1.0) { return make(GPSLAM_ROBUST_GEMAN_MCCLURE, k); } };
+struct Welsh { typedef Base::shared_ptr shared_ptr; static shared_ptr Create(double k = 2.9846) { return make(GPSLAM_ROBUST_WELSH, k); } };
+struct Fair { typedef Base::shared_ptr shared_ptr; static shared_ptr Create(double k = 1.3998) { return make(GPSLAM_ROBUST_FAIR, k); } };
+}  // namespace mEstimator
+// noiseModel::Robust::Create(mEstimator, base model): measurement factors and loop closures (non-adjacent BetweenFactor) take it; the
+// chain's own factors -- GP priors, PriorFactor, BetweenFactor(x_i, x_i+1) -- do not (they throw, naming the limitation)
+struct Robust { typedef std::shared_ptr<Base> shared_ptr;
+  static shared_ptr Create(const mEstimator::Base::shared_ptr &robust, const std::shared_ptr<Base> &noise) {
+    if (!robust || !noise) throw std::invalid_argument("noiseModel::Robust::Create: null argument");
+    auto b = std::make_shared<Base>(*noise); b->robust_ = robust->kind_; b->robust_k_ = robust->k_; return b;
   } };
 }  // namespace noiseModel
 typedef std::shared_ptr<noiseModel::Base> SharedNoiseModel;
@@ -305,6 +335,8 @@ struct Desc {   // what a factor hands to the graph compiler
   bool vw = false;                   // world-frame (v, w) velocity family
   std::vector<double> meas, sig, sensor, aux;
   std::vector<double> cov;           // measurement factors with a noiseModel::Gaussian (full covariance): rows x rows, else empty
+  int32_t robust = 0;                // noiseModel::Robust: GPSLAM_ROBUST_* and its parameter (measurement factors, loop closures)
+  double robust_k = 0.0;
   double dt = 0, tau = 0;
   Matrix Qc;
 };
@@ -322,6 +354,7 @@ inline bool desc_equals(const Desc &a, const Desc &b, double tol, bool gp) {
   for (int i = 0; i < 2; i++) if (a.kw[i] != b.kw[i]) return false;
   if (!close(a.meas, b.meas, tol) || !close(a.sig, b.sig, tol) || !close(a.cov, b.cov, tol)) return false;
   if (!close(a.sensor, b.sensor, tol) || !close(a.aux, b.aux, tol)) return false;
+  if (a.robust != b.robust || !(std::fabs(a.robust_k - b.robust_k) < tol || a.robust_k == b.robust_k)) return false;
   if (a.type == F_GP) return std::fabs(a.dt - b.dt) < tol && close(a.Qc.a, b.Qc.a, tol);   // (the prior's noise model IS Q(Qc, delta_t))
   if (!gp) return true;
   return std::fabs(a.dt - b.dt) < tol && std::fabs(a.tau - b.tau) < tol && close(a.Qc.a, b.Qc.a, tol);
@@ -353,6 +386,7 @@ inline void desc_print(const Desc &d, const std::string &s, const char *name, in
   };
   vec("measured", d.meas);
   if (d.cov.empty()) vec("noise model: diagonal sigmas", d.sig); else vec("noise model: Gaussian covariance", d.cov);
+  if (d.robust) std::cout << "  robust: mEstimator " << d.robust << ", k = " << d.robust_k << std::endl;
   vec("body_P_sensor", d.sensor);
   vec("calibration", d.aux);
   if (d.dt != 0) std::cout << "  delta_t = " << d.dt << (d.type == F_GP ? "" : ", tau = " + std::to_string(d.tau)) << std::endl;
@@ -373,7 +407,9 @@ class NonlinearFactor {
   virtual void print(const std::string &s = "", const KeyFormatter &keyFormatter = DefaultKeyFormatter) const = 0;
 };
 
-inline std::vector<double> sigmas_of(const SharedNoiseModel &m) {
+inline std::vector<double> sigmas_of(const SharedNoiseModel &m, bool robust_ok = false) {
+  if (m && m->robust_ && !robust_ok)
+    throw std::invalid_argument("noiseModel::Robust is supported on measurement factors and loop closures only, not on the chain's own factors (GP priors, PriorFactor, BetweenFactor of consecutive states)");
   if (!m || !m->diagonal_) throw std::invalid_argument("the noise model of PriorFactor / BetweenFactor must be diagonal (Isotropic / Diagonal)");
   return m->sigmas_;
 }
@@ -381,6 +417,7 @@ inline std::vector<double> sigmas_of(const SharedNoiseModel &m) {
 // a full covariance travels in Desc::cov and reaches the device through gpslam_hip_set_meas_covariance
 inline void noise_of(const SharedNoiseModel &m, detail::Desc &d) {
   if (!m) throw std::invalid_argument("null noise model");
+  d.robust = m->robust_; d.robust_k = m->robust_k_;      // noiseModel::Robust: the loss rides on top of the base model below
   if (m->diagonal_) { d.sig = m->sigmas_; d.cov.clear(); return; }
   d.cov = m->cov_.a;
   d.sig.resize(m->dim_);
@@ -422,7 +459,8 @@ template <typename T> class BetweenFactor : public NonlinearFactor {
  public:
   BetweenFactor(Key key1, Key key2, const T &measured, const SharedNoiseModel &model) {
     d_.type = (symbolChr(key1) == 'b' && detail::VT<T>::t == detail::T_VEC3) ? detail::F_BIAS_BETWEEN : detail::F_BETWEEN;
-    d_.k[0] = key1; d_.k[2] = key2; d_.meas = detail::VT<T>::pack(measured); d_.sig = sigmas_of(model);
+    d_.k[0] = key1; d_.k[2] = key2; d_.meas = detail::VT<T>::pack(measured); d_.sig = sigmas_of(model, true);
+    d_.robust = model->robust_; d_.robust_k = model->robust_k_;   // (a loop closure may carry a loss; a chain factor throws at compile)
   }
   GPSLAM_FACTOR_BOILERPLATE(BetweenFactor<T>, 2)
 };
@@ -604,8 +642,9 @@ struct Session {
         //  the interpolated measurement factors do not depend on theirs: Qc cancels in Lambda and Psi)
         if (!qc_set) { check(gpslam_hip_set_qc(h, Qc.a.data()), h, "set_qc"); qc_set = true; qc_used = Qc.a; }
       };
-      auto gaussian = [&](int kind) {   // noiseModel::Gaussian::Covariance on the factor just added
+      auto gaussian = [&](int kind) {   // noiseModel::Gaussian::Covariance / noiseModel::Robust on the factor just added
         if (!f.cov.empty()) check(gpslam_hip_set_meas_covariance(h, kind, 1, f.cov.data()), h, "set_meas_covariance");
+        if (f.robust) check(gpslam_hip_set_meas_robust(h, kind, 1, &f.robust, &f.robust_k), h, "set_meas_robust");
       };
       auto adjacent = [&](Key k1, Key k2) {
         const int s1 = state_of(k1), s2 = state_of(k2);
@@ -642,6 +681,7 @@ struct Session {
         } break;
         case F_BIAS_BETWEEN: {
           if (!bias) throw std::invalid_argument("BetweenFactor on 'b' keys needs bias variables in the Values");
+          if (f.robust) throw std::invalid_argument("noiseModel::Robust on a BetweenFactor of consecutive states: the chain's own factors take no loss");
           int32_t l = adjacent(f.k[0], f.k[2]);
           std::vector<double> m = {1, 0, 0, 0, 1, 0, 0, 0, 1, f.meas[0], f.meas[1], f.meas[2]};
           std::vector<double> sg = {INFINITY, INFINITY, INFINITY, f.sig[0], f.sig[1], f.sig[2]};
@@ -670,6 +710,8 @@ struct Session {
         case F_LM_PRIOR: { int32_t s = lm_of(f.k[0]); check(gpslam_hip_add_landmark_priors(h, 1, &s, f.meas.data(), f.sig.data()), h, "add_landmark_priors"); } break;
         case F_BETWEEN: {   // any two states: consecutive ones are a chain factor, anything else a loop closure (round 6)
           int32_t s1 = state_of(f.k[0]), s2 = state_of(f.k[2]);
+          if (f.robust && (s2 == s1 + 1 || f.type == F_BIAS_BETWEEN))
+            throw std::invalid_argument("noiseModel::Robust on a BetweenFactor of consecutive states: the chain's own factors take no loss (loop closures do)");
           if (bias) {   // BetweenFactorRot3 on the rotation half
             std::vector<double> m(12, 0.0), sg(6, INFINITY);
             std::memcpy(m.data(), f.meas.data(), sizeof(double) * 9);
@@ -678,6 +720,7 @@ struct Session {
           } else {
             check(gpslam_hip_add_between_pairs(h, 1, &s1, &s2, f.meas.data(), f.sig.data()), h, "add_between_pairs");
           }
+          if (f.robust) check(gpslam_hip_set_between_pairs_robust(h, 1, &f.robust, &f.robust_k), h, "set_between_pairs_robust");
         } break;
         case F_INTERP_RANGE: { set_qc(f.Qc); int32_t l = adjacent(f.k[0], f.k[2]), m = lm_of(f.k[4]);
           check(gpslam_hip_add_interp_range(h, 1, &l, &m, f.meas.data(), f.sig.data(), &f.dt, &f.tau, sens), h, "add_interp_range"); gaussian(GPSLAM_MEAS_INTERP_RANGE); } break;
@@ -1071,6 +1114,7 @@ inline gtsam::detail::Desc gp(int manifold, gtsam::Key p1, gtsam::Key v1, gtsam:
                               const gtsam::SharedNoiseModel &Qc) {
   gtsam::detail::Desc d;
   d.type = gtsam::detail::F_GP; d.manifold = manifold; d.k[0] = p1; d.k[1] = v1; d.k[2] = p2; d.k[3] = v2; d.dt = dt;
+  if (Qc && Qc->robust_) throw std::invalid_argument("noiseModel::Robust on a GP prior: the chain's own factors take no loss (measurement factors and loop closures do)");
   d.Qc = Qc->covariance();      // getQc(Qc_model), gpslam/gp/GPutils.cpp:16-20
   return d;
 }

@@ -36,6 +36,15 @@
 #include <gtsam/nonlinear/Values.h>
 #include <gtsam/slam/BetweenFactor.h>
 #include <gtsam/slam/PriorFactor.h>
+// noiseModel::Robust is mapped where the mEstimators expose their parameter (modelParameter(): GTSAM >= 4.2); elsewhere -- and against
+// the declaration stand-ins -- a Robust model is refused like any other non-diagonal model
+#if __has_include(<gtsam/config.h>) && __has_include(<gtsam/linear/LossFunctions.h>)
+#include <gtsam/config.h>
+#if defined(GTSAM_VERSION_NUMERIC) && GTSAM_VERSION_NUMERIC >= 40200
+#include <gtsam/linear/LossFunctions.h>
+#define GPSLAM_HIP_HAVE_GTSAM_LOSS 1
+#endif
+#endif
 
 #include <gpslam/gp/GPutils.h>
 #include <gpslam/gp/GaussianProcessPriorPose2.h>
@@ -105,6 +114,29 @@ inline std::vector<double> sigmas(const gtsam::SharedNoiseModel &m) {
   if (!diag) throw std::invalid_argument("HipChainOptimizer: the noise models of priors, odometry and range factors must be diagonal");
   const gtsam::Vector s = diag->sigmas();
   return std::vector<double>(s.data(), s.data() + s.size());
+}
+// noiseModel::Robust(mEstimator, base): the base model, and the loss as (GPSLAM_ROBUST_*, k); any other model: itself, no loss.
+// Measurement factors and loop closures take the loss (gpslam_hip_set_meas_robust / _set_between_pairs_robust); the chain's own
+// factors go through sigmas() above with the model as given, which refuses a Robust one.
+struct RobustSpec { int32_t loss = GPSLAM_ROBUST_NONE; double k = 0.0; };
+inline gtsam::SharedNoiseModel base_model(const gtsam::SharedNoiseModel &m, RobustSpec &r) {
+#ifdef GPSLAM_HIP_HAVE_GTSAM_LOSS
+  namespace me = gtsam::noiseModel::mEstimator;
+  auto rb = boost::dynamic_pointer_cast<gtsam::noiseModel::Robust>(m);
+  if (!rb) return m;
+  const auto est = rb->robust();
+  if (auto e1 = boost::dynamic_pointer_cast<me::Huber>(est)) { r.loss = GPSLAM_ROBUST_HUBER; r.k = e1->modelParameter(); }
+  else if (auto e2 = boost::dynamic_pointer_cast<me::Cauchy>(est)) { r.loss = GPSLAM_ROBUST_CAUCHY; r.k = e2->modelParameter(); }
+  else if (auto e3 = boost::dynamic_pointer_cast<me::Tukey>(est)) { r.loss = GPSLAM_ROBUST_TUKEY; r.k = e3->modelParameter(); }
+  else if (auto e4 = boost::dynamic_pointer_cast<me::GemanMcClure>(est)) { r.loss = GPSLAM_ROBUST_GEMAN_MCCLURE; r.k = e4->modelParameter(); }
+  else if (auto e5 = boost::dynamic_pointer_cast<me::Welsh>(est)) { r.loss = GPSLAM_ROBUST_WELSH; r.k = e5->modelParameter(); }
+  else if (auto e6 = boost::dynamic_pointer_cast<me::Fair>(est)) { r.loss = GPSLAM_ROBUST_FAIR; r.k = e6->modelParameter(); }
+  else throw std::invalid_argument("HipChainOptimizer: mEstimator not covered (Huber, Cauchy, Tukey, GemanMcClure, Welsh, Fair are)");
+  return rb->noise();
+#else
+  (void)r;
+  return m;
+#endif
 }
 struct HandleDeleter { void operator()(gpslam_hip_handle *h) const { if (h) gpslam_hip_destroy(h); } };
 inline void pack(const gtsam::Pose3 &p, double *o) {
@@ -199,11 +231,13 @@ template <typename POSE> class HipChainOptimizerT {
       } else if (auto rg = boost::dynamic_pointer_cast<typename TR::Range>(f)) {
         // (an interpolated factor's Qc_model has no effect on its error or Jacobians: Qc cancels in Lambda and Psi)
         const int32_t left = chain_left(rg->key1(), rg->key2(), rg->key3(), rg->key4()), lm = lm_of(rg->key5());
-        const std::vector<double> sg = detail::sigmas(rg->noiseModel());
+        detail::RobustSpec rob;
+        const std::vector<double> sg = detail::sigmas(detail::base_model(rg->noiseModel(), rob));
         double sensor[12];
         if (rg->sensor) detail::pack(*rg->sensor, sensor);
         check(gpslam_hip_add_interp_range(h_, 1, &left, &lm, &rg->measured_value, sg.data(), &rg->gp.delta_t, &rg->gp.tau,
                                           rg->sensor ? sensor : nullptr), "add_interp_range");
+        if (rob.loss != GPSLAM_ROBUST_NONE) check(gpslam_hip_set_meas_robust(h_, GPSLAM_MEAS_INTERP_RANGE, 1, &rob.loss, &rob.k), "set_meas_robust");
       } else if (auto pr = boost::dynamic_pointer_cast<gtsam::PriorFactor<POSE>>(f)) {
         const int32_t idx = state_of(pr->key());
         double m[12];
@@ -227,8 +261,12 @@ template <typename POSE> class HipChainOptimizerT {
         const int32_t first = state_of(bt->key1()), second = state_of(bt->key2());
         double m[12];
         detail::pack(bt->measured(), m);
-        const std::vector<double> sg = detail::sigmas(bt->noiseModel());
+        detail::RobustSpec rob;
+        const std::vector<double> sg = detail::sigmas(detail::base_model(bt->noiseModel(), rob));
+        if (rob.loss != GPSLAM_ROBUST_NONE && second == first + 1)
+          throw std::invalid_argument("HipChainOptimizer: noiseModel::Robust on a BetweenFactor of consecutive states (the chain's own factors take no loss; loop closures do)");
         check(gpslam_hip_add_between_pairs(h_, 1, &first, &second, m, sg.data()), "add_between_pairs");
+        if (rob.loss != GPSLAM_ROBUST_NONE) check(gpslam_hip_set_between_pairs_robust(h_, 1, &rob.loss, &rob.k), "set_between_pairs_robust");
       } else {
         throw std::invalid_argument("HipChainOptimizer: factor type not covered by the chain solver (keep it on stock GTSAM)");
       }

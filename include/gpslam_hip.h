@@ -24,7 +24,8 @@
  *    (the GP Markov property, gpslam/gp/GaussianProcessPriorPose3.h:43-47).
  *  - Noise models: the GP prior uses Q(dt) built from Qc (gpslam/gp/GPutils.h:24-41) -- the handle's shared one or one per
  *    factor (add_gp_priors_qc); every other factor takes diagonal sigmas, or a full Gaussian covariance through
- *    gpslam_hip_set_meas_covariance.
+ *    gpslam_hip_set_meas_covariance; measurement factors and loop closures also a robust loss on top of either
+ *    (noiseModel::Robust: gpslam_hip_set_meas_robust, gpslam_hip_set_between_pairs_robust).
  */
 #ifndef GPSLAM_HIP_H
 #define GPSLAM_HIP_H
@@ -284,6 +285,46 @@ int gpslam_hip_add_bearing_range(gpslam_hip_handle *h, int32_t count, const int3
  * gtsam::noiseModel::Gaussian does. */
 int gpslam_hip_set_meas_covariance(gpslam_hip_handle *h, int32_t kind, int32_t count, const double *cov);
 
+/* noiseModel::Robust(mEstimator, base) on measurement factors and loop closures (gtsam/linear/NoiseModel.h, LossFunctions.h; added
+ * without an ABI bump: a binding detects these entry points by their presence).  The base model is what the factor has -- sigmas, or
+ * the square-root information of set_meas_covariance; the loss (kind, k) sits on top of it.  With e_w the factor's whitened error
+ * over all of its rows and r = |e_w|_2:
+ *   linearisation  every row of the factor and its error entry are multiplied by sqrt(w(r)), ONE weight per factor -- GTSAM's
+ *                  Robust::WhitenSystem with Block reweighting: noise_->WhitenSystem(A, b); robust_->reweight(A, b);
+ *   cost           gpslam_hip_error, error_before / error_after and every cost Levenberg-Marquardt compares take rho(r) for the
+ *                  factor in place of r^2 / 2 -- Robust::loss of GTSAM >= 4.1 (4.0 reported w r^2 / 2, which for the redescending
+ *                  losses falls to zero as a residual grows: DESIGN.md section 2).  The model-fidelity denominator stays the
+ *                  weighted linear system's, as in GTSAM.
+ * With u = r^2 / k^2 (mEstimator::Huber, Cauchy, Tukey, GemanMcClure, Welsh, Fair):
+ *   HUBER          w = 1 (r <= k), k / r            rho = r^2 / 2 (r <= k), k (r - k / 2)
+ *   CAUCHY         w = k^2 / (k^2 + r^2)            rho = (k^2 / 2) log(1 + u)
+ *   TUKEY          w = (1 - u)^2 (r <= k), 0        rho = k^2 (1 - (1 - u)^3) / 6 (r <= k), k^2 / 6
+ *   GEMAN_MCCLURE  w = k^4 / (k^2 + r^2)^2          rho = k^2 r^2 / (2 (k^2 + r^2))
+ *   WELSH          w = exp(-u)                      rho = (k^2 / 2) (1 - exp(-u))
+ *   FAIR           w = 1 / (1 + r / k)              rho = k^2 (r / k - log(1 + r / k))
+ * each with rho'(r) = w(r) r, rho(0) = 0, w(0) = 1.  k <= 0 or not finite: GPSLAM_E_INVALID.  A factor whose loss is NONE, and a
+ * handle on which every loss is NONE, run exactly as without these calls.
+ * compile() answers GPSLAM_E_UNSUPPORTED on fp32 handles, sharded handles and split pieces that carry any loss.  A graph with a robust
+ * interpolated GPS factor keeps those factors as 24-column rows (as GPSLAM_PLAN_MEAS_ROWS does): the weight needs all three rows.
+ * gpslam_hip_marginals linearises through the same kernels and so inverts the reweighted H, as gtsam::Marginals does. */
+enum { GPSLAM_ROBUST_NONE = 0, GPSLAM_ROBUST_HUBER = 1, GPSLAM_ROBUST_CAUCHY = 2, GPSLAM_ROBUST_TUKEY = 3, GPSLAM_ROBUST_GEMAN_MCCLURE = 4,
+       GPSLAM_ROBUST_WELSH = 5, GPSLAM_ROBUST_FAIR = 6 };
+/* replaces the loss of the `count` most recently added factors of `kind` (GPSLAM_MEAS_*; the calling convention of
+ * set_meas_covariance, in either order with it): loss = count x GPSLAM_ROBUST_*, k = count parameters (ignored where the loss is
+ * NONE).  GPSLAM_MEAS_AHRS is refused (GPSLAM_E_UNSUPPORTED).  The handle needs a new compile(); marginals held from before are stale. */
+int gpslam_hip_set_meas_robust(gpslam_hip_handle *h, int32_t kind, int32_t count, const int32_t *loss, const double *k);
+/* the same for the `count` most recently added loop closures (the non-adjacent pairs of add_between_pairs).  Adjacent pairs are chain
+ * factors (add_between) and take no loss, like the GP priors and the pose / velocity priors. */
+int gpslam_hip_set_between_pairs_robust(gpslam_hip_handle *h, int32_t count, const int32_t *loss, const double *k);
+/* the weights w(r) at the current states, in the order the factors were added (1 for a factor without a loss): what a caller reads
+ * after optimize() to see which measurements were rejected.  One error-only pass each.  w: count of the kind / of the closures.
+ * Returns the count. */
+int gpslam_hip_get_meas_weights(gpslam_hip_handle *h, int32_t kind, double *w);
+int gpslam_hip_get_between_pairs_weights(gpslam_hip_handle *h, double *w);
+/* w(r) and rho(r) of one loss, host arithmetic only, no handle: the inline functions the kernels include (gpslam_amd/csrc/robust.hpp).
+ * r >= 0 and finite; NONE gives 1 and r^2 / 2. */
+int gpslam_hip_robust_eval(int32_t loss, double k, double r, double *w, double *rho);
+
 /* drop every factor added so far (states, landmarks and Qc stay); the handle needs a new compile() */
 int gpslam_hip_clear_factors(gpslam_hip_handle *h);
 
@@ -368,7 +409,7 @@ int gpslam_hip_interpolate_poses_jac(gpslam_hip_handle *h, int32_t count, const 
 int gpslam_hip_marginals(gpslam_hip_handle *h);
 /* copies the window [first, first + count) of S / S_next / S_x_lm (count x b x b, count x b x b, count x b x nl), and S_lm; any pointer
  * may be NULL.  GPSLAM_E_INVALID ("stale") before gpslam_hip_marginals, or after any call that can change states, landmarks,
- * factors or Qc since: set_states, set_landmarks, set_qc, add_*, set_meas_covariance, clear_factors, compile, iterate_gn, iterate_lm,
+ * factors or Qc since: set_states, set_landmarks, set_qc, add_*, set_meas_covariance, set_*_robust, clear_factors, compile, iterate_gn, iterate_lm,
  * run_gn, optimize. */
 int gpslam_hip_get_marginals(gpslam_hip_handle *h, int32_t first, int32_t count, double *S, double *S_next, double *S_lm,
                              double *S_x_lm);

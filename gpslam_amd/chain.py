@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "gpslam_hip_launch_census",
     "gpslam_hip_set_meas_robust", "gpslam_hip_set_between_pairs_robust", "gpslam_hip_get_meas_weights",
     "gpslam_hip_get_between_pairs_weights", "gpslam_hip_robust_eval",
+    "gpslam_hip_set_closure_passes", "gpslam_hip_closure_info",
 ]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
@@ -311,6 +312,18 @@ class ChainSolver:
             raise ValueError("add_between_pairs: first and second differ in length")
         return self._chk(self.lib.gpslam_hip_add_between_pairs(self._h, len(first), _p(first), _p(second), _p(measured), _p(sigmas)),
                          "add_between_pairs")
+
+    def set_closure_passes(self, max_passes, closures_per_pass=0):
+        """Before compile(): allow more loop closures than one border holds, as up to max_passes column passes of closures_per_pass
+        closures each (0: as many as fit).  max_passes <= 1 is the default: one pass, today's capacity."""
+        return self._chk(self.lib.gpslam_hip_set_closure_passes(self._h, int(max_passes), int(closures_per_pass)), "set_closure_passes")
+
+    def closure_info(self):
+        """After compile(): dict(closures, per_pass, passes, solves) -- the closures, the w of them that share a pass, the column
+        passes P, and the solves of the chain one linear system takes (P + 1 beyond one pass)."""
+        out = (C.c_int32 * 4)()
+        self._chk(self.lib.gpslam_hip_closure_info(self._h, out), "closure_info")
+        return dict(zip(("closures", "per_pass", "passes", "solves"), (int(v) for v in out)))
 
     def add_landmark_priors(self, idx, prior, sigmas):
         idx, prior, sigmas = _i32(idx), _f64(prior), _f64(sigmas)

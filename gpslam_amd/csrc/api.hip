@@ -152,7 +152,7 @@ int gpslam_hip_destroy(gpslam_hip_handle *h) {
                     &h->halo_add, &h->iface_send, &h->iface_recv, &h->top_blk, &h->top_x, &h->scal, &h->flag,
                     &h->api_e, &h->api_H, &h->gps, &h->gpidx, &h->dU, &h->gsave2, &h->partial2, &h->brec, &h->btwidx,
                     &h->rowI, &h->irowptr, &h->coll_s, &h->coll_r, &h->d_clo_second, &h->clo_A, &h->clo_Y, &h->simd_cnt,
-                    &h->d_clo_rob, &h->clo_w};
+                    &h->d_clo_rob, &h->clo_w, &h->clo_W, &h->clo_X};
   for (DevBuf *b : bufs) b->release();
   marginals_release(h);
   for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri, &h->clo}) s->release();
@@ -430,6 +430,24 @@ int gpslam_hip_add_between_pairs(gpslam_hip_handle *h, int32_t count, const int3
   }
   h->compiled = false;
   h->marg_ok = false;
+  return 0;
+}
+int gpslam_hip_set_closure_passes(gpslam_hip_handle *h, int32_t max_passes, int32_t closures_per_pass) {
+  if (!h) return GPSLAM_E_INVALID;
+  if (closures_per_pass < 0) return fail(h, GPSLAM_E_INVALID, "set_closure_passes: closures_per_pass must not be negative (0: as many as fit)");
+  h->clo_max_passes = max_passes < 1 ? 1 : max_passes;
+  h->clo_per_pass = closures_per_pass;
+  h->compiled = false;
+  h->marg_ok = false;
+  return 0;
+}
+int gpslam_hip_closure_info(gpslam_hip_handle *h, int32_t out4[4]) {
+  int rc = need_compiled(h);
+  if (rc) return rc;
+  if (!out4) return GPSLAM_E_INVALID;
+  // solves of the chain per linear system: one per column pass and, beyond one pass, the final one
+  const int32_t v[4] = {h->nclo, h->clo_slice, h->clo_P, h->clo_P > 1 ? h->clo_P + 1 : 1};
+  for (int i = 0; i < 4; i++) out4[i] = v[i];
   return 0;
 }
 int gpslam_hip_add_landmark_priors(gpslam_hip_handle *h, int32_t count, const int32_t *idx, const double *prior,

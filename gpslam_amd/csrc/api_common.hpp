@@ -137,6 +137,11 @@ struct gpslam_hip_handle {
   std::vector<double> clo_rob;        // noiseModel::Robust on closures (gpslam_hip_set_between_pairs_robust): as MeasSet::rob
   DevBuf d_clo_rob, clo_w;
   int nclo = 0, nc = 0;       // closures of the compiled graph, their right-hand-side columns (nclo * d)
+  // closures in column passes (gpslam_hip_set_closure_passes; kernels.hpp CloPass): the caller's two numbers, and what compile() made
+  // of them -- clo_P > 1: slices of clo_slice closures, W = U [X | Z] and pass 0's X kept between the passes
+  int clo_max_passes = 1, clo_per_pass = 0;
+  int clo_slice = 0, clo_P = 0;
+  DevBuf clo_W, clo_X;
   MeasSet ms[kNumMeasKinds];
   // row table
   int M = 0;

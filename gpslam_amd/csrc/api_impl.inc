@@ -80,6 +80,15 @@ CloArgs clo_args(gpslam_hip_handle *h) {
   a.N = h->N; a.ncols = 1 + h->nl; a.Y = h->clo_Y.as<double>(); a.flag = h->flag.as<int>();
   return a;
 }
+// closures in column passes: slice p of the compiled graph's closures, and what the pass kernels share
+CloPass clo_pass(gpslam_hip_handle *h, int p) {
+  CloPass c;
+  c.k0 = std::min(p * h->clo_slice, h->nclo); c.k1 = std::min(c.k0 + h->clo_slice, h->nclo);
+  c.lead = p == 0 ? 1 : 0;
+  c.W = h->clo_W.as<double>(); c.ldw = 1 + h->nl + h->nc;
+  c.X = h->clo_X.as<double>();
+  return c;
+}
 // Y = (I + U Z)^-1 ([r | 0] - U X) and X += Z Y, between the chain's back-substitution and the landmark Schur complement
 int launch_closures(gpslam_hip_handle *h) {
   if (h->nclo <= 0) return 0;
@@ -333,7 +342,9 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
   return 0;
 }
 
-int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g) {
+// pass (closures in column passes, clo_P > 1): which slice of the closures' columns the records take; pass == clo_P: the final
+// pass, whose right-hand sides are U^T Y alone
+int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g, int pass = 0) {
   AsmArgs<Real, RowT> a;
   a.N = h->N; a.R = h->R;
   a.rowptr = h->rowptr.as<int>();
@@ -360,7 +371,16 @@ int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g) {
   if (h->nclo > 0) {   // the closures' columns of U^T into the records of their states (and U^T r into the gradient copy)
     CloArgs c = clo_args(h);
     c.gsave = save_g ? h->gsave.as<double>() : nullptr;
-    dispatch_b(h->b, [&](auto tag) { k_clo_inject<decltype(tag)::value / 2><<<dim3(1), dim3(256), 0, h->stream>>>(c); });
+    if (h->clo_P > 1 && pass >= h->clo_P) {
+      dispatch_b(h->b, [&](auto tag) {
+        constexpr int D = decltype(tag)::value / 2;
+        k_clo_clear_lead<D><<<dim3(nblocks(h->N * c.ncols * h->b, 256)), dim3(256), 0, h->stream>>>(c);
+        k_clo_inject_y<D><<<dim3(1), dim3(256), 0, h->stream>>>(c);
+      });
+    } else {
+      const CloPass cp = clo_pass(h, pass);   // (one pass: every closure)
+      dispatch_b(h->b, [&](auto tag) { k_clo_inject<decltype(tag)::value / 2><<<dim3(1), dim3(256), 0, h->stream>>>(c, cp.k0, cp.k1); });
+    }
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1008,9 +1028,41 @@ int fs_build(gpslam_hip_handle *h, const std::vector<int> &touch_lo, const std::
   return 0;
 }
 
+// Closures in column passes (clo_P > 1): the caller's assembly carried slice 0.  Every pass is the same factorisation at the same
+// lambda; the records are reassembled in front of each one because the elimination works in place.
+int launch_solve_passes(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
+  int rc;
+  const CloArgs a = clo_args(h);
+  const int P = h->clo_P, nlead = h->N * a.ncols * h->b;
+  LaunchMode later = m;       // (a timed iteration stamps the level-0 launch of pass 0 alone)
+  later.stamp_l0 = false;
+  for (int p = 0; p < P; p++) {
+    if (p > 0 && (rc = launch_assemble(h, m, false, p))) return rc;
+    if ((rc = launch_forward(h, p == 0 ? m : later, lambda))) return rc;
+    if ((rc = launch_backward(h, nullptr))) return rc;
+    const CloPass cp = clo_pass(h, p);
+    const int entries = h->nc * ((cp.lead ? a.ncols : 0) + (cp.k1 - cp.k0) * h->d);
+    dispatch_b(h->b, [&](auto tag) {
+      constexpr int D = decltype(tag)::value / 2;
+      if (p == 0) k_clo_save<D><<<dim3(nblocks(nlead, 256)), dim3(256), 0, h->stream>>>(a, cp);
+      k_clo_gather<D><<<dim3(nblocks(entries, 256)), dim3(256), 0, h->stream>>>(a, cp);
+    });
+  }
+  const CloPass cp = clo_pass(h, 0);
+  const size_t smem = ((size_t)h->nc * (h->nc + 1) + (size_t)h->nc * a.ncols) * sizeof(double);
+  dispatch_b(h->b, [&](auto tag) { k_clo_solve_wide<decltype(tag)::value / 2><<<dim3(1), dim3(256), smem, h->stream>>>(a, cp); });
+  if ((rc = launch_assemble(h, m, false, P))) return rc;
+  if ((rc = launch_forward(h, later, lambda))) return rc;
+  if ((rc = launch_backward(h, nullptr))) return rc;
+  dispatch_b(h->b, [&](auto tag) { k_clo_add<decltype(tag)::value / 2><<<dim3(nblocks(nlead, 256)), dim3(256), 0, h->stream>>>(a, cp); });
+  HIPCHK(hipGetLastError());
+  return launch_landmarks(h, lambda);
+}
+
 int launch_solve(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
   int rc;
   if (h->fs.active) return fs_solve(h, lambda);
+  if (h->clo_P > 1) return launch_solve_passes(h, m, lambda);
   if ((rc = launch_forward(h, m, lambda))) return rc;
   if ((rc = launch_backward(h, nullptr))) return rc;
   if ((rc = launch_closures(h))) return rc;
@@ -1136,7 +1188,28 @@ int choose_landmark_path(gpslam_hip_handle *h, bool &segmented) {
   for (int k = 0; k < h->nclo; k++)
     if (h->clo.idx[k] >= N || h->clo_second[k] >= N)
       return fail(h, GPSLAM_E_INVALID, "a stored loop closure refers to a state that no longer exists (set_states shrank the problem)");
-  h->R = 1 + h->nl + h->nc;
+  h->clo_slice = h->nclo;
+  h->clo_P = h->nclo > 0 ? 1 : 0;
+  bool passes = false;
+  // closures in column passes (gpslam_hip_set_closure_passes, max_passes >= 2; unsharded fp64 handles, the others are refused below):
+  // slices of w closures, R = 1 + nl + w d.  A graph that fits one pass keeps today's path and today's R
+  if (h->nclo > 0 && h->clo_max_passes >= 2 && kIsF64 && !sharded(h) && h->cfg.force_segmented != 1 && !h->fs.split) {
+    const int room = std::min(kMaxRhs, 64 - 3 * b) - 1 - h->nl;   // 1 + nl + w d <= 28 and 3 b + R <= 64
+    const int fit = room > 0 ? room / d : 0;
+    int w = h->clo_per_pass > 0 ? h->clo_per_pass : fit;
+    if (fit < 1) return fail(h, GPSLAM_E_UNSUPPORTED, "loop closures in column passes: the landmark columns leave no room for a closure (1 + landmarks * landmark_dim + d must not exceed 28 right-hand sides)");
+    if (w > fit) return fail(h, GPSLAM_E_UNSUPPORTED, "loop closures in column passes: closures_per_pass is larger than fits (1 + landmarks * landmark_dim + closures_per_pass * d must not exceed 28 right-hand sides)");
+    w = std::min(w, h->nclo);
+    const int P = (h->nclo + w - 1) / w;
+    if (P > 1) {
+      if (h->nc > kCloWideMax) return fail(h, GPSLAM_E_UNSUPPORTED, "too many loop closures: closures * d must not exceed 120");
+      if (P > h->clo_max_passes) return fail(h, GPSLAM_E_UNSUPPORTED, "too many loop closures for max_passes column passes (set_closure_passes): closures / closures per pass exceeds it");
+      passes = true;
+    }
+    h->clo_slice = w;
+    h->clo_P = P;
+  }
+  h->R = 1 + h->nl + (passes ? h->clo_slice * d : h->nc);
   h->fs.active = false;
   segmented = h->nl > 0 && (h->cfg.force_segmented == 1 || h->fs.split || 3 * b + h->R > 64 || h->R > kMaxRhs);
   if (h->fs.split) {
@@ -1265,6 +1338,16 @@ int upload_factors(gpslam_hip_handle *h, const RowLayout &lay, int &npart) {
     if ((rc = upload(h, h->d_clo_second, h->clo_second))) return rc;
     HIPCHK(h->clo_A.reserve((size_t)h->nclo * kCloLen(d) * sizeof(double)));
     HIPCHK(h->clo_Y.reserve((size_t)h->nc * (1 + h->nl) * sizeof(double)));
+    if (h->clo_P > 1) {
+      HIPCHK(h->clo_W.reserve((size_t)h->nc * (1 + h->nl + h->nc) * sizeof(double)));
+      HIPCHK(h->clo_X.reserve((size_t)h->N * (1 + h->nl) * b * sizeof(double)));
+      // (process-wide per kernel: always the size of the widest system)
+      hipError_t ea = hipSuccess;
+      dispatch_b(b, [&](auto tag) {
+        ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_clo_solve_wide<decltype(tag)::value / 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCloWideLds);
+      });
+      HIPCHK(ea);
+    }
     if ((rc = upload(h, h->d_clo_rob, h->clo_rob))) return rc;
     if (!h->clo_rob.empty()) HIPCHK(h->clo_w.reserve((size_t)h->nclo * sizeof(double)));
   }

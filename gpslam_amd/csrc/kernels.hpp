@@ -1941,15 +1941,17 @@ template <int MF, bool JAC> __global__ void __launch_bounds__(128) k_clo_eval(Cl
   if (threadIdx.x == 0) a.partial[0] = tot;
 }
 
-// the columns of U^T into the records of the two states of every closure (k_assemble_ghost left those columns zero); one workgroup
-template <int d> __global__ void __launch_bounds__(256) k_clo_inject(CloArgs a) {
+// the columns of U^T into the records of the two states of every closure (k_assemble_ghost left those columns zero); one workgroup.
+// [k0, k1): the closures whose columns ride in this pass, in columns col0 .. col0 + (k1 - k0) d - 1 (one pass: all of them); the
+// gradient copy takes U^T r of EVERY closure whenever it is asked for.
+template <int d> __global__ void __launch_bounds__(256) k_clo_inject(CloArgs a, int k0, int k1) {
   const int per = 2 * d * d;
-  for (int t = threadIdx.x; t < a.count * per; t += 256) {
-    const int k = t / per, u = t - k * per;
+  for (int t = threadIdx.x; t < (k1 - k0) * per; t += 256) {
+    const int kk = t / per, u = t - kk * per, k = k0 + kk;
     const int side = u / (d * d), v = u - side * d * d;
     const int q = v / d, c = v - q * d;
     const int s = side ? a.second[k] : a.first[k];
-    a.blk[(size_t)s * a.BS + 2 * a.B * a.B + (size_t)(a.col0 + k * d + q) * a.B + c] = a.A[(size_t)k * kCloLen(d) + u];
+    a.blk[(size_t)s * a.BS + 2 * a.B * a.B + (size_t)(a.col0 + kk * d + q) * a.B + c] = a.A[(size_t)k * kCloLen(d) + u];
   }
   if (a.gsave && threadIdx.x == 0) {     // several closures may meet in one state: one thread, the order they were added in
     for (int k = 0; k < a.count; k++) {
@@ -2035,6 +2037,148 @@ template <int d> __global__ void __launch_bounds__(256) k_clo_correct(CloArgs a)
     for (int q = 0; q < nc; q++) v += z[q] * a.Y[(size_t)q * a.ncols + c];
     xs[(size_t)c * a.B + k] = v;
   }
+}
+
+// ---- closures in column passes (gpslam_hip_set_closure_passes): more closures than one border holds.  The nc = K d columns of U^T
+// go through the chain solver a slice of w closures at a time (P = ceil(K / w) passes of the same factorisation, each at the same
+// lambda), and only W = U [X | Z] -- Z at the closures' own two states -- is kept of them (nc x (ncols + nc), global memory).  Then
+//   Y = (I + U Z)^-1 ([r | 0] - U X)   (k_clo_solve_wide, one workgroup),   X_full = X + H0^-1 (U^T Y):
+// one more pass with U^T Y in place of [g | B] and the closure columns empty, added to the X saved from pass 0.
+struct CloPass {
+  int k0, k1;             // the closures of this pass's slice
+  int lead;               // pass 0: the ncols leading columns U X are gathered as well
+  double *W;              // nc x ldw
+  int ldw;                // ncols + nc
+  double *X;              // N x ncols x B: columns 0 .. ncols - 1 of pass 0's solution
+};
+constexpr int kCloWideMax = 120;    // rows of the wide system (closures * d)
+constexpr int kCloWidePanel = 8;    // panel width of its Cholesky factorisation
+constexpr size_t kCloWideLds = ((size_t)kCloWideMax * (kCloWideMax + 1) + (size_t)kCloWideMax * kMaxRhs) * sizeof(double);
+
+// X <- columns 0 .. ncols - 1 of the level-0 solution (they lead every state's R x B record)
+template <int d> __global__ void __launch_bounds__(256) k_clo_save(CloArgs a, CloPass p) {
+  const int per = a.ncols * a.B;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)a.N * per) return;
+  const size_t s = i / per;
+  p.X[i] = a.x[s * a.R * a.B + (i - s * per)];
+}
+
+// W[:, slice] = U Z_slice (and W[:, 0 .. ncols - 1] = U X on pass 0): one thread per entry, the dot products of k_clo_solve
+template <int d> __global__ void __launch_bounds__(256) k_clo_gather(CloArgs a, CloPass p) {
+  const int nc = a.count * d, R = a.R;
+  const int nlead = p.lead ? a.ncols : 0, wid = nlead + (p.k1 - p.k0) * d;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= nc * wid) return;
+  const int row = idx / wid, cc = idx - row * wid;
+  const int xc = cc < nlead ? cc : a.col0 + (cc - nlead);             // column of the solution
+  const int wc = cc < nlead ? cc : a.ncols + p.k0 * d + (cc - nlead);   // column of W
+  const int k = row / d, q = row - k * d;
+  const double *rec = a.A + (size_t)k * kCloLen(d);
+  const double *xi = a.x + ((size_t)a.first[k] * R + xc) * a.B, *xj = a.x + ((size_t)a.second[k] * R + xc) * a.B;
+  double acc = 0.0;
+  for (int m = 0; m < d; m++) acc += rec[q * d + m] * xi[m];
+  for (int m = 0; m < d; m++) acc += rec[d * d + q * d + m] * xj[m];
+  p.W[(size_t)row * p.ldw + wc] = acc;
+}
+
+// Y = (I + 1/2 (U Z + (U Z)^T))^-1 ([r | 0] - U X), nc <= kCloWideMax: one workgroup, the matrix and the right-hand sides in dynamic
+// LDS (nc (nc + 1) + nc ncols doubles).  Right-looking Cholesky in panels of kCloWidePanel columns, then the two substitutions, every
+// entry owned by one thread between two barriers: the same sums in the same order on every run.
+template <int d> __global__ void __launch_bounds__(256) k_clo_solve_wide(CloArgs a, CloPass p) {
+  extern __shared__ double clo_lds[];
+  const int tid = threadIdx.x, nc = a.count * d, ls = nc + 1, nr = a.ncols;
+  double *S = clo_lds, *Rh = clo_lds + (size_t)nc * ls;
+  for (int idx = tid; idx < nc * nc; idx += 256) {
+    const int i = idx / nc, j = idx - i * nc;
+    S[i * ls + j] = (i == j ? 1.0 : 0.0) + 0.5 * (p.W[(size_t)i * p.ldw + nr + j] + p.W[(size_t)j * p.ldw + nr + i]);
+  }
+  for (int idx = tid; idx < nc * nr; idx += 256) {
+    const int i = idx / nr, c = idx - i * nr;
+    const int k = i / d, q = i - k * d;
+    Rh[idx] = (c == 0 ? a.A[(size_t)k * kCloLen(d) + 2 * d * d + q] : 0.0) - p.W[(size_t)i * p.ldw + c];
+  }
+  __syncthreads();
+  for (int j0 = 0; j0 < nc; j0 += kCloWidePanel) {
+    const int j1 = min(j0 + kCloWidePanel, nc);
+    for (int j = j0; j < j1; j++) {     // the panel: column j, then its update of the panel's columns to the right
+      double dd = S[j * ls + j];
+      if (!(dd > 0.0)) { if (tid == 0) *a.flag = 1; dd = 1.0; }
+      const double l = sqrt(dd), linv = 1.0 / l;
+      __syncthreads();
+      for (int i = j + tid; i < nc; i += 256) S[i * ls + j] = (i == j) ? l : S[i * ls + j] * linv;
+      __syncthreads();
+      const int pc = j1 - j - 1, pr = nc - j - 1;
+      for (int idx = tid; idx < pr * pc; idx += 256) {
+        const int i = j + 1 + idx / pc, k = j + 1 + idx % pc;
+        if (k <= i) S[i * ls + k] -= S[i * ls + j] * S[k * ls + j];
+      }
+      __syncthreads();
+    }
+    const int m = nc - j1, jb = j1 - j0;   // the trailing matrix: rank-jb update, lower triangle
+    for (int idx = tid; idx < m * m; idx += 256) {
+      const int i = j1 + idx / m, k = j1 + idx % m;
+      if (k <= i) {
+        double acc = S[i * ls + k];
+        for (int t = 0; t < jb; t++) acc -= S[i * ls + j0 + t] * S[k * ls + j0 + t];
+        S[i * ls + k] = acc;
+      }
+    }
+    __syncthreads();
+  }
+  for (int j = 0; j < nc; j++) {          // L y = b
+    if (tid < nr) Rh[j * nr + tid] /= S[j * ls + j];
+    __syncthreads();
+    for (int idx = tid; idx < (nc - j - 1) * nr; idx += 256) {
+      const int i = j + 1 + idx / nr, c = idx % nr;
+      Rh[i * nr + c] -= S[i * ls + j] * Rh[j * nr + c];
+    }
+    __syncthreads();
+  }
+  for (int j = nc - 1; j >= 0; j--) {     // L^T z = y
+    if (tid < nr) Rh[j * nr + tid] /= S[j * ls + j];
+    __syncthreads();
+    for (int idx = tid; idx < j * nr; idx += 256) {
+      const int i = idx / nr, c = idx - i * nr;
+      Rh[i * nr + c] -= S[j * ls + i] * Rh[j * nr + c];
+    }
+    __syncthreads();
+  }
+  for (int idx = tid; idx < nc * nr; idx += 256) a.Y[idx] = Rh[idx];
+}
+
+// the final pass's right-hand sides: columns 0 .. ncols - 1 of every record emptied ...
+template <int d> __global__ void __launch_bounds__(256) k_clo_clear_lead(CloArgs a) {
+  const int per = a.ncols * a.B;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)a.N * per) return;
+  const size_t s = i / per;
+  a.blk[s * a.BS + 2 * a.B * a.B + (i - s * per)] = 0.0;
+}
+// ... and U^T Y added at the closures' states: one workgroup, a thread owns one (column, pose coordinate) through every closure, in
+// the order they were added in
+template <int d> __global__ void __launch_bounds__(256) k_clo_inject_y(CloArgs a) {
+  for (int t = threadIdx.x; t < a.ncols * d; t += 256) {
+    const int c = t / d, m = t - c * d;
+    for (int k = 0; k < a.count; k++) {
+      const double *rec = a.A + (size_t)k * kCloLen(d);
+      for (int side = 0; side < 2; side++) {
+        const int s = side ? a.second[k] : a.first[k];
+        double acc = 0.0;
+        for (int q = 0; q < d; q++) acc += rec[side * d * d + q * d + m] * a.Y[(size_t)(k * d + q) * a.ncols + c];
+        a.blk[(size_t)s * a.BS + 2 * a.B * a.B + (size_t)c * a.B + m] += acc;
+      }
+    }
+  }
+}
+// x[:, c] = X[:, c] + x[:, c], c < ncols
+template <int d> __global__ void __launch_bounds__(256) k_clo_add(CloArgs a, CloPass p) {
+  const int per = a.ncols * a.B;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)a.N * per) return;
+  const size_t s = i / per;
+  double *xs = a.x + s * a.R * a.B + (i - s * per);
+  *xs = p.X[i] + *xs;
 }
 
 // ------------------------------------------------------------------ K3: assemble normal equations

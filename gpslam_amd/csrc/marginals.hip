@@ -347,6 +347,7 @@ int mg_refuse(gpslam_hip_handle *h) {
   if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: sharded handles are not supported");
   if (h->fs.active && h->fs.split) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: split pieces are not supported");
   if (h->fs.active) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: the segmented landmark path is not supported");
+  if (h->clo_P > 1) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: loop closures in more than one column pass (set_closure_passes) are not supported: Z = H0^-1 U^T is not kept at every state");
   return 0;
 }
 

@@ -631,6 +631,7 @@ struct Session {
     if (L > 0) check(gpslam_hip_set_landmarks(h, L, LM.data()), h, "set_landmarks");
     // ---- factors
     bool qc_set = false;
+    int closures = 0;                  // BetweenFactors between non-adjacent states
     std::vector<double> qc_used;
     for (auto &fp : graph.factors()) {
       const Desc f = fp->describe();
@@ -721,6 +722,7 @@ struct Session {
             check(gpslam_hip_add_between_pairs(h, 1, &s1, &s2, f.meas.data(), f.sig.data()), h, "add_between_pairs");
           }
           if (f.robust) check(gpslam_hip_set_between_pairs_robust(h, 1, &f.robust, &f.robust_k), h, "set_between_pairs_robust");
+          if (s2 != s1 + 1) closures++;
         } break;
         case F_INTERP_RANGE: { set_qc(f.Qc); int32_t l = adjacent(f.k[0], f.k[2]), m = lm_of(f.k[4]);
           check(gpslam_hip_add_interp_range(h, 1, &l, &m, f.meas.data(), f.sig.data(), &f.dt, &f.tau, sens), h, "add_interp_range"); gaussian(GPSLAM_MEAS_INTERP_RANGE); } break;
@@ -744,6 +746,9 @@ struct Session {
       int32_t idx = s;
       check(gpslam_hip_add_vel_priors(h, 1, &idx, z.data(), one.data()), h, "add_vel_priors");
     }
+    // more closures than one border of 28 right-hand sides holds: GTSAM would simply solve such a graph, so the column passes are
+    // switched on here (gpslam_hip_set_closure_passes); graphs within one pass create their handle exactly as before
+    if (closures > 0 && 1 + L * ld + closures * d > 28) check(gpslam_hip_set_closure_passes(h, 32, 0), h, "set_closure_passes");
     check(gpslam_hip_compile(h), h, "compile");
   }
 

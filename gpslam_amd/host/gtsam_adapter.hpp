@@ -218,6 +218,7 @@ template <typename POSE> class HipChainOptimizerT {
     check(gpslam_hip_set_states(h_, N, P.data(), V.data()), "set_states");
     if (L > 0) check(gpslam_hip_set_landmarks(h_, L, LM.data()), "set_landmarks");
     bool qc_set = false;
+    int closures = 0;                  // BetweenFactors between non-adjacent states
     for (const auto &f : graph) {
       if (!f) continue;
       if (auto gp = boost::dynamic_pointer_cast<typename TR::Prior>(f)) {
@@ -266,11 +267,15 @@ template <typename POSE> class HipChainOptimizerT {
         if (rob.loss != GPSLAM_ROBUST_NONE && second == first + 1)
           throw std::invalid_argument("HipChainOptimizer: noiseModel::Robust on a BetweenFactor of consecutive states (the chain's own factors take no loss; loop closures do)");
         check(gpslam_hip_add_between_pairs(h_, 1, &first, &second, m, sg.data()), "add_between_pairs");
+        if (second != first + 1) closures++;
         if (rob.loss != GPSLAM_ROBUST_NONE) check(gpslam_hip_set_between_pairs_robust(h_, 1, &rob.loss, &rob.k), "set_between_pairs_robust");
       } else {
         throw std::invalid_argument("HipChainOptimizer: factor type not covered by the chain solver (keep it on stock GTSAM)");
       }
     }
+    // more closures than one border of 28 right-hand sides holds: GTSAM would simply solve such a graph, so the column passes are
+    // switched on here (gpslam_hip_set_closure_passes); graphs within one pass create their handle exactly as before
+    if (1 + (int)lms_.size() * TR::ld + closures * TR::d > 28) check(gpslam_hip_set_closure_passes(h_, 32, 0), "set_closure_passes");
     check(gpslam_hip_compile(h_), "compile");
     gpslam_hip_default_params(&p_);
     p_.use_lm = use_lm ? 1 : 0;

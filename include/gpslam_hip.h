@@ -79,7 +79,8 @@ enum {
  * last_trial_error; GPSLAM_E_COMM; plan bits 64, 128) -- shipped without a version symbol; 2.0 this header: gpslam_hip_config_v2 +
  * gpslam_hip_create_v2 (named fields, struct_size first), gpslam_hip_abi_version, gpslam_hip_struct_size.  The v1 config and
  * gpslam_hip_create stay, bit for bit; 2.1 gpslam_hip_add_between_pairs (loop closures); 2.2 gpslam_hip_set_level0_stamps; 2.3
- * gpslam_hip_marginals, gpslam_hip_get_marginals, gpslam_hip_interpolate_covariances; 2.4 gpslam_hip_launch_census.  A MAJOR bump changes a struct or a
+ * gpslam_hip_marginals, gpslam_hip_get_marginals, gpslam_hip_interpolate_covariances; 2.4 gpslam_hip_launch_census (and, added since without a bump,
+ * gpslam_hip_set_closure_passes / gpslam_hip_closure_info).  A MAJOR bump changes a struct or a
  * signature, a MINOR bump only adds. */
 #define GPSLAM_HIP_ABI_MAJOR 2
 #define GPSLAM_HIP_ABI_MINOR 4
@@ -220,12 +221,24 @@ int gpslam_hip_add_between(gpslam_hip_handle *h, int32_t count, const int32_t *l
  * they form; here everything but closures couples state i with i + 1, and a closure is applied to the chain solve as a low-rank
  * correction: its d whitened rows ride through the block-tridiagonal solver as d extra right-hand sides behind the landmark
  * columns (Sherman-Morrison-Woodbury; kernels.hpp "loop closures").  Pairs with second == first + 1 are ordinary chain factors
- * (add_between).  Capacity: 1 + landmarks * landmark_dim + closures * d <= 28 right-hand sides (Pose2 / Rot3 / Linear3: 9 closures
- * without landmarks, Pose3: 4); compile() answers GPSLAM_E_UNSUPPORTED beyond that, on fp32 handles, on sharded handles and on
+ * (add_between).  Capacity of one pass: 1 + landmarks * landmark_dim + closures * d <= 28 right-hand sides (Pose2 / Rot3 / Linear3:
+ * 9 closures without landmarks, Pose3: 4); compile() answers GPSLAM_E_UNSUPPORTED beyond that unless gpslam_hip_set_closure_passes
+ * allowed column passes (then closures * d <= 120: 40 closures, Pose3: 20), and always on fp32 handles, on sharded handles and on
  * the segmented landmark path.  measured: count x pose_dim, sigmas: count x d.  Gauss-Newton, Levenberg-Marquardt, optimize and
  * error include the closures; gpslam_hip_normal_equations reports the chain part H0 (the closures' blocks are not in D / O / g). */
 int gpslam_hip_add_between_pairs(gpslam_hip_handle *h, int32_t count, const int32_t *first, const int32_t *second,
                                  const double *measured, const double *sigmas);
+/* Loop closures beyond one border: column passes.  Call before compile().  max_passes <= 1 (the default) leaves the capacity above
+ * as it is.  With max_passes >= 2 compile() deals the closures, in the order they were added, into P = ceil(closures / w) slices of
+ * w closures -- closures_per_pass if that is > 0, else the most that fit: 1 + landmarks * landmark_dim + w * d <= 28 -- and one linear
+ * solve becomes P passes of the chain solver over the closures' columns, a dense (closures * d)-square solve, and one final pass
+ * (kernels.hpp CloPass); the linearisation still runs once.  A graph whose closures fit one pass (P == 1) keeps the single-pass path
+ * bit for bit.  compile() answers GPSLAM_E_UNSUPPORTED when the landmark columns leave no room for a closure, when
+ * closures_per_pass is larger than fits, when P > max_passes and when closures * d > 120; fp32, sharded and segmented handles
+ * refuse closures as before.  gpslam_hip_marginals answers GPSLAM_E_UNSUPPORTED on a handle with P > 1. */
+int gpslam_hip_set_closure_passes(gpslam_hip_handle *h, int32_t max_passes, int32_t closures_per_pass);
+/* after compile(): {closures, closures per pass w, column passes P, solves of the chain per linear system (P + 1 beyond one pass)} */
+int gpslam_hip_closure_info(gpslam_hip_handle *h, int32_t out4[4]);
 /* gtsam::PriorFactor<Point> on landmark idx (matlab/PlazaPose2.m:63) */
 int gpslam_hip_add_landmark_priors(gpslam_hip_handle *h, int32_t count, const int32_t *idx, const double *prior,
                                    const double *sigmas);

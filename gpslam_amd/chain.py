@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "gpslam_hip_set_meas_robust", "gpslam_hip_set_between_pairs_robust", "gpslam_hip_get_meas_weights",
     "gpslam_hip_get_between_pairs_weights", "gpslam_hip_robust_eval",
     "gpslam_hip_set_closure_passes", "gpslam_hip_closure_info",
+    "gpslam_hip_marginals_keep_closure_columns",
 ]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
@@ -541,6 +542,12 @@ class ChainSolver:
     def marginals(self):
         """gtsam::Marginals(graph, values) at the current states: computes Sigma = H^-1's blocks on the device (see get_marginals)."""
         return self._chk(self.lib.gpslam_hip_marginals(self._h), "marginals")
+
+    def marginals_keep_closure_columns(self, enable=True):
+        """Let marginals() run on a handle whose closures go in column passes (closure_info()["passes"] > 1): it then keeps the
+        closures' columns at every state, one more device buffer of about N * closures * d * b doubles.  Any time after create;
+        changes nothing on a handle within one pass.  enable=False restores the refusal and frees the buffer."""
+        return self._chk(self.lib.gpslam_hip_marginals_keep_closure_columns(self._h, 1 if enable else 0), "marginals_keep_closure_columns")
 
     def get_marginals(self, first=0, count=None, cross=False):
         """Blocks of the last marginals() call for states [first, first + count): S (count, b, b) = Sigma_{i,i} and S_next

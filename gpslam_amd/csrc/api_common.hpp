@@ -1,5 +1,5 @@
 // api_common.hpp -- what the translation units of the library's host side share (api.hip: the C ABI; api_impl64.hip / api_impl32.hip:
-// api_impl.inc + api_iterate.inc once per row precision; marginals.hip): the handle, the host helpers and the kernel launchers
+// api_impl.inc + api_iterate.inc once per row precision; marginals.hip, marginals_clo.hip): the handle, the host helpers and the kernel launchers
 // (round 3: api.hip was one 3.5-minute translation unit; the fp64 and fp32 halves compile side by side now)
 #pragma once
 // api.hip -- host side of libgpslam_hip.so: the opaque handle, the graph-compile pass and the C ABI
@@ -194,6 +194,10 @@ struct gpslam_hip_handle {
   bool marg_ok = false;
   int marg_N = 0;
   DevBuf mg_fac, mg_S, mg_Sn, mg_up, mg_K, mg_Slm, mg_Sxl;
+  // gpslam_hip_marginals_keep_closure_columns: on a handle in column passes (clo_P > 1) the marginals keep Z = A^-1 U^T at every
+  // state (mg_Z: mg_zrows(N, b) rows of mg_ldz(nc) doubles) and the inverse of I + U Z (mg_Minv: mg_ldz(nc) squared)
+  bool mg_keep_z = false;
+  DevBuf mg_Z, mg_Minv;
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch
@@ -203,6 +207,8 @@ struct gpslam_hip_handle {
 
 // frees the marginals' buffers (destroy; compile when N changed)
 void marginals_release(gpslam_hip_handle *h);
+// the closure term of the marginals on a handle in column passes (marginals_clo.hip)
+int marginals_closure_term(gpslam_hip_handle *h);
 
 // What the launches of one call do: each entry point builds the mode it means and hands it to the launch helpers.
 // LaunchMode{}: row tables (d = 3 records where the graph has them), level 0 unfused, every reduction at once, untimed.

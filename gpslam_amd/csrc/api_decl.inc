@@ -38,3 +38,5 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
 // lambda = 0 (forward, backward, closure correction) and the landmark Schur complement, without the landmark solve
 int marginals_assemble(gpslam_hip_handle *h);
 int marginals_border(gpslam_hip_handle *h);
+// ... and on a handle in column passes: every slice of Z kept in h->mg_Z on the way (gpslam_hip_marginals_keep_closure_columns)
+int marginals_border_passes(gpslam_hip_handle *h);

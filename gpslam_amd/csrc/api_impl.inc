@@ -1823,6 +1823,39 @@ int marginals_border(gpslam_hip_handle *h) {
   if ((rc = launch_closures(h))) return rc;
   return launch_landmarks_reduce(h, 0.0);
 }
+// The same on a handle whose closures go through the solver in column passes (clo_P > 1; gpslam_hip_marginals_keep_closure_columns):
+// launch_solve_passes at lambda = 0, every pass's slice of Z = A^-1 U^T copied into h->mg_Z behind its backward sweep, and the
+// landmark reduction alone at the end.  Leaves W = U [X | Z] in clo_W (k_mg_clo_inverse forms I + U Z from it) and the corrected
+// landmark columns in the leading columns of the level-0 solution.
+int marginals_border_passes(gpslam_hip_handle *h) {
+  int rc;
+  const LaunchMode m{};
+  const CloArgs a = clo_args(h);
+  const int P = h->clo_P, nlead = h->N * a.ncols * h->b, ldz = mg_ldz(h->nc);
+  for (int p = 0; p < P; p++) {
+    if (p > 0 && (rc = launch_assemble(h, m, false, p))) return rc;
+    if ((rc = launch_forward(h, m, 0.0))) return rc;
+    if ((rc = launch_backward(h, nullptr))) return rc;
+    const CloPass cp = clo_pass(h, p);
+    const int entries = h->nc * ((cp.lead ? a.ncols : 0) + (cp.k1 - cp.k0) * h->d);
+    const size_t kept = (size_t)h->N * (cp.k1 - cp.k0) * h->d * h->b;
+    dispatch_b(h->b, [&](auto tag) {
+      constexpr int D = decltype(tag)::value / 2;
+      k_mg_keep_z<D><<<dim3((unsigned)((kept + 255) / 256)), dim3(256), 0, h->stream>>>(a, cp, h->mg_Z.as<double>(), ldz);
+      if (p == 0) k_clo_save<D><<<dim3(nblocks(nlead, 256)), dim3(256), 0, h->stream>>>(a, cp);
+      k_clo_gather<D><<<dim3(nblocks(entries, 256)), dim3(256), 0, h->stream>>>(a, cp);
+    });
+  }
+  const CloPass cp = clo_pass(h, 0);
+  const size_t smem = ((size_t)h->nc * (h->nc + 1) + (size_t)h->nc * a.ncols) * sizeof(double);
+  dispatch_b(h->b, [&](auto tag) { k_clo_solve_wide<decltype(tag)::value / 2><<<dim3(1), dim3(256), smem, h->stream>>>(a, cp); });
+  if ((rc = launch_assemble(h, m, false, P))) return rc;
+  if ((rc = launch_forward(h, m, 0.0))) return rc;
+  if ((rc = launch_backward(h, nullptr))) return rc;
+  dispatch_b(h->b, [&](auto tag) { k_clo_add<decltype(tag)::value / 2><<<dim3(nblocks(nlead, 256)), dim3(256), 0, h->stream>>>(a, cp); });
+  HIPCHK(hipGetLastError());
+  return launch_landmarks_reduce(h, 0.0);
+}
 
 // whitened Jacobian rows of the current linearisation, in row-table order (rows grouped by left state; inside a
 // state: GP priors, pose priors, velocity priors, between, then the measurement kinds in FKind order)

@@ -9,7 +9,8 @@
 //   (c) landmarks and closures as one low-rank term: the existing solver's right-hand sides give Y = [W | Z] (the landmark
 //       columns corrected for the closures, H_xx^-1 B, and the closure columns A^-1 J_c^T), its landmark reduction the Schur
 //       complement S = H_LL - B^T H_xx^-1 B; then Sigma_xx = A^-1 + Y K Y^T with K = blkdiag(S^-1, -(I + J_c Z)^-1),
-//       Sigma_LL = S^-1, Sigma_xL = -W S^-1 (k_mg_core, k_mg_finish);
+//       Sigma_LL = S^-1, Sigma_xL = -W S^-1 (k_mg_core, k_mg_finish); on a handle whose closures go in column passes (clo_P > 1,
+//       gpslam_hip_marginals_keep_closure_columns) Z is kept slice by slice and its term has kernels of its own (marginals_clo.hip);
 //   (d) batched posterior covariances of GP-interpolated poses (k_mg_interp behind k_interp_query's H1..H4).
 // fp64 only; no atomics, every sum in a fixed order: two calls give bit-identical blocks.
 #include "api_common.hpp"
@@ -347,7 +348,8 @@ int mg_refuse(gpslam_hip_handle *h) {
   if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: sharded handles are not supported");
   if (h->fs.active && h->fs.split) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: split pieces are not supported");
   if (h->fs.active) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: the segmented landmark path is not supported");
-  if (h->clo_P > 1) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: loop closures in more than one column pass (set_closure_passes) are not supported: Z = H0^-1 U^T is not kept at every state");
+  if (h->clo_P > 1 && !h->mg_keep_z)
+    return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: loop closures in more than one column pass (set_closure_passes) are not supported: Z = H0^-1 U^T is not kept at every state (unless gpslam_hip_marginals_keep_closure_columns asks for it)");
   return 0;
 }
 
@@ -359,12 +361,23 @@ int mg_stale(gpslam_hip_handle *h) {
 }  // namespace
 
 void marginals_release(gpslam_hip_handle *h) {
-  for (DevBuf *b : {&h->mg_fac, &h->mg_S, &h->mg_Sn, &h->mg_up, &h->mg_K, &h->mg_Slm, &h->mg_Sxl}) b->release();
+  for (DevBuf *b : {&h->mg_fac, &h->mg_S, &h->mg_Sn, &h->mg_up, &h->mg_K, &h->mg_Slm, &h->mg_Sxl, &h->mg_Z, &h->mg_Minv}) b->release();
   h->marg_ok = false;
   h->marg_N = 0;
 }
 
 extern "C" {
+
+int gpslam_hip_marginals_keep_closure_columns(gpslam_hip_handle *h, int32_t enable) {
+  if (!h) return GPSLAM_E_INVALID;
+  h->marg_ok = false;
+  h->mg_keep_z = enable != 0;
+  if (!h->mg_keep_z) {
+    h->mg_Z.release();
+    h->mg_Minv.release();
+  }
+  return 0;
+}
 
 int gpslam_hip_marginals(gpslam_hip_handle *h) {
   int rc = need_compiled(h);
@@ -387,6 +400,14 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
   HIPCHK(h->mg_K.reserve((size_t)std::max(m * m, 1) * sizeof(double)));
   HIPCHK(h->mg_Slm.reserve((size_t)std::max(h->nl * h->nl, 1) * sizeof(double)));
   HIPCHK(h->mg_Sxl.reserve((size_t)std::max(N * B * h->nl, 1) * sizeof(double)));
+  const bool passes = h->clo_P > 1;     // (mg_refuse: only with gpslam_hip_marginals_keep_closure_columns)
+  const int ldz = mg_ldz(h->nc);
+  if (passes) {
+    const size_t zbytes = mg_zrows(N, B) * ldz * sizeof(double);
+    HIPCHK(h->mg_Z.reserve(zbytes));
+    HIPCHK(h->mg_Minv.reserve((size_t)ldz * ldz * sizeof(double)));
+    HIPCHK(hipMemsetAsync(h->mg_Z.p, 0, zbytes, h->stream));   // the padding rows and columns: k_mg_clo_finish reads them
+  }
   h->marg_N = N;
   HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
   if ((rc = impl64::marginals_assemble(h))) return rc;
@@ -426,7 +447,19 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
   }
   HIPCHK(hipGetLastError());
   // (c) landmarks and closures: Y = [W | Z] and S from the solver's own right-hand sides, then K
-  if (m > 0) {
+  if (m > 0 && passes) {
+    // closures in column passes: Z slice by slice into mg_Z, then - Z M^-1 Z^T on its own; what is left for k_mg_core and
+    // k_mg_finish is the landmark term (W in the leading columns of the level-0 solution, K = S^-1)
+    if ((rc = impl64::marginals_border_passes(h))) return rc;
+    if ((rc = marginals_closure_term(h))) return rc;
+    if (h->nl > 0) {
+      MgCore c;
+      c.S = h->lm_S.as<double>(); c.cloA = nullptr; c.first = nullptr; c.second = nullptr;
+      c.x = h->lv[0].x.as<double>(); c.nl = h->nl; c.nclo = 0; c.R = R; c.B = B;
+      c.K = h->mg_K.as<double>(); c.Slm = h->mg_Slm.as<double>(); c.flag = h->flag.as<int>();
+      dispatch_b(B, [&](auto tag) { k_mg_core<decltype(tag)::value / 2><<<dim3(1), dim3(64), 0, h->stream>>>(c); });
+    }
+  } else if (m > 0) {
     if ((rc = impl64::marginals_border(h))) return rc;
     MgCore c;
     c.S = h->lm_S.as<double>(); c.cloA = h->clo_A.as<double>(); c.first = h->clo.d_idx.as<int>(); c.second = h->d_clo_second.as<int>();
@@ -435,11 +468,12 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
     dispatch_b(B, [&](auto tag) { k_mg_core<decltype(tag)::value / 2><<<dim3(1), dim3(64), 0, h->stream>>>(c); });
   }
   const bool pad = h->mf == ROT3_BIAS;
-  if (m > 0 || pad) {
+  const int mfin = passes ? h->nl : m;   // the columns k_mg_finish adds: [W | Z], or W alone behind k_mg_clo_finish
+  if (mfin > 0 || pad) {
     MgFinish f;
     f.Sd = h->mg_S.as<double>(); f.Sn = h->mg_Sn.as<double>(); f.Sxl = h->mg_Sxl.as<double>();
     f.x = h->lv[0].x.as<double>(); f.K = h->mg_K.as<double>();
-    f.N = N; f.R = R; f.m = m; f.nl = h->nl;
+    f.N = N; f.R = R; f.m = mfin; f.nl = h->nl;
     f.pad0 = pad ? 9 : 0; f.npad = pad ? 3 : 0;
     dispatch_b(B, [&](auto tag) { k_mg_finish<decltype(tag)::value><<<dim3(nblocks(N * B, 256)), dim3(256), 0, h->stream>>>(f); });
   }

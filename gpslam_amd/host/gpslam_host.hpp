@@ -902,6 +902,8 @@ class Marginals {
  public:
   Marginals(const NonlinearFactorGraph &graph, const Values &values) {
     s_.build(graph, values);
+    // (closures in column passes: who constructs Marginals has asked for the closures' columns to be kept at every state)
+    detail::check(gpslam_hip_marginals_keep_closure_columns(s_.h, 1), s_.h, "marginals_keep_closure_columns");
     detail::check(gpslam_hip_marginals(s_.h), s_.h, "marginals");
   }
   /// Marginals::marginalCovariance(variable)

@@ -80,7 +80,7 @@ enum {
  * gpslam_hip_create_v2 (named fields, struct_size first), gpslam_hip_abi_version, gpslam_hip_struct_size.  The v1 config and
  * gpslam_hip_create stay, bit for bit; 2.1 gpslam_hip_add_between_pairs (loop closures); 2.2 gpslam_hip_set_level0_stamps; 2.3
  * gpslam_hip_marginals, gpslam_hip_get_marginals, gpslam_hip_interpolate_covariances; 2.4 gpslam_hip_launch_census (and, added since without a bump,
- * gpslam_hip_set_closure_passes / gpslam_hip_closure_info).  A MAJOR bump changes a struct or a
+ * gpslam_hip_set_closure_passes / gpslam_hip_closure_info / gpslam_hip_marginals_keep_closure_columns).  A MAJOR bump changes a struct or a
  * signature, a MINOR bump only adds. */
 #define GPSLAM_HIP_ABI_MAJOR 2
 #define GPSLAM_HIP_ABI_MINOR 4
@@ -235,7 +235,8 @@ int gpslam_hip_add_between_pairs(gpslam_hip_handle *h, int32_t count, const int3
  * (kernels.hpp CloPass); the linearisation still runs once.  A graph whose closures fit one pass (P == 1) keeps the single-pass path
  * bit for bit.  compile() answers GPSLAM_E_UNSUPPORTED when the landmark columns leave no room for a closure, when
  * closures_per_pass is larger than fits, when P > max_passes and when closures * d > 120; fp32, sharded and segmented handles
- * refuse closures as before.  gpslam_hip_marginals answers GPSLAM_E_UNSUPPORTED on a handle with P > 1. */
+ * refuse closures as before.  gpslam_hip_marginals answers GPSLAM_E_UNSUPPORTED on a handle with P > 1 unless
+ * gpslam_hip_marginals_keep_closure_columns was called on it. */
 int gpslam_hip_set_closure_passes(gpslam_hip_handle *h, int32_t max_passes, int32_t closures_per_pass);
 /* after compile(): {closures, closures per pass w, column passes P, solves of the chain per linear system (P + 1 beyond one pass)} */
 int gpslam_hip_closure_info(gpslam_hip_handle *h, int32_t out4[4]);
@@ -420,6 +421,16 @@ int gpslam_hip_interpolate_poses_jac(gpslam_hip_handle *h, int32_t count, const 
  * low-rank term) and kept there.  GPSLAM_E_UNSUPPORTED on fp32 handles, sharded handles, split pieces and the segmented landmark
  * path; GPSLAM_E_NOT_SPD when H is indeterminate (e.g. nothing anchors the chain), as iterate_gn. */
 int gpslam_hip_marginals(gpslam_hip_handle *h);
+/* Marginals on a handle whose closures go through the solver in column passes (gpslam_hip_set_closure_passes, P > 1).  There only
+ * one slice of Z = A^-1 U^T (A the chain part of H, U the nc = closures * d whitened closure rows) exists at a time, and
+ * gpslam_hip_marginals refuses.  enable != 0 lets it run: it then keeps Z at every state in one more device buffer of
+ *     (ceil(N * b / 48) * 48 + 16) * (ceil(nc / 16) * 16) doubles  ~  N * nc * b * 8 bytes
+ * (1.15 GB at 1e5 Pose3 states with 20 closures; allocated inside gpslam_hip_marginals, freed by enable == 0 and by destroy) and
+ * forms Sigma_xx = A^-1 + W S^-1 W^T - Z M^-1 Z^T, M = I + 1/2 (U Z + (U Z)^T), with the closure term on the fp64 matrix cores
+ * (marginals.hip: k_mg_clo_inverse, k_mg_clo_finish).  Callable any time after create, no new compile() is needed; marginals held
+ * from before are stale.  enable == 0 (the default) restores the refusal.  On a handle with P <= 1 the call is accepted and
+ * changes nothing.  GPSLAM_E_INVALID on a NULL handle.  The fp32, sharded, split and segmented refusals stay. */
+int gpslam_hip_marginals_keep_closure_columns(gpslam_hip_handle *h, int32_t enable);
 /* copies the window [first, first + count) of S / S_next / S_x_lm (count x b x b, count x b x b, count x b x nl), and S_lm; any pointer
  * may be NULL.  GPSLAM_E_INVALID ("stale") before gpslam_hip_marginals, or after any call that can change states, landmarks,
  * factors or Qc since: set_states, set_landmarks, set_qc, add_*, set_meas_covariance, set_*_robust, clear_factors, compile, iterate_gn, iterate_lm,

@@ -151,11 +151,11 @@ int gpslam_hip_destroy(gpslam_hip_handle *h) {
                     &h->lmrow_state, &h->lmrow_ptr, &h->lm_t, &h->lm_S, &h->lm_dL, &h->lm_chunk_lm, &h->lm_chunk_j0, &h->lm_chunk_j1, &h->lm_chunk_ptr, &h->lm_part, &h->gsave, &h->dvec,
                     &h->halo_add, &h->iface_send, &h->iface_recv, &h->top_blk, &h->top_x, &h->scal, &h->flag,
                     &h->api_e, &h->api_H, &h->gps, &h->gpidx, &h->dU, &h->gsave2, &h->partial2, &h->brec, &h->btwidx,
-                    &h->rowI, &h->irowptr, &h->coll_s, &h->coll_r, &h->d_clo_second, &h->clo_A, &h->clo_Y, &h->simd_cnt,
-                    &h->d_clo_rob, &h->clo_w, &h->clo_W, &h->clo_X};
+                    &h->rowI, &h->irowptr, &h->coll_s, &h->coll_r, &h->simd_cnt};
   for (DevBuf *b : bufs) b->release();
   marginals_release(h);
-  for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri, &h->clo}) s->release();
+  for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri}) s->release();
+  h->clo.release();
   for (MeasSet &s : h->ms) s.release();
   h->fs.release();
   h->lm_gL.release();
@@ -383,7 +383,7 @@ int gpslam_hip_set_meas_robust(gpslam_hip_handle *h, int32_t kind, int32_t count
 }
 int gpslam_hip_set_between_pairs_robust(gpslam_hip_handle *h, int32_t count, const int32_t *loss, const double *k) {
   if (!h) return GPSLAM_E_INVALID;
-  return set_robust(h, h->clo_rob, h->clo.count(), count, loss, k, "set_between_pairs_robust");
+  return set_robust(h, h->clo.rob, h->clo.fac.count(), count, loss, k, "set_between_pairs_robust");
 }
 int gpslam_hip_robust_eval(int32_t loss, double k, double r, double *w, double *rho) {
   if (!w || !rho || loss < GPSLAM_ROBUST_NONE || loss > GPSLAM_ROBUST_FAIR) return GPSLAM_E_INVALID;
@@ -421,12 +421,12 @@ int gpslam_hip_add_between_pairs(gpslam_hip_handle *h, int32_t count, const int3
       continue;
     }
     if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "loop closures on a sharded handle (nranks > 1): both states must live on one rank");
-    h->clo.width = h->pd;
-    h->clo.idx.push_back(first[k]);
-    h->clo_second.push_back(second[k]);
-    h->clo.meas.insert(h->clo.meas.end(), m, m + h->pd);
-    h->clo.sig.insert(h->clo.sig.end(), sg, sg + h->d);
-    if (!h->clo_rob.empty()) h->clo_rob.insert(h->clo_rob.end(), 2, 0.0);
+    h->clo.fac.width = h->pd;
+    h->clo.fac.idx.push_back(first[k]);
+    h->clo.second.push_back(second[k]);
+    h->clo.fac.meas.insert(h->clo.fac.meas.end(), m, m + h->pd);
+    h->clo.fac.sig.insert(h->clo.fac.sig.end(), sg, sg + h->d);
+    if (!h->clo.rob.empty()) h->clo.rob.insert(h->clo.rob.end(), 2, 0.0);
   }
   h->compiled = false;
   h->marg_ok = false;
@@ -435,8 +435,8 @@ int gpslam_hip_add_between_pairs(gpslam_hip_handle *h, int32_t count, const int3
 int gpslam_hip_set_closure_passes(gpslam_hip_handle *h, int32_t max_passes, int32_t closures_per_pass) {
   if (!h) return GPSLAM_E_INVALID;
   if (closures_per_pass < 0) return fail(h, GPSLAM_E_INVALID, "set_closure_passes: closures_per_pass must not be negative (0: as many as fit)");
-  h->clo_max_passes = max_passes < 1 ? 1 : max_passes;
-  h->clo_per_pass = closures_per_pass;
+  h->clo.max_passes = max_passes < 1 ? 1 : max_passes;
+  h->clo.per_pass = closures_per_pass;
   h->compiled = false;
   h->marg_ok = false;
   return 0;
@@ -446,7 +446,7 @@ int gpslam_hip_closure_info(gpslam_hip_handle *h, int32_t out4[4]) {
   if (rc) return rc;
   if (!out4) return GPSLAM_E_INVALID;
   // solves of the chain per linear system: one per column pass and, beyond one pass, the final one
-  const int32_t v[4] = {h->nclo, h->clo_slice, h->clo_P, h->clo_P > 1 ? h->clo_P + 1 : 1};
+  const int32_t v[4] = {h->clo.n, h->clo.slice, h->clo.P, h->clo.P > 1 ? h->clo.P + 1 : 1};
   for (int i = 0; i < 4; i++) out4[i] = v[i];
   return 0;
 }
@@ -540,9 +540,9 @@ int gpslam_hip_add_bearing_range(gpslam_hip_handle *h, int32_t count, const int3
 int gpslam_hip_clear_factors(gpslam_hip_handle *h) {
   if (!h) return GPSLAM_E_INVALID;
   h->gp_left.clear(); h->gp_dt.clear(); h->gp_q.clear(); h->gp_Utab.clear(); h->gp_perm.clear(); h->gp_groups.clear();
-  for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri, &h->clo}) { s->idx.clear(); s->meas.clear(); s->sig.clear(); }
-  h->clo_second.clear();
-  h->clo_rob.clear();
+  for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri, &h->clo.fac}) { s->idx.clear(); s->meas.clear(); s->sig.clear(); }
+  h->clo.second.clear();
+  h->clo.rob.clear();
   for (MeasSet &s : h->ms) {
     s.rob.clear();
     s.idx.clear(); s.lm.clear(); s.meas.clear(); s.sig.clear(); s.dt.clear(); s.tau.clear(); s.aux.clear(); s.aidx.clear(); s.sqi.clear();

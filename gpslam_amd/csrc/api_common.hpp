@@ -1,5 +1,5 @@
 // api_common.hpp -- what the translation units of the library's host side share (api.hip: the C ABI; api_impl64.hip / api_impl32.hip:
-// api_impl.inc + api_iterate.inc once per row precision; marginals.hip, marginals_clo.hip): the handle, the host helpers and the kernel launchers
+// api_impl.inc + api_iterate.inc once per row precision; closures.hip, marginals.hip, marginals_clo.hip): the handle, the host helpers and the kernel launchers
 // (round 3: api.hip was one 3.5-minute translation unit; the fp64 and fp32 halves compile side by side now)
 #pragma once
 // api.hip -- host side of libgpslam_hip.so: the opaque handle, the graph-compile pass and the C ABI
@@ -21,6 +21,7 @@
 
 #include "devbuf.hpp"
 #include "kernels.hpp"
+#include "closures.hpp"
 #include "fatsep.hpp"
 #include "upper.hpp"
 
@@ -62,6 +63,21 @@ struct MeasSet {  // measurement factors (kernels.hpp FKind)
   DevBuf d_irow0;                      // first row of each factor in the table of 16-double interpolated rows (Plan::lines)
   int count() const { return (int)idx.size(); }
   void release() { d_idx.release(); d_lm.release(); d_meas.release(); d_sig.release(); d_coef.release(); d_row0.release(); d_aux.release(); d_aidx.release(); d_sqi.release(); d_irow0.release(); d_rob.release(); d_w.release(); }
+};
+
+// loop closures (gpslam_hip_add_between_pairs; closures.hpp, launched by closures.hip): fac.idx = first state, second = second state
+struct Closures {
+  SimpleSet fac;
+  std::vector<int32_t> second;
+  DevBuf d_second, A, Y;
+  std::vector<double> rob;            // noiseModel::Robust on closures (gpslam_hip_set_between_pairs_robust): as MeasSet::rob
+  DevBuf d_rob, w;
+  int n = 0, nc = 0;          // closures of the compiled graph, their right-hand-side columns (n * d)
+  // closures in column passes (gpslam_hip_set_closure_passes; closures.hpp CloPass): the caller's two numbers, and what compile() made
+  // of them -- P > 1: slices of `slice` closures, W = U [X | Z] and pass 0's X kept between the passes
+  int max_passes = 1, per_pass = 0, slice = 0, P = 0;
+  DevBuf W, X;
+  void release() { fac.release(); for (DevBuf *b : {&d_second, &A, &Y, &d_rob, &w, &W, &X}) b->release(); }
 };
 
 // Which kernels serve a compiled graph, and in which form.  make_plan() (api_impl.inc) fills one per compile(), once the row layout
@@ -130,18 +146,7 @@ struct gpslam_hip_handle {
   int gp_single_q = 0;      // > 0: every GP prior came through add_gp_priors_qc with the SAME Qc (entry gp_single_q - 1 of gp_Utab):
                             // one group, one launch, and the structured-record path of k_fused_level0 stays available
   SimpleSet pri, vpri, btw, lpri;
-  // loop closures (gpslam_hip_add_between_pairs; kernels.hpp "loop closures"): clo.idx = first state, clo_second = second state
-  SimpleSet clo;
-  std::vector<int32_t> clo_second;
-  DevBuf d_clo_second, clo_A, clo_Y;
-  std::vector<double> clo_rob;        // noiseModel::Robust on closures (gpslam_hip_set_between_pairs_robust): as MeasSet::rob
-  DevBuf d_clo_rob, clo_w;
-  int nclo = 0, nc = 0;       // closures of the compiled graph, their right-hand-side columns (nclo * d)
-  // closures in column passes (gpslam_hip_set_closure_passes; kernels.hpp CloPass): the caller's two numbers, and what compile() made
-  // of them -- clo_P > 1: slices of clo_slice closures, W = U [X | Z] and pass 0's X kept between the passes
-  int clo_max_passes = 1, clo_per_pass = 0;
-  int clo_slice = 0, clo_P = 0;
-  DevBuf clo_W, clo_X;
+  Closures clo;
   MeasSet ms[kNumMeasKinds];
   // row table
   int M = 0;
@@ -194,8 +199,8 @@ struct gpslam_hip_handle {
   bool marg_ok = false;
   int marg_N = 0;
   DevBuf mg_fac, mg_S, mg_Sn, mg_up, mg_K, mg_Slm, mg_Sxl;
-  // gpslam_hip_marginals_keep_closure_columns: on a handle in column passes (clo_P > 1) the marginals keep Z = A^-1 U^T at every
-  // state (mg_Z: mg_zrows(N, b) rows of mg_ldz(nc) doubles) and the inverse of I + U Z (mg_Minv: mg_ldz(nc) squared)
+  // gpslam_hip_marginals_keep_closure_columns: on a handle in column passes (clo.P > 1) the marginals keep Z = A^-1 U^T at every
+  // state (mg_Z: mg_zrows(N, b) rows of mg_ldz(clo.nc) doubles) and the inverse of I + U Z (mg_Minv: mg_ldz(clo.nc) squared)
   bool mg_keep_z = false;
   DevBuf mg_Z, mg_Minv;
   std::string err;
@@ -225,6 +230,23 @@ struct LaunchMode {
   bool l0_events = false;
   bool weights = false;       // an error-only pass that also stores every robust factor's weight w(r) (MeasArgs::out_w, CloArgs::out_w)
 };
+
+// Loop closures (closures.hip; fp64 only: both precision namespaces call these, and compile() refuses closures on an fp32 handle).
+// closures_upload: compile()'s share -- the factor set to the device, the buffers sized.  closures_eval: the records [A_i | A_j | r]
+// (pass 0) and the closures' error into partial[0], on stream st.  closures_inject: behind the assembly, slice `pass` of the columns
+// of U^T into the records (U^T r into the gradient copy if save_g); pass == P in column passes: the final pass's right-hand sides
+// U^T Y.  closures_correct: one pass -- Y = (I + U Z)^-1 ([r | 0] - U X) and X += Z Y, between the chain's back-substitution and the
+// landmark Schur complement.  Column passes (launch_solve_passes, api_impl.inc): closures_collect behind pass p's backward sweep
+// (keep_z: the slice of Z into h->mg_Z first; pass 0: X saved; W gathered; behind the last pass the wide solve for Y),
+// closures_add behind the final pass.
+int closures_upload(gpslam_hip_handle *h);
+void closures_eval(gpslam_hip_handle *h, const LaunchMode &m, int pass, double *partial, hipStream_t st);
+void closures_inject(gpslam_hip_handle *h, bool save_g, int pass);
+int closures_correct(gpslam_hip_handle *h);
+void closures_collect(gpslam_hip_handle *h, int p, bool keep_z);
+int closures_add(gpslam_hip_handle *h);
+// row length of W = U [X | Z] (CloPass::ldw)
+inline int clo_ldw(const gpslam_hip_handle *h) { return 1 + h->nl + h->clo.nc; }
 
 #define HIPCHK(call)                                                                          \
   do {                                                                                        \
@@ -305,6 +327,12 @@ template <typename V> int upload(gpslam_hip_handle *h, DevBuf &buf, const std::v
   }
   return 0;
 }
+// a SimpleSet's arrays (row0: the first row of each factor in its row table, or empty)
+inline int upload_set(gpslam_hip_handle *h, SimpleSet &s, const std::vector<int> &row0) {
+  int rc;
+  if ((rc = upload(h, s.d_idx, s.idx)) || (rc = upload(h, s.d_meas, s.meas)) || (rc = upload(h, s.d_sig, s.sig))) return rc;
+  return upload(h, s.d_row0, row0);
+}
 inline int nblocks(int n, int bs) { return (n + bs - 1) / bs; }
 
 // ---- manifold / block-size dispatch: call f(std::integral_constant<int, X>{}) for the runtime value
@@ -344,7 +372,7 @@ bool has_right_rank(const gpslam_hip_handle *h) { return sharded(h) && h->cfg.ra
 
 // some measurement factor or closure carries a loss (noiseModel::Robust)
 bool any_robust(const gpslam_hip_handle *h) {
-  bool any = !h->clo_rob.empty();
+  bool any = !h->clo.rob.empty();
   for (const MeasSet &s : h->ms) any = any || !s.rob.empty();
   return any;
 }

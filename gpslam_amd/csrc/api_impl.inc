@@ -65,43 +65,6 @@ LmArgs<Real, RowT> lm_args(gpslam_hip_handle *h, double lambda) {
   return a;
 }
 
-// loop closures (kernels.hpp "loop closures"; fp64 handles only: compile() refuses the others)
-CloArgs clo_args(gpslam_hip_handle *h) {
-  CloArgs a;
-  a.pose = h->pose.as<double>(); a.stride = h->stride; a.count = h->nclo; a.chart = h->cfg.chart;
-  a.first = h->clo.d_idx.as<int>(); a.second = h->d_clo_second.as<int>();
-  a.meas = h->clo.d_meas.as<double>(); a.sig = h->clo.d_sig.as<double>();
-  a.A = h->clo_A.as<double>(); a.partial = nullptr;
-  a.rob = h->clo_rob.empty() ? nullptr : h->d_clo_rob.as<double>();
-  a.blk = h->lv.empty() ? nullptr : h->lv[0].blk.as<double>();
-  a.BS = 2 * h->b * h->b + h->b * h->R; a.B = h->b; a.R = h->R; a.col0 = 1 + h->nl;
-  a.gsave = nullptr;
-  a.x = h->lv.empty() ? nullptr : h->lv[0].x.as<double>();
-  a.N = h->N; a.ncols = 1 + h->nl; a.Y = h->clo_Y.as<double>(); a.flag = h->flag.as<int>();
-  return a;
-}
-// closures in column passes: slice p of the compiled graph's closures, and what the pass kernels share
-CloPass clo_pass(gpslam_hip_handle *h, int p) {
-  CloPass c;
-  c.k0 = std::min(p * h->clo_slice, h->nclo); c.k1 = std::min(c.k0 + h->clo_slice, h->nclo);
-  c.lead = p == 0 ? 1 : 0;
-  c.W = h->clo_W.as<double>(); c.ldw = 1 + h->nl + h->nc;
-  c.X = h->clo_X.as<double>();
-  return c;
-}
-// Y = (I + U Z)^-1 ([r | 0] - U X) and X += Z Y, between the chain's back-substitution and the landmark Schur complement
-int launch_closures(gpslam_hip_handle *h) {
-  if (h->nclo <= 0) return 0;
-  CloArgs a = clo_args(h);
-  dispatch_b(h->b, [&](auto tag) {
-    constexpr int D = decltype(tag)::value / 2;
-    k_clo_solve<D><<<dim3(1), dim3(64), 0, h->stream>>>(a);
-    k_clo_correct<D><<<dim3(nblocks(h->N * h->b, 256)), dim3(256), 0, h->stream>>>(a);
-  });
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot);
 // pass 0: Jacobian rows + error, 1: error only.  Error partial sums land in h->partial, reduced into scal[slot].
 // e32 (the fp64 instantiation serving an fp32 handle, pass 1): the error pass also deposits its whitened errors as the
@@ -301,15 +264,8 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
     });
     off += nb;
   }
-  if (kIsF64 && h->nclo > 0) {   // loop closures: records [A_i | A_j | r] (Jacobian pass) and their error
-    CloArgs a = clo_args(h);
-    a.partial = reinterpret_cast<double *>(part + off);   // (RowT == double here)
-    a.out_w = (m.weights && a.rob) ? h->clo_w.as<double>() : nullptr;
-    dispatch_mf(h->mf, [&](auto tag) {
-      constexpr int MF = decltype(tag)::value;
-      if (pass == 0) k_clo_eval<MF, true><<<dim3(1), dim3(128), 0, side>>>(a);
-      else k_clo_eval<MF, false><<<dim3(1), dim3(128), 0, side>>>(a);
-    });
+  if (kIsF64 && h->clo.n > 0) {   // loop closures: records [A_i | A_j | r] (Jacobian pass) and their error
+    closures_eval(h, m, pass, reinterpret_cast<double *>(part + off), side);   // (RowT == double here)
     off += 1;
   }
   // (landmark priors have no Jacobian rows: on an fp32 handle their error belongs to the fp64 error pass alone)
@@ -342,7 +298,7 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
   return 0;
 }
 
-// pass (closures in column passes, clo_P > 1): which slice of the closures' columns the records take; pass == clo_P: the final
+// pass (closures in column passes, clo.P > 1): which slice of the closures' columns the records take; pass == clo.P: the final
 // pass, whose right-hand sides are U^T Y alone
 int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g, int pass = 0) {
   AsmArgs<Real, RowT> a;
@@ -368,20 +324,7 @@ int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g, int 
     const int waves = nblocks(nstates, 64 / BB - 1);
     k_assemble_ghost<Real, BB, 4, RowT><<<dim3(nblocks(waves, 4)), dim3(256), 0, h->stream>>>(a);   // 1 / 8 / 16 waves per block measured slower
   });
-  if (h->nclo > 0) {   // the closures' columns of U^T into the records of their states (and U^T r into the gradient copy)
-    CloArgs c = clo_args(h);
-    c.gsave = save_g ? h->gsave.as<double>() : nullptr;
-    if (h->clo_P > 1 && pass >= h->clo_P) {
-      dispatch_b(h->b, [&](auto tag) {
-        constexpr int D = decltype(tag)::value / 2;
-        k_clo_clear_lead<D><<<dim3(nblocks(h->N * c.ncols * h->b, 256)), dim3(256), 0, h->stream>>>(c);
-        k_clo_inject_y<D><<<dim3(1), dim3(256), 0, h->stream>>>(c);
-      });
-    } else {
-      const CloPass cp = clo_pass(h, pass);   // (one pass: every closure)
-      dispatch_b(h->b, [&](auto tag) { k_clo_inject<decltype(tag)::value / 2><<<dim3(1), dim3(256), 0, h->stream>>>(c, cp.k0, cp.k1); });
-    }
-  }
+  if (h->clo.n > 0) closures_inject(h, save_g, pass);   // the closures' columns of U^T into the records of their states
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1028,45 +971,38 @@ int fs_build(gpslam_hip_handle *h, const std::vector<int> &touch_lo, const std::
   return 0;
 }
 
-// Closures in column passes (clo_P > 1): the caller's assembly carried slice 0.  Every pass is the same factorisation at the same
-// lambda; the records are reassembled in front of each one because the elimination works in place.
-int launch_solve_passes(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
+// Closures in column passes (clo.P > 1): the caller's assembly carried slice 0.  Every pass is the same factorisation at the same
+// lambda; the records are reassembled in front of each one because the elimination works in place.  The marginals run the same
+// passes at lambda = 0 with keep_z (every pass's slice of Z = A^-1 U^T copied into h->mg_Z behind its backward sweep) and without
+// the landmark solve (the landmark reduction alone ends them: the states stay).  Leaves W = U [X | Z] in clo.W and the corrected
+// landmark columns in the leading columns of the level-0 solution.
+int launch_solve_passes(gpslam_hip_handle *h, const LaunchMode &m, double lambda, bool keep_z, bool solve_landmarks) {
   int rc;
-  const CloArgs a = clo_args(h);
-  const int P = h->clo_P, nlead = h->N * a.ncols * h->b;
+  const int P = h->clo.P;
   LaunchMode later = m;       // (a timed iteration stamps the level-0 launch of pass 0 alone)
   later.stamp_l0 = false;
   for (int p = 0; p < P; p++) {
     if (p > 0 && (rc = launch_assemble(h, m, false, p))) return rc;
     if ((rc = launch_forward(h, p == 0 ? m : later, lambda))) return rc;
     if ((rc = launch_backward(h, nullptr))) return rc;
-    const CloPass cp = clo_pass(h, p);
-    const int entries = h->nc * ((cp.lead ? a.ncols : 0) + (cp.k1 - cp.k0) * h->d);
-    dispatch_b(h->b, [&](auto tag) {
-      constexpr int D = decltype(tag)::value / 2;
-      if (p == 0) k_clo_save<D><<<dim3(nblocks(nlead, 256)), dim3(256), 0, h->stream>>>(a, cp);
-      k_clo_gather<D><<<dim3(nblocks(entries, 256)), dim3(256), 0, h->stream>>>(a, cp);
-    });
+    closures_collect(h, p, keep_z);   // (behind the last pass: the wide solve for Y)
   }
-  const CloPass cp = clo_pass(h, 0);
-  const size_t smem = ((size_t)h->nc * (h->nc + 1) + (size_t)h->nc * a.ncols) * sizeof(double);
-  dispatch_b(h->b, [&](auto tag) { k_clo_solve_wide<decltype(tag)::value / 2><<<dim3(1), dim3(256), smem, h->stream>>>(a, cp); });
   if ((rc = launch_assemble(h, m, false, P))) return rc;
   if ((rc = launch_forward(h, later, lambda))) return rc;
   if ((rc = launch_backward(h, nullptr))) return rc;
-  dispatch_b(h->b, [&](auto tag) { k_clo_add<decltype(tag)::value / 2><<<dim3(nblocks(nlead, 256)), dim3(256), 0, h->stream>>>(a, cp); });
-  HIPCHK(hipGetLastError());
-  return launch_landmarks(h, lambda);
+  if ((rc = closures_add(h))) return rc;
+  return solve_landmarks ? launch_landmarks(h, lambda) : launch_landmarks_reduce(h, lambda);
 }
 
-int launch_solve(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
+// keep_z, solve_landmarks: as launch_solve_passes (the marginals: marginals_border)
+int launch_solve(gpslam_hip_handle *h, const LaunchMode &m, double lambda, bool keep_z = false, bool solve_landmarks = true) {
   int rc;
   if (h->fs.active) return fs_solve(h, lambda);
-  if (h->clo_P > 1) return launch_solve_passes(h, m, lambda);
+  if (h->clo.P > 1) return launch_solve_passes(h, m, lambda, keep_z, solve_landmarks);
   if ((rc = launch_forward(h, m, lambda))) return rc;
   if ((rc = launch_backward(h, nullptr))) return rc;
-  if ((rc = launch_closures(h))) return rc;
-  return launch_landmarks(h, lambda);
+  if ((rc = closures_correct(h))) return rc;
+  return solve_landmarks ? launch_landmarks(h, lambda) : launch_landmarks_reduce(h, lambda);
 }
 
 // k_retract over the local states: its arguments and its grid (one workgroup more when this iteration's error partial sums are
@@ -1183,33 +1119,33 @@ int check_stored_indices(gpslam_hip_handle *h) {
 int choose_landmark_path(gpslam_hip_handle *h, bool &segmented) {
   const int N = h->N, d = h->d, b = h->b;
   h->nl = h->L * h->ld;
-  h->nclo = h->clo.count();
-  h->nc = h->nclo * d;
-  for (int k = 0; k < h->nclo; k++)
-    if (h->clo.idx[k] >= N || h->clo_second[k] >= N)
+  h->clo.n = h->clo.fac.count();
+  h->clo.nc = h->clo.n * d;
+  for (int k = 0; k < h->clo.n; k++)
+    if (h->clo.fac.idx[k] >= N || h->clo.second[k] >= N)
       return fail(h, GPSLAM_E_INVALID, "a stored loop closure refers to a state that no longer exists (set_states shrank the problem)");
-  h->clo_slice = h->nclo;
-  h->clo_P = h->nclo > 0 ? 1 : 0;
+  h->clo.slice = h->clo.n;
+  h->clo.P = h->clo.n > 0 ? 1 : 0;
   bool passes = false;
   // closures in column passes (gpslam_hip_set_closure_passes, max_passes >= 2; unsharded fp64 handles, the others are refused below):
   // slices of w closures, R = 1 + nl + w d.  A graph that fits one pass keeps today's path and today's R
-  if (h->nclo > 0 && h->clo_max_passes >= 2 && kIsF64 && !sharded(h) && h->cfg.force_segmented != 1 && !h->fs.split) {
+  if (h->clo.n > 0 && h->clo.max_passes >= 2 && kIsF64 && !sharded(h) && h->cfg.force_segmented != 1 && !h->fs.split) {
     const int room = std::min(kMaxRhs, 64 - 3 * b) - 1 - h->nl;   // 1 + nl + w d <= 28 and 3 b + R <= 64
     const int fit = room > 0 ? room / d : 0;
-    int w = h->clo_per_pass > 0 ? h->clo_per_pass : fit;
+    int w = h->clo.per_pass > 0 ? h->clo.per_pass : fit;
     if (fit < 1) return fail(h, GPSLAM_E_UNSUPPORTED, "loop closures in column passes: the landmark columns leave no room for a closure (1 + landmarks * landmark_dim + d must not exceed 28 right-hand sides)");
     if (w > fit) return fail(h, GPSLAM_E_UNSUPPORTED, "loop closures in column passes: closures_per_pass is larger than fits (1 + landmarks * landmark_dim + closures_per_pass * d must not exceed 28 right-hand sides)");
-    w = std::min(w, h->nclo);
-    const int P = (h->nclo + w - 1) / w;
+    w = std::min(w, h->clo.n);
+    const int P = (h->clo.n + w - 1) / w;
     if (P > 1) {
-      if (h->nc > kCloWideMax) return fail(h, GPSLAM_E_UNSUPPORTED, "too many loop closures: closures * d must not exceed 120");
-      if (P > h->clo_max_passes) return fail(h, GPSLAM_E_UNSUPPORTED, "too many loop closures for max_passes column passes (set_closure_passes): closures / closures per pass exceeds it");
+      if (h->clo.nc > kCloWideMax) return fail(h, GPSLAM_E_UNSUPPORTED, "too many loop closures: closures * d must not exceed 120");
+      if (P > h->clo.max_passes) return fail(h, GPSLAM_E_UNSUPPORTED, "too many loop closures for max_passes column passes (set_closure_passes): closures / closures per pass exceeds it");
       passes = true;
     }
-    h->clo_slice = w;
-    h->clo_P = P;
+    h->clo.slice = w;
+    h->clo.P = P;
   }
-  h->R = 1 + h->nl + (passes ? h->clo_slice * d : h->nc);
+  h->R = 1 + h->nl + (passes ? h->clo.slice * d : h->clo.nc);
   h->fs.active = false;
   segmented = h->nl > 0 && (h->cfg.force_segmented == 1 || h->fs.split || 3 * b + h->R > 64 || h->R > kMaxRhs);
   if (h->fs.split) {
@@ -1218,7 +1154,7 @@ int choose_landmark_path(gpslam_hip_handle *h, bool &segmented) {
       for (int l : *v) if (l < 0 || l >= h->L) return fail(h, GPSLAM_E_INVALID, "fs_set_split: landmark index out of range");
     h->fs.nb_top = 0;
   }
-  if (h->nclo > 0) {   // loop closures: d extra right-hand sides each, through the dense-border path of the chain solver
+  if (h->clo.n > 0) {   // loop closures: d extra right-hand sides each, through the dense-border path of the chain solver
     if (!kIsF64) return fail(h, GPSLAM_E_UNSUPPORTED, "loop closures on an fp32 handle");
     if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "loop closures on a sharded handle");
     if (segmented) return fail(h, GPSLAM_E_UNSUPPORTED, "loop closures together with the segmented landmark elimination (too many landmark + closure columns for the dense border: 1 + landmarks * dim + closures * d <= 28)");
@@ -1321,36 +1257,11 @@ int upload_factors(gpslam_hip_handle *h, const RowLayout &lay, int &npart) {
     if ((rc = upload(h, h->d_gp_dt, pdt))) return rc;
     if ((rc = upload(h, h->d_gp_row0, pr))) return rc;
   }
-  auto up_set = [&](SimpleSet &s, const std::vector<int> &row0) -> int {
-    int r2;
-    if ((r2 = upload(h, s.d_idx, s.idx))) return r2;
-    if ((r2 = upload(h, s.d_meas, s.meas))) return r2;
-    if ((r2 = upload(h, s.d_sig, s.sig))) return r2;
-    return upload(h, s.d_row0, row0);
-  };
-  const std::vector<int> none;
-  if ((rc = up_set(h->pri, lay.r_pri))) return rc;
-  if ((rc = up_set(h->vpri, lay.r_vpri))) return rc;
-  if ((rc = up_set(h->btw, lay.r_btw))) return rc;
-  if ((rc = up_set(h->lpri, none))) return rc;
-  if (h->nclo > 0) {
-    if ((rc = up_set(h->clo, none))) return rc;
-    if ((rc = upload(h, h->d_clo_second, h->clo_second))) return rc;
-    HIPCHK(h->clo_A.reserve((size_t)h->nclo * kCloLen(d) * sizeof(double)));
-    HIPCHK(h->clo_Y.reserve((size_t)h->nc * (1 + h->nl) * sizeof(double)));
-    if (h->clo_P > 1) {
-      HIPCHK(h->clo_W.reserve((size_t)h->nc * (1 + h->nl + h->nc) * sizeof(double)));
-      HIPCHK(h->clo_X.reserve((size_t)h->N * (1 + h->nl) * b * sizeof(double)));
-      // (process-wide per kernel: always the size of the widest system)
-      hipError_t ea = hipSuccess;
-      dispatch_b(b, [&](auto tag) {
-        ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_clo_solve_wide<decltype(tag)::value / 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCloWideLds);
-      });
-      HIPCHK(ea);
-    }
-    if ((rc = upload(h, h->d_clo_rob, h->clo_rob))) return rc;
-    if (!h->clo_rob.empty()) HIPCHK(h->clo_w.reserve((size_t)h->nclo * sizeof(double)));
-  }
+  if ((rc = upload_set(h, h->pri, lay.r_pri))) return rc;
+  if ((rc = upload_set(h, h->vpri, lay.r_vpri))) return rc;
+  if ((rc = upload_set(h, h->btw, lay.r_btw))) return rc;
+  if ((rc = upload_set(h, h->lpri, std::vector<int>()))) return rc;
+  if (h->clo.n > 0 && (rc = closures_upload(h))) return rc;
   // (one k_gp launch per distinct Qc, each rounding its factor count up to whole blocks: at most one extra slot per group)
   npart = nblocks((int)h->gp_left.size(), 128) + gp_ngroups(h) + nblocks(h->pri.count(), 128) + nblocks(h->vpri.count(), 128) +
           nblocks(h->btw.count(), 128) + 1 + 256 + 1;   // (+ 1: the loop closures' error)
@@ -1590,7 +1501,7 @@ int make_plan(gpslam_hip_handle *h, const RowLayout &lay) {
   {   // the retraction folded into the next K1 inside run_gn (PendUpd): record chains (SE(3), and the d = 3 manifolds: config 2) on
       // one unsharded handle whose every state but the last is the left state of exactly one GP prior (the owner that writes it
       // back), one k_lin launch (a single Qc)
-    bool ok = p.gp_rec != GpForm::Rows && h->lv.size() >= 2 && !sharded(h) && h->nl == 0 && h->nclo == 0 && gp_ngroups(h) <= 1 &&
+    bool ok = p.gp_rec != GpForm::Rows && h->lv.size() >= 2 && !sharded(h) && h->nl == 0 && h->clo.n == 0 && gp_ngroups(h) <= 1 &&
               ngp == N - 1 && N >= 2;      // (lv.size() >= 2: the fused level 0, whose K1 writes the records, runs)
     // measurement factors: on SE(3) record chains k_meas runs BEHIND k_lin on the same stream (it reads the interval's record) and
     // so behind the buffer swap -- it sees the updated states; the d = 3 chains run it beside k_lin on a second stream
@@ -1775,12 +1686,12 @@ int gpslam_hip_get_between_pairs_weights(gpslam_hip_handle *h, double *w) {
   int rc = need_local(h);
   if (rc) return rc;
   if (!w) return GPSLAM_E_INVALID;
-  const int F = h->nclo;
-  if (h->clo_rob.empty()) { for (int f = 0; f < F; f++) w[f] = 1.0; return F; }
+  const int F = h->clo.n;
+  if (h->clo.rob.empty()) { for (int f = 0; f < F; f++) w[f] = 1.0; return F; }
   LaunchMode m;
   m.weights = true;
   if ((rc = launch_factors(h, m, 1, 1))) return rc;
-  HIPCHK(hipMemcpyAsync(w, h->clo_w.p, (size_t)F * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(w, h->clo.w.p, (size_t)F * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return F;
 }
@@ -1815,47 +1726,9 @@ int marginals_assemble(gpslam_hip_handle *h) {
   return launch_assemble(h, LaunchMode{}, false);
 }
 // ... and the solver's right-hand sides at lambda = 0: the closure columns Z = A^-1 J_c^T, the landmark columns corrected for the
-// closures, and the landmark Schur complement S of the whole chain -- launch_solve without the landmark solve (the states stay)
-int marginals_border(gpslam_hip_handle *h) {
-  int rc;
-  if ((rc = launch_forward(h, LaunchMode{}, 0.0))) return rc;
-  if ((rc = launch_backward(h, nullptr))) return rc;
-  if ((rc = launch_closures(h))) return rc;
-  return launch_landmarks_reduce(h, 0.0);
-}
-// The same on a handle whose closures go through the solver in column passes (clo_P > 1; gpslam_hip_marginals_keep_closure_columns):
-// launch_solve_passes at lambda = 0, every pass's slice of Z = A^-1 U^T copied into h->mg_Z behind its backward sweep, and the
-// landmark reduction alone at the end.  Leaves W = U [X | Z] in clo_W (k_mg_clo_inverse forms I + U Z from it) and the corrected
-// landmark columns in the leading columns of the level-0 solution.
-int marginals_border_passes(gpslam_hip_handle *h) {
-  int rc;
-  const LaunchMode m{};
-  const CloArgs a = clo_args(h);
-  const int P = h->clo_P, nlead = h->N * a.ncols * h->b, ldz = mg_ldz(h->nc);
-  for (int p = 0; p < P; p++) {
-    if (p > 0 && (rc = launch_assemble(h, m, false, p))) return rc;
-    if ((rc = launch_forward(h, m, 0.0))) return rc;
-    if ((rc = launch_backward(h, nullptr))) return rc;
-    const CloPass cp = clo_pass(h, p);
-    const int entries = h->nc * ((cp.lead ? a.ncols : 0) + (cp.k1 - cp.k0) * h->d);
-    const size_t kept = (size_t)h->N * (cp.k1 - cp.k0) * h->d * h->b;
-    dispatch_b(h->b, [&](auto tag) {
-      constexpr int D = decltype(tag)::value / 2;
-      k_mg_keep_z<D><<<dim3((unsigned)((kept + 255) / 256)), dim3(256), 0, h->stream>>>(a, cp, h->mg_Z.as<double>(), ldz);
-      if (p == 0) k_clo_save<D><<<dim3(nblocks(nlead, 256)), dim3(256), 0, h->stream>>>(a, cp);
-      k_clo_gather<D><<<dim3(nblocks(entries, 256)), dim3(256), 0, h->stream>>>(a, cp);
-    });
-  }
-  const CloPass cp = clo_pass(h, 0);
-  const size_t smem = ((size_t)h->nc * (h->nc + 1) + (size_t)h->nc * a.ncols) * sizeof(double);
-  dispatch_b(h->b, [&](auto tag) { k_clo_solve_wide<decltype(tag)::value / 2><<<dim3(1), dim3(256), smem, h->stream>>>(a, cp); });
-  if ((rc = launch_assemble(h, m, false, P))) return rc;
-  if ((rc = launch_forward(h, m, 0.0))) return rc;
-  if ((rc = launch_backward(h, nullptr))) return rc;
-  dispatch_b(h->b, [&](auto tag) { k_clo_add<decltype(tag)::value / 2><<<dim3(nblocks(nlead, 256)), dim3(256), 0, h->stream>>>(a, cp); });
-  HIPCHK(hipGetLastError());
-  return launch_landmarks_reduce(h, 0.0);
-}
+// closures, and the landmark Schur complement S of the whole chain -- launch_solve without the landmark solve (the states stay).
+// On a handle in column passes (gpslam_hip_marginals_keep_closure_columns) every slice of Z is kept in h->mg_Z on the way.
+int marginals_border(gpslam_hip_handle *h) { return launch_solve(h, LaunchMode{}, 0.0, true, false); }
 
 // whitened Jacobian rows of the current linearisation, in row-table order (rows grouped by left state; inside a
 // state: GP priors, pose priors, velocity priors, between, then the measurement kinds in FKind order)

@@ -9,11 +9,12 @@
 //   (c) landmarks and closures as one low-rank term: the existing solver's right-hand sides give Y = [W | Z] (the landmark
 //       columns corrected for the closures, H_xx^-1 B, and the closure columns A^-1 J_c^T), its landmark reduction the Schur
 //       complement S = H_LL - B^T H_xx^-1 B; then Sigma_xx = A^-1 + Y K Y^T with K = blkdiag(S^-1, -(I + J_c Z)^-1),
-//       Sigma_LL = S^-1, Sigma_xL = -W S^-1 (k_mg_core, k_mg_finish); on a handle whose closures go in column passes (clo_P > 1,
+//       Sigma_LL = S^-1, Sigma_xL = -W S^-1 (k_mg_core, k_mg_finish); on a handle whose closures go in column passes (clo.P > 1,
 //       gpslam_hip_marginals_keep_closure_columns) Z is kept slice by slice and its term has kernels of its own (marginals_clo.hip);
 //   (d) batched posterior covariances of GP-interpolated poses (k_mg_interp behind k_interp_query's H1..H4).
 // fp64 only; no atomics, every sum in a fixed order: two calls give bit-identical blocks.
 #include "api_common.hpp"
+#include "marginals_clo.hpp"
 
 namespace impl64 {
 #include "api_decl.inc"
@@ -204,7 +205,7 @@ template <int B> __global__ void __launch_bounds__(64) k_mg_backward(MgLevel a) 
 }
 
 // K = blkdiag(S^-1, -(I + J_c Z)^-1), one wave.  S: the landmark reduction's Schur complement (upper part, as k_lm_solve reads
-// it); J_c Z from the closures' whitened Jacobians and the closure columns of the solution at their two states (as k_clo_solve).
+// it); J_c Z from the closures' whitened Jacobians and the closure columns of the solution at their two states (clo_row_dot's sums, spelt out: with the helper the code of k_mg_core<2> changes).
 struct MgCore {
   const double *S;              // nl x R, columns 1 .. nl
   const double *cloA;           // closure records [A_i | A_j | r]
@@ -235,7 +236,7 @@ template <int d> __global__ void __launch_bounds__(64) k_mg_core(MgCore a) {
       for (int u = 0; u < d; u++) acc += rec[d * d + q * d + u] * xj[u];
       w[side] = acc;
     }
-    Mm[p * kMgMaxCols + c] = (p == c ? 1.0 : 0.0) + 0.5 * (w[0] + w[1]);
+    Mm[p * kMgMaxCols + c] = clo_sym_entry(p == c, w[0], w[1]);
   }
   __syncthreads();
   mg_inverse_n(Sm, nl, kMgMaxCols, a.flag);
@@ -348,7 +349,7 @@ int mg_refuse(gpslam_hip_handle *h) {
   if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: sharded handles are not supported");
   if (h->fs.active && h->fs.split) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: split pieces are not supported");
   if (h->fs.active) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: the segmented landmark path is not supported");
-  if (h->clo_P > 1 && !h->mg_keep_z)
+  if (h->clo.P > 1 && !h->mg_keep_z)
     return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: loop closures in more than one column pass (set_closure_passes) are not supported: Z = H0^-1 U^T is not kept at every state (unless gpslam_hip_marginals_keep_closure_columns asks for it)");
   return 0;
 }
@@ -400,8 +401,8 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
   HIPCHK(h->mg_K.reserve((size_t)std::max(m * m, 1) * sizeof(double)));
   HIPCHK(h->mg_Slm.reserve((size_t)std::max(h->nl * h->nl, 1) * sizeof(double)));
   HIPCHK(h->mg_Sxl.reserve((size_t)std::max(N * B * h->nl, 1) * sizeof(double)));
-  const bool passes = h->clo_P > 1;     // (mg_refuse: only with gpslam_hip_marginals_keep_closure_columns)
-  const int ldz = mg_ldz(h->nc);
+  const bool passes = h->clo.P > 1;     // (mg_refuse: only with gpslam_hip_marginals_keep_closure_columns)
+  const int ldz = mg_ldz(h->clo.nc);
   if (passes) {
     const size_t zbytes = mg_zrows(N, B) * ldz * sizeof(double);
     HIPCHK(h->mg_Z.reserve(zbytes));
@@ -447,25 +448,18 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
   }
   HIPCHK(hipGetLastError());
   // (c) landmarks and closures: Y = [W | Z] and S from the solver's own right-hand sides, then K
-  if (m > 0 && passes) {
+  if (m > 0) {
     // closures in column passes: Z slice by slice into mg_Z, then - Z M^-1 Z^T on its own; what is left for k_mg_core and
-    // k_mg_finish is the landmark term (W in the leading columns of the level-0 solution, K = S^-1)
-    if ((rc = impl64::marginals_border_passes(h))) return rc;
-    if ((rc = marginals_closure_term(h))) return rc;
-    if (h->nl > 0) {
+    // k_mg_finish is the landmark term (W in the leading columns of the level-0 solution, K = S^-1: no closure reaches k_mg_core)
+    if ((rc = impl64::marginals_border(h))) return rc;
+    if (passes && (rc = marginals_closure_term(h))) return rc;
+    if (!passes || h->nl > 0) {
       MgCore c;
-      c.S = h->lm_S.as<double>(); c.cloA = nullptr; c.first = nullptr; c.second = nullptr;
-      c.x = h->lv[0].x.as<double>(); c.nl = h->nl; c.nclo = 0; c.R = R; c.B = B;
+      c.S = h->lm_S.as<double>(); c.cloA = h->clo.A.as<double>(); c.first = h->clo.fac.d_idx.as<int>(); c.second = h->clo.d_second.as<int>();
+      c.x = h->lv[0].x.as<double>(); c.nl = h->nl; c.nclo = passes ? 0 : h->clo.n; c.R = R; c.B = B;
       c.K = h->mg_K.as<double>(); c.Slm = h->mg_Slm.as<double>(); c.flag = h->flag.as<int>();
       dispatch_b(B, [&](auto tag) { k_mg_core<decltype(tag)::value / 2><<<dim3(1), dim3(64), 0, h->stream>>>(c); });
     }
-  } else if (m > 0) {
-    if ((rc = impl64::marginals_border(h))) return rc;
-    MgCore c;
-    c.S = h->lm_S.as<double>(); c.cloA = h->clo_A.as<double>(); c.first = h->clo.d_idx.as<int>(); c.second = h->d_clo_second.as<int>();
-    c.x = h->lv[0].x.as<double>(); c.nl = h->nl; c.nclo = h->nclo; c.R = R; c.B = B;
-    c.K = h->mg_K.as<double>(); c.Slm = h->mg_Slm.as<double>(); c.flag = h->flag.as<int>();
-    dispatch_b(B, [&](auto tag) { k_mg_core<decltype(tag)::value / 2><<<dim3(1), dim3(64), 0, h->stream>>>(c); });
   }
   const bool pad = h->mf == ROT3_BIAS;
   const int mfin = passes ? h->nl : m;   // the columns k_mg_finish adds: [W | Z], or W alone behind k_mg_clo_finish

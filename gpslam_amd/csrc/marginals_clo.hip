@@ -1,9 +1,10 @@
 // marginals_clo.hip -- gpslam_hip_marginals on a handle whose loop closures go through the solver in column passes
-// (gpslam_hip_marginals_keep_closure_columns; marginals.hip (c), api_impl.inc marginals_border_passes): the closure term
+// (gpslam_hip_marginals_keep_closure_columns; marginals.hip (c), api_impl.inc launch_solve_passes with keep_z): the closure term
 //   Sigma_{i,i} -= Z_i M^-1 Z_i^T,   Sigma_{i,i+1} -= Z_i M^-1 Z_{i+1}^T,   M = I + 1/2 (U Z + (U Z)^T),
 // with Z = A^-1 U^T kept at every state (k_mg_keep_z) and nc = closures * d up to kCloWideMax = 120.  A translation unit of its
 // own: the kernels of marginals.hip stay what they were, byte for byte.
 #include "api_common.hpp"
+#include "marginals_clo.hpp"
 
 namespace {
 
@@ -24,7 +25,7 @@ __global__ void __launch_bounds__(kMgInvThreads) k_mg_clo_inverse(MgCloInv a) {
   double *S = mg_lds, *colk = mg_lds + (size_t)nc * ls, *rowk = colk + nc;
   for (int idx = tid; idx < nc * nc; idx += kMgInvThreads) {
     const int i = idx / nc, j = idx - i * nc;
-    S[i * ls + j] = (i == j ? 1.0 : 0.0) + 0.5 * (a.W[(size_t)i * a.ldw + a.nr + j] + a.W[(size_t)j * a.ldw + a.nr + i]);
+    S[i * ls + j] = clo_sym_entry(i == j, a.W[(size_t)i * a.ldw + a.nr + j], a.W[(size_t)j * a.ldw + a.nr + i]);
   }
   __syncthreads();
   for (int k = 0; k < nc; k++) {
@@ -144,16 +145,16 @@ template <int B> __global__ void __launch_bounds__(64 * kMgCloWaves) k_mg_clo_fi
 
 }  // namespace
 
-// behind marginals_border_passes (W = U [X | Z] in clo_W, Z in mg_Z) and in front of k_mg_finish: M^-1 into mg_Minv, then the term
+// behind the column passes of marginals_border (W = U [X | Z] in clo.W, Z in mg_Z) and in front of k_mg_finish: M^-1 into mg_Minv, then the term
 int marginals_closure_term(gpslam_hip_handle *h) {
-  const int N = h->N, B = h->b, ldz = mg_ldz(h->nc);
+  const int N = h->N, B = h->b, ldz = mg_ldz(h->clo.nc);
   MgCloInv ci;
-  ci.W = h->clo_W.as<double>(); ci.ldw = 1 + h->nl + h->nc; ci.nr = 1 + h->nl; ci.nc = h->nc; ci.ldz = ldz;
+  ci.W = h->clo.W.as<double>(); ci.ldw = clo_ldw(h); ci.nr = 1 + h->nl; ci.nc = h->clo.nc; ci.ldz = ldz;
   ci.Minv = h->mg_Minv.as<double>(); ci.flag = h->flag.as<int>();
   // (process-wide per kernel: always the size of the widest system, whatever this handle's)
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mg_clo_inverse), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)mg_clo_inverse_lds(kCloWideMax)));
-  k_mg_clo_inverse<<<dim3(1), dim3(kMgInvThreads), mg_clo_inverse_lds(h->nc), h->stream>>>(ci);
+  k_mg_clo_inverse<<<dim3(1), dim3(kMgInvThreads), mg_clo_inverse_lds(h->clo.nc), h->stream>>>(ci);
   MgCloFinish cf;
   cf.Sd = h->mg_S.as<double>(); cf.Sn = h->mg_Sn.as<double>(); cf.Z = h->mg_Z.as<double>(); cf.Minv = h->mg_Minv.as<double>();
   cf.N = N; cf.ldz = ldz; cf.ngroups = (int)(((size_t)N * B + kMgGroupRows - 1) / kMgGroupRows);

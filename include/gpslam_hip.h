@@ -220,7 +220,7 @@ int gpslam_hip_add_between(gpslam_hip_handle *h, int32_t count, const int32_t *l
  * The reference's factors take arbitrary keys (gpslam/gp/GaussianProcessPriorPose3.h:43-47) and GTSAM eliminates whatever graph
  * they form; here everything but closures couples state i with i + 1, and a closure is applied to the chain solve as a low-rank
  * correction: its d whitened rows ride through the block-tridiagonal solver as d extra right-hand sides behind the landmark
- * columns (Sherman-Morrison-Woodbury; kernels.hpp "loop closures").  Pairs with second == first + 1 are ordinary chain factors
+ * columns (Sherman-Morrison-Woodbury; closures.hpp "loop closures").  Pairs with second == first + 1 are ordinary chain factors
  * (add_between).  Capacity of one pass: 1 + landmarks * landmark_dim + closures * d <= 28 right-hand sides (Pose2 / Rot3 / Linear3:
  * 9 closures without landmarks, Pose3: 4); compile() answers GPSLAM_E_UNSUPPORTED beyond that unless gpslam_hip_set_closure_passes
  * allowed column passes (then closures * d <= 120: 40 closures, Pose3: 20), and always on fp32 handles, on sharded handles and on
@@ -232,7 +232,7 @@ int gpslam_hip_add_between_pairs(gpslam_hip_handle *h, int32_t count, const int3
  * as it is.  With max_passes >= 2 compile() deals the closures, in the order they were added, into P = ceil(closures / w) slices of
  * w closures -- closures_per_pass if that is > 0, else the most that fit: 1 + landmarks * landmark_dim + w * d <= 28 -- and one linear
  * solve becomes P passes of the chain solver over the closures' columns, a dense (closures * d)-square solve, and one final pass
- * (kernels.hpp CloPass); the linearisation still runs once.  A graph whose closures fit one pass (P == 1) keeps the single-pass path
+ * (closures.hpp CloPass); the linearisation still runs once.  A graph whose closures fit one pass (P == 1) keeps the single-pass path
  * bit for bit.  compile() answers GPSLAM_E_UNSUPPORTED when the landmark columns leave no room for a closure, when
  * closures_per_pass is larger than fits, when P > max_passes and when closures * d > 120; fp32, sharded and segmented handles
  * refuse closures as before.  gpslam_hip_marginals answers GPSLAM_E_UNSUPPORTED on a handle with P > 1 unless

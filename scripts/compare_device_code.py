@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Is the device code of two builds the same?  compare_device_code.py LIB_A LIB_B [--arch gfx950]
+"""Is the device code of two builds the same?  compare_device_code.py LIB_A LIB_B [--arch gfx950] [--by-symbol]
 
 LIB_A / LIB_B: two gpslam_amd/lib directories (obj/*.o and libgpslam_hip.so, as `python -m gpslam_amd.build` leaves them).
 Per object: the gfx950 code object is taken out of .hip_fatbin, and every kernel is compared by name, by the bytes of its code and
 by its metadata (registers, LDS, scratch: the amdhsa.kernels note).  Per symbol, not per file: the order of instantiation moves
-with the host code.  Also compares the C ABI (the exported gpslam_hip_* symbols) of the two libraries.  Exit status 1 on any difference.
+with the host code.  --by-symbol: kernels may move between objects (a refactor that gives a feature a translation unit of its own) --
+every kernel of the whole library is compared by name whichever object holds it, a kernel may neither appear nor vanish, and the
+moves are listed (kernel count per pair of object sets).  Also compares the C ABI (the exported gpslam_hip_* symbols) of the two libraries.  Exit status 1 on any difference.
 """
 import argparse
 import hashlib
@@ -48,10 +50,52 @@ def kernels(obj, arch, tmp):
     meta = {}
     notes = run(tool("llvm-readelf"), "--notes", base + ".co")
     for block in re.split(r"\n\s*- \.agpr_count", notes)[1:]:
+        block = re.split(r"\n\s*amdhsa\.", block)[0]      # (the last kernel's block runs on into the tail of the note)
         name = re.search(r"\.name:\s+(\S+)", block)
         body = "\n".join(l.strip() for l in block.splitlines() if not l.strip().startswith("amdhsa.") and "---" not in l)
         meta[name.group(1)] = body.split("amdhsa.target")[0]
     return {k: (v, meta.get(k, "")) for k, v in code.items()}
+
+
+def by_symbol(a, ta, tb):
+    """whole library, per kernel: {name: {object: (code, metadata)}} of both builds; returns the number of differences"""
+    bad = 0
+    libs = []
+    for d, tmp in ((a.lib_a, ta), (a.lib_b, tb)):
+        per = {}
+        for o in sorted(f for f in os.listdir(os.path.join(d, "obj")) if f.endswith(".o")):
+            ks = kernels(os.path.join(d, "obj", o), a.arch, tmp)
+            print("%s %-18s %4d kernels" % ("A" if d == a.lib_a else "B", o, len(ks)))
+            for k, v in ks.items():
+                per.setdefault(k, {})[o] = v
+        libs.append(per)
+    la, lb = libs
+    moves = {}
+    for k in sorted(set(la) | set(lb)):
+        if k not in la or k not in lb:
+            print("%s only in %s (%s)" % (k, "A" if k in la else "B", ", ".join(sorted((la if k in la else lb)[k]))))
+            bad += 1
+            continue
+        va, vb = set(la[k].values()), set(lb[k].values())
+        if len(va) > 1 or len(vb) > 1:
+            print("%s: its copies differ inside one library" % k)
+            bad += 1
+        elif {v[0] for v in va} != {v[0] for v in vb}:
+            print("%s: code differs" % k)
+            bad += 1
+        elif va != vb:
+            print("%s: metadata differs" % k)
+            bad += 1
+        oa, ob = tuple(sorted(la[k])), tuple(sorted(lb[k]))
+        if oa != ob:
+            moves.setdefault((oa, ob), []).append(k)
+    for (oa, ob), ks in sorted(moves.items()):
+        print("%4d kernels moved: %s -> %s" % (len(ks), " + ".join(oa), " + ".join(ob)))
+        if a.verbose:
+            for k in ks:
+                print("       " + k)
+    print("%d kernel names in A, %d in B" % (len(la), len(lb)))
+    return bad
 
 
 def main():
@@ -59,11 +103,15 @@ def main():
     ap.add_argument("lib_a")
     ap.add_argument("lib_b")
     ap.add_argument("--arch", default="gfx950")
+    ap.add_argument("--by-symbol", action="store_true", help="whole library, per kernel: kernels may have moved between objects")
+    ap.add_argument("--verbose", action="store_true", help="--by-symbol: name the kernels that moved")
     a = ap.parse_args()
     bad = 0
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-        objs = sorted(f for f in os.listdir(os.path.join(a.lib_a, "obj")) if f.endswith(".o"))
-        if objs != sorted(f for f in os.listdir(os.path.join(a.lib_b, "obj")) if f.endswith(".o")):
+        objs = [] if a.by_symbol else sorted(f for f in os.listdir(os.path.join(a.lib_a, "obj")) if f.endswith(".o"))
+        if a.by_symbol:
+            bad += by_symbol(a, ta, tb)
+        elif objs != sorted(f for f in os.listdir(os.path.join(a.lib_b, "obj")) if f.endswith(".o")):
             print("different sets of objects")
             bad += 1
         for o in objs:

@@ -1,4 +1,4 @@
-"""numpy model of loop closures in column passes (kernels.hpp CloPass, api_impl.inc launch_solve_passes) on dense matrices.
+"""numpy model of loop closures in column passes (closures.hpp CloPass, api_impl.inc launch_solve_passes) on dense matrices.
 
 H = H0 + U^T U with H0 everything but the closures and U (nc x n) their whitened rows.  One linear solve is
     X  = H0^-1 [g + 0 | B]                      pass 0, which also carries slice 0 of U^T as extra columns

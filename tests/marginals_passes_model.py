@@ -1,5 +1,5 @@
 """numpy model of the marginals on a handle whose loop closures go in column passes (marginals.hip: k_mg_clo_inverse,
-k_mg_clo_finish; api_impl.inc marginals_border_passes) on dense matrices.
+k_mg_clo_finish; api_impl.inc launch_solve_passes with keep_z) on dense matrices.
 
 H = [[A + U^T U, B], [B^T, H_LL]] with A the chain part, U (nc x n) the closures' whitened rows, B the landmark coupling.  With
     Z_s = A^-1 U_s^T                            one pass per slice s of w closures, kept at EVERY state (the device's mg_Z)

@@ -1,7 +1,7 @@
 """Loop closures on the HIP path: gtsam::BetweenFactor<Pose>(x_i, x_j) between NON-adjacent states (gpslam_hip_add_between_pairs).
 The reference's factors take arbitrary keys (gpslam/gp/GaussianProcessPriorPose3.h:43-47) and GTSAM eliminates whatever graph they
 form; the product keeps its block-tridiagonal chain solver and applies the closures as a low-rank correction (d extra right-hand
-sides each, kernels.hpp "loop closures").  The oracle solves the same graphs by an envelope Cholesky of the whole system in chain
+sides each, closures.hpp "loop closures").  The oracle solves the same graphs by an envelope Cholesky of the whole system in chain
 order (oracle/orc_chain.c: skyline_solve, pinned by tests/test_oracle_closure.py) -- a different elimination, so agreement at 1e-9
 checks the Woodbury algebra, the injected columns, the error terms and the Levenberg-Marquardt model together."""
 import numpy as np

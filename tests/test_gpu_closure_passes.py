@@ -1,4 +1,4 @@
-"""Loop closures past one border: column passes (gpslam_hip_set_closure_passes; kernels.hpp CloPass).  More closures than the 28
+"""Loop closures past one border: column passes (gpslam_hip_set_closure_passes; closures.hpp CloPass).  More closures than the 28
 right-hand sides of one pass hold go through the chain solver a slice at a time; W = U [X | Z] is kept, one workgroup solves
 (I + U Z) Y = [r | 0] - U X, and a final pass adds H0^-1 U^T Y to the X of pass 0 (the algebra: tests/closure_passes_model.py).
 The oracle solves the same graphs by an envelope Cholesky of the whole system, so agreement at the project's 1e-9 per step checks the

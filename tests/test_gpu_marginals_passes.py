@@ -1,5 +1,5 @@
 """Marginals on handles whose loop closures go through the solver in column passes (gpslam_hip_marginals_keep_closure_columns;
-marginals_clo.hip: k_mg_clo_inverse, k_mg_clo_finish; api_impl.inc marginals_border_passes) against dense inverses of the oracle's H.
+marginals_clo.hip: k_mg_clo_inverse, k_mg_clo_finish; api_impl.inc launch_solve_passes with keep_z) against dense inverses of the oracle's H.
 
 Sigma_xx = A^-1 + W S^-1 W^T - Z M^-1 Z^T with Z = A^-1 U^T kept at every state, a slice per pass (the algebra:
 tests/marginals_passes_model.py).  Tolerance: the project's, tol_of(H) = max(1e-10, 100 eps kappa_s) in correlation units, kappa_s

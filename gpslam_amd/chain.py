@@ -51,6 +51,8 @@ ABI_SYMBOLS = [
     "gpslam_hip_get_between_pairs_weights", "gpslam_hip_robust_eval",
     "gpslam_hip_set_closure_passes", "gpslam_hip_closure_info",
     "gpslam_hip_marginals_keep_closure_columns",
+    "gpslam_hip_marginals_on_segments", "gpslam_hip_get_landmark_marginals", "gpslam_hip_get_state_landmark_marginals",
+    "gpslam_hip_get_landmark_pair_marginals",
 ]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
@@ -548,6 +550,41 @@ class ChainSolver:
         closures' columns at every state, one more device buffer of about N * closures * d * b doubles.  Any time after create;
         changes nothing on a handle within one pass.  enable=False restores the refusal and frees the buffer."""
         return self._chk(self.lib.gpslam_hip_marginals_keep_closure_columns(self._h, 1 if enable else 0), "marginals_keep_closure_columns")
+
+    def marginals_on_segments(self, enable=True):
+        """Let marginals() run on the segmented landmark path (segment_plan()["active"]): it then keeps G = A_s^-1 H[I_s, B_s] at every
+        interior state, one more device buffer of about N * b * NCP doubles, and the fat blocks' covariances.  Fat blocks up to 64
+        columns.  Any time after create; changes nothing on a handle that is not segmented.  enable=False restores the refusal and
+        frees the buffers.  Landmark blocks then come from get_landmark_marginals / get_state_landmark_marginals /
+        get_landmark_pair_marginals (get_marginals(cross=True) is refused there: S_lm and S_x_lm are too large to exist)."""
+        return self._chk(self.lib.gpslam_hip_marginals_on_segments(self._h, 1 if enable else 0), "marginals_on_segments")
+
+    def get_landmark_marginals(self, first=0, count=None):
+        """Sigma_{l,l} (count, ld, ld) of the landmarks [first, first + count) after marginals(); any handle with landmarks."""
+        count = self.L - first if count is None else count
+        out = np.zeros((count, self.ld, self.ld))
+        self._chk(self.lib.gpslam_hip_get_landmark_marginals(self._h, int(first), int(count), _p(out)), "get_landmark_marginals")
+        return out
+
+    def get_state_landmark_marginals(self, states, landmarks):
+        """Sigma_{state, landmark} (count, b, ld) for pairs of a state and a landmark.  Segmented handles: the landmark must sit in a
+        fat block next to the state's segment (every landmark the state observes does)."""
+        states, landmarks = _i32(states), _i32(landmarks)
+        if len(states) != len(landmarks):
+            raise ValueError("get_state_landmark_marginals: states and landmarks differ in length")
+        out = np.zeros((len(states), self.b, self.ld))
+        self._chk(self.lib.gpslam_hip_get_state_landmark_marginals(self._h, len(states), _p(states), _p(landmarks), _p(out)),
+                  "get_state_landmark_marginals")
+        return out
+
+    def get_landmark_pair_marginals(self, a, b):
+        """Sigma_{a, b} (count, ld, ld) for pairs of landmarks.  Segmented handles: both in the same or in neighbouring fat blocks."""
+        a, b = _i32(a), _i32(b)
+        if len(a) != len(b):
+            raise ValueError("get_landmark_pair_marginals: a and b differ in length")
+        out = np.zeros((len(a), self.ld, self.ld))
+        self._chk(self.lib.gpslam_hip_get_landmark_pair_marginals(self._h, len(a), _p(a), _p(b), _p(out)), "get_landmark_pair_marginals")
+        return out
 
     def get_marginals(self, first=0, count=None, cross=False):
         """Blocks of the last marginals() call for states [first, first + count): S (count, b, b) = Sigma_{i,i} and S_next

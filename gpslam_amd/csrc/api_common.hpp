@@ -1,5 +1,5 @@
 // api_common.hpp -- what the translation units of the library's host side share (api.hip: the C ABI; api_impl64.hip / api_impl32.hip:
-// api_impl.inc + api_iterate.inc once per row precision; closures.hip, marginals.hip, marginals_clo.hip): the handle, the host helpers and the kernel launchers
+// api_impl.inc + api_iterate.inc once per row precision; closures.hip, marginals.hip, marginals_clo.hip, marginals_fs.hip): the handle, the host helpers and the kernel launchers
 // (round 3: api.hip was one 3.5-minute translation unit; the fp64 and fp32 halves compile side by side now)
 #pragma once
 // api.hip -- host side of libgpslam_hip.so: the opaque handle, the graph-compile pass and the C ABI
@@ -203,6 +203,11 @@ struct gpslam_hip_handle {
   // state (mg_Z: mg_zrows(N, b) rows of mg_ldz(clo.nc) doubles) and the inverse of I + U Z (mg_Minv: mg_ldz(clo.nc) squared)
   bool mg_keep_z = false;
   DevBuf mg_Z, mg_Minv;
+  // gpslam_hip_marginals_on_segments: the marginals run on the segmented landmark path (marginals_fs.hip) and keep the fat chain's
+  // selected inverse (mg_fsD: K blocks Sigma_{k,k}; mg_fsP: one block Sigma_{left,right} per link of the cyclic reduction, the first
+  // K - 1 of them Sigma_{k,k+1}) and G = A_s^-1 H[I_s, B_s] at every interior state (mg_G: (N b + 64) rows of NCP doubles)
+  bool mg_on_segments = false;
+  DevBuf mg_fsD, mg_fsP, mg_G;
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch
@@ -214,6 +219,10 @@ struct gpslam_hip_handle {
 void marginals_release(gpslam_hip_handle *h);
 // the closure term of the marginals on a handle in column passes (marginals_clo.hip)
 int marginals_closure_term(gpslam_hip_handle *h);
+// the marginals of a handle on the segmented landmark path, and the gather behind the landmark getters (marginals_fs.hip)
+int marginals_fs(gpslam_hip_handle *h);
+void marginals_fs_release(gpslam_hip_handle *h);
+int marginals_fs_gather(gpslam_hip_handle *h, int mode, int32_t count, const int32_t *a, const int32_t *b, double *out);
 
 // What the launches of one call do: each entry point builds the mode it means and hands it to the launch helpers.
 // LaunchMode{}: row tables (d = 3 records where the graph has them), level 0 unfused, every reduction at once, untimed.

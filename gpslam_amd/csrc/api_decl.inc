@@ -39,3 +39,5 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
 // in column passes launch_solve_passes, every slice of Z kept in h->mg_Z on the way (gpslam_hip_marginals_keep_closure_columns)
 int marginals_assemble(gpslam_hip_handle *h);
 int marginals_border(gpslam_hip_handle *h);
+// the same on the segmented landmark path (marginals_fs.hip): fs_forward at lambda = 0 in the two-launch form, Y into the caller's buffer
+int marginals_fs_forward(gpslam_hip_handle *h, void *Y);

@@ -619,9 +619,12 @@ void launch_fat_back(const FsArgs<Real, RowT> &a, const FatLevel &fl, hipStream_
 
 // forward half: segment interiors -> fat blocks -> cyclic-reduction levels (down to one block, or to the two end blocks of a
 // piece of a split chain)
-int fs_forward(gpslam_hip_handle *h, double lambda) {
+// y_own: the sweep and the Schur complements in two launches through THIS Y buffer, whatever the plan's choice (marginals_fs_forward)
+int fs_forward(gpslam_hip_handle *h, double lambda, Real *y_own = nullptr) {
   FatSepPlan &p = h->fs;
   FsArgs<Real, RowT> a = fs_args(h, lambda);
+  const bool fused_sweep = p.fused_sweep && !y_own;
+  if (y_own) a.Y = y_own;
   hipStream_t st = h->stream;
   const int nseg = p.K - 1;
   const size_t smem_elim = ((size_t)p.NB * (p.NB + 1) + (size_t)p.NB * (2 * p.NB + 1)) * sizeof(Real);
@@ -644,9 +647,9 @@ int fs_forward(gpslam_hip_handle *h, double lambda) {
       (void)hipEventRecord(h->ev_join, h->aux_stream);
       (void)hipStreamWaitEvent(st, h->ev_join, 0);
     }
-    if (!p.fused_sweep) k_fs_sweep<Real, BB, RowT><<<dim3(nseg), dim3(((p.NC + 63) / 64) * 64), 0, st>>>(a);
+    if (!fused_sweep) k_fs_sweep<Real, BB, RowT><<<dim3(nseg), dim3(((p.NC + 63) / 64) * 64), 0, st>>>(a);
   });
-  if (p.fused_sweep) {   // sweep + Schur complement in one launch (planar chains, borders up to 112 columns): no Y buffer
+  if (fused_sweep) {   // sweep + Schur complement in one launch (planar chains, borders up to 112 columns): no Y buffer
     const size_t smem = fs_fused_smem(h->b, p.NCP);
     switch (p.NCP / 16) {
       case 2: k_fs_sweep_syrk<6, 2, RowT><<<dim3(nseg), dim3(256), smem, st>>>(a); break;
@@ -802,6 +805,7 @@ int fs_build(gpslam_hip_handle *h, const std::vector<int> &touch_lo, const std::
   HIPCHK(upload_vec(st, p.d_fat_lm, fat_lm));
   HIPCHK(upload_vec(st, p.d_lm_fat, fat_of));
   HIPCHK(upload_vec(st, p.d_lm_slot, slot_of));
+  p.h_lm_fat = fat_of; p.h_lm_slot = slot_of;
   HIPCHK(upload_vec(st, p.d_lmpri_ptr, pri_ptr));
   HIPCHK(upload_vec(st, p.d_lmpri, pri_ids));
   std::vector<int> lg_ptr(L + 1, 0), lg_state;
@@ -1729,6 +1733,9 @@ int marginals_assemble(gpslam_hip_handle *h) {
 // closures, and the landmark Schur complement S of the whole chain -- launch_solve without the landmark solve (the states stay).
 // On a handle in column passes (gpslam_hip_marginals_keep_closure_columns) every slice of Z is kept in h->mg_Z on the way.
 int marginals_border(gpslam_hip_handle *h) { return launch_solve(h, LaunchMode{}, 0.0, true, false); }
+// ... and on the segmented landmark path (marginals_fs.hip) the forward half at lambda = 0: segment factors, the half-swept border
+// Y = L^-1 G into the marginals' own buffer (zeroed by the caller; a fused_sweep plan has none), the fat chain's cyclic reduction
+int marginals_fs_forward(gpslam_hip_handle *h, void *Y) { return fs_forward(h, 0.0, static_cast<Real *>(Y)); }
 
 // whitened Jacobian rows of the current linearisation, in row-table order (rows grouped by left state; inside a
 // state: GP priors, pose priors, velocity priors, between, then the measurement kinds in FKind order)

@@ -2151,6 +2151,7 @@ struct FatSepPlan {
   bool fused_sweep = false;                         // k_fs_sweep_syrk serves this plan (else k_fs_sweep + k_fs_syrk through Y)
   int ngroups = 0;
   std::vector<int> h_lmrow, h_lmstate, h_lmptr;     // compile(): rows per landmark, sorted by left state
+  std::vector<int> h_lm_fat, h_lm_slot;             // host copies of d_lm_fat / d_lm_slot (the marginals' landmark getters)
 
   void release() {
     for (DevBuf *b : {&d_cuts, &d_segid, &d_fat_lm_ptr, &d_fat_lm, &d_lm_fat, &d_lm_slot, &d_lmpri_ptr, &d_lmpri, &d_elim, &d_upd,

@@ -11,10 +11,13 @@
 //       complement S = H_LL - B^T H_xx^-1 B; then Sigma_xx = A^-1 + Y K Y^T with K = blkdiag(S^-1, -(I + J_c Z)^-1),
 //       Sigma_LL = S^-1, Sigma_xL = -W S^-1 (k_mg_core, k_mg_finish); on a handle whose closures go in column passes (clo.P > 1,
 //       gpslam_hip_marginals_keep_closure_columns) Z is kept slice by slice and its term has kernels of its own (marginals_clo.hip);
-//   (d) batched posterior covariances of GP-interpolated poses (k_mg_interp behind k_interp_query's H1..H4).
+//   (d) batched posterior covariances of GP-interpolated poses (k_mg_interp behind k_interp_query's H1..H4);
+//   (e) a handle on the segmented landmark path (gpslam_hip_marginals_on_segments) takes none of (b), (c): marginals_fs.hip inverts
+//       through the nested dissection and leaves Sigma_{i,i}, Sigma_{i,i+1} where (d) and get_marginals read them.
 // fp64 only; no atomics, every sum in a fixed order: two calls give bit-identical blocks.
 #include "api_common.hpp"
 #include "marginals_clo.hpp"
+#include "marginals_fs.hpp"
 
 namespace impl64 {
 #include "api_decl.inc"
@@ -348,7 +351,7 @@ int mg_refuse(gpslam_hip_handle *h) {
   if (h->cfg.precision == GPSLAM_FP32) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: fp32 handles are not supported (fp64 only)");
   if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: sharded handles are not supported");
   if (h->fs.active && h->fs.split) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: split pieces are not supported");
-  if (h->fs.active) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: the segmented landmark path is not supported");
+  if (h->fs.active && !h->mg_on_segments) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: the segmented landmark path is not supported");
   if (h->clo.P > 1 && !h->mg_keep_z)
     return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: loop closures in more than one column pass (set_closure_passes) are not supported: Z = H0^-1 U^T is not kept at every state (unless gpslam_hip_marginals_keep_closure_columns asks for it)");
   return 0;
@@ -363,6 +366,7 @@ int mg_stale(gpslam_hip_handle *h) {
 
 void marginals_release(gpslam_hip_handle *h) {
   for (DevBuf *b : {&h->mg_fac, &h->mg_S, &h->mg_Sn, &h->mg_up, &h->mg_K, &h->mg_Slm, &h->mg_Sxl, &h->mg_Z, &h->mg_Minv}) b->release();
+  marginals_fs_release(h);
   h->marg_ok = false;
   h->marg_N = 0;
 }
@@ -380,12 +384,21 @@ int gpslam_hip_marginals_keep_closure_columns(gpslam_hip_handle *h, int32_t enab
   return 0;
 }
 
+int gpslam_hip_marginals_on_segments(gpslam_hip_handle *h, int32_t enable) {
+  if (!h) return GPSLAM_E_INVALID;
+  h->marg_ok = false;
+  h->mg_on_segments = enable != 0;
+  if (!h->mg_on_segments) marginals_fs_release(h);
+  return 0;
+}
+
 int gpslam_hip_marginals(gpslam_hip_handle *h) {
   int rc = need_compiled(h);
   if (rc) return rc;
   if ((rc = mg_refuse(h))) return rc;
   (void)hipSetDevice(h->cfg.device);
   h->marg_ok = false;
+  if (h->fs.active) return marginals_fs(h);
   const int N = h->N, B = h->b, BB = B * B, R = h->R, m = R - 1;
   // levels: n_0 = N, n_{l+1} = ceil(n_l / kMgChunk), down to one block; the levels above 0 live in one buffer
   std::vector<int> n{N};
@@ -486,6 +499,9 @@ int gpslam_hip_get_marginals(gpslam_hip_handle *h, int32_t first, int32_t count,
   int rc = mg_refuse(h);
   if (rc || (rc = mg_stale(h))) return rc;
   if (first < 0 || count < 0 || first + count > h->N) return fail(h, GPSLAM_E_INVALID, "get_marginals: state window out of range");
+  if (h->fs.active && (S_lm || S_x_lm))
+    return fail(h, GPSLAM_E_UNSUPPORTED, "get_marginals: S_lm / S_x_lm do not exist on the segmented landmark path (nl x nl, N b x nl); use "
+                "gpslam_hip_get_landmark_marginals, gpslam_hip_get_state_landmark_marginals, gpslam_hip_get_landmark_pair_marginals");
   (void)hipSetDevice(h->cfg.device);
   const size_t BB = (size_t)h->b * h->b, nl = (size_t)h->nl;
   if (S && count) HIPCHK(hipMemcpyAsync(S, h->mg_S.as<double>() + first * BB, count * BB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -495,6 +511,33 @@ int gpslam_hip_get_marginals(gpslam_hip_handle *h, int32_t first, int32_t count,
     HIPCHK(hipMemcpyAsync(S_x_lm, h->mg_Sxl.as<double>() + (size_t)first * h->b * nl, (size_t)count * h->b * nl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
+}
+
+int gpslam_hip_get_landmark_marginals(gpslam_hip_handle *h, int32_t first, int32_t count, double *out) {
+  if (!h || count < 0 || (count > 0 && !out)) return GPSLAM_E_INVALID;
+  int rc = mg_refuse(h);
+  if (rc || (rc = mg_stale(h))) return rc;
+  if (first < 0 || first + count > h->L) return fail(h, GPSLAM_E_INVALID, "get_landmark_marginals: landmark window out of range");
+  (void)hipSetDevice(h->cfg.device);
+  std::vector<int32_t> idx(count);
+  for (int t = 0; t < count; t++) idx[t] = first + t;
+  return marginals_fs_gather(h, kMgGatherLmPair, count, idx.data(), idx.data(), out);
+}
+
+int gpslam_hip_get_state_landmark_marginals(gpslam_hip_handle *h, int32_t count, const int32_t *state, const int32_t *landmark, double *out) {
+  if (!h || count < 0 || (count > 0 && (!state || !landmark || !out))) return GPSLAM_E_INVALID;
+  int rc = mg_refuse(h);
+  if (rc || (rc = mg_stale(h))) return rc;
+  (void)hipSetDevice(h->cfg.device);
+  return marginals_fs_gather(h, kMgGatherStateLm, count, state, landmark, out);
+}
+
+int gpslam_hip_get_landmark_pair_marginals(gpslam_hip_handle *h, int32_t count, const int32_t *a, const int32_t *b, double *out) {
+  if (!h || count < 0 || (count > 0 && (!a || !b || !out))) return GPSLAM_E_INVALID;
+  int rc = mg_refuse(h);
+  if (rc || (rc = mg_stale(h))) return rc;
+  (void)hipSetDevice(h->cfg.device);
+  return marginals_fs_gather(h, kMgGatherLmPair, count, a, b, out);
 }
 
 int gpslam_hip_interpolate_covariances(gpslam_hip_handle *h, int32_t count, const int32_t *left, const double *dt,

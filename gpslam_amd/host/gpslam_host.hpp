@@ -897,13 +897,17 @@ class JointMarginal {
 
 /// gtsam::Marginals(graph, values): the Gauss-Newton Hessian of the whole graph at `values`, inverted on the device
 /// (gpslam_hip_marginals).  Served: single keys (x, v, w, b and landmark keys), joint sets whose state keys belong to one
-/// state or to two adjacent states, with any landmarks; other sets throw std::invalid_argument.
+/// state or to two adjacent states, with any landmarks; other sets throw std::invalid_argument.  On a graph that takes the segmented
+/// landmark path (more than 13 planar landmarks) the landmarks of a set must sit in the same or in neighbouring fat blocks, and next to
+/// the segment of the set's states -- every landmark a state observes does; sets beyond that throw std::invalid_argument as well.
 class Marginals {
  public:
   Marginals(const NonlinearFactorGraph &graph, const Values &values) {
     s_.build(graph, values);
     // (closures in column passes: who constructs Marginals has asked for the closures' columns to be kept at every state)
     detail::check(gpslam_hip_marginals_keep_closure_columns(s_.h, 1), s_.h, "marginals_keep_closure_columns");
+    // (... and on the segmented landmark path, for G at every interior state: the landmark blocks are gathered from it)
+    detail::check(gpslam_hip_marginals_on_segments(s_.h, 1), s_.h, "marginals_on_segments");
     detail::check(gpslam_hip_marginals(s_.h), s_.h, "marginals");
   }
   /// Marginals::marginalCovariance(variable)
@@ -922,11 +926,25 @@ class Marginals {
     }
     if (lo >= 0 && hi - lo > 1)
       throw std::invalid_argument("jointMarginalCovariance: the keys span non-adjacent states; only one state or two adjacent states (with any landmarks) are served");
-    const int b = 2 * s_.d, nl = s_.L * s_.ld, first = lo < 0 ? 0 : lo, count = lo < 0 ? 0 : hi - lo + 1;
-    std::vector<double> S((size_t)std::max(count, 1) * b * b), Sn(S.size()), Slm((size_t)std::max(nl * nl, 1)),
-        Sxl((size_t)std::max(count * b * nl, 1));
-    detail::check(gpslam_hip_get_marginals(s_.h, first, count, count ? S.data() : nullptr, count ? Sn.data() : nullptr,
-                                           nl ? Slm.data() : nullptr, (count && nl) ? Sxl.data() : nullptr), s_.h, "get_marginals");
+    const int b = 2 * s_.d, ld = s_.ld, first = lo < 0 ? 0 : lo, count = lo < 0 ? 0 : hi - lo + 1;
+    std::vector<double> S((size_t)std::max(count, 1) * b * b), Sn(S.size());
+    detail::check(gpslam_hip_get_marginals(s_.h, first, count, count ? S.data() : nullptr, count ? Sn.data() : nullptr, nullptr, nullptr),
+                  s_.h, "get_marginals");
+    // the landmarks of the set, through the getters that gather on the device what they are asked for (the only ones a session on
+    // the segmented landmark path has: S_lm and S_x_lm do not exist there): every pair of them, and each with every state of the set
+    std::vector<int32_t> lms;
+    for (const Var &v : vars)
+      if (v.state < 0 && std::find(lms.begin(), lms.end(), v.off / ld) == lms.end()) lms.push_back(v.off / ld);
+    const int nL = (int)lms.size();
+    auto pos = [&](int lm) { return (int)(std::find(lms.begin(), lms.end(), lm) - lms.begin()); };
+    std::vector<int32_t> pa, pb, xs, xl;
+    for (int u = 0; u < nL; u++)
+      for (int v = 0; v < nL; v++) { pa.push_back(lms[u]); pb.push_back(lms[v]); }
+    for (int t = 0; t < count; t++)
+      for (int v = 0; v < nL; v++) { xs.push_back(first + t); xl.push_back(lms[v]); }
+    std::vector<double> LL(std::max<size_t>(pa.size() * ld * ld, 1)), XL(std::max<size_t>(xs.size() * b * ld, 1));
+    served(gpslam_hip_get_landmark_pair_marginals(s_.h, (int32_t)pa.size(), pa.data(), pb.data(), LL.data()), "get_landmark_pair_marginals");
+    served(gpslam_hip_get_state_landmark_marginals(s_.h, (int32_t)xs.size(), xs.data(), xl.data(), XL.data()), "get_state_landmark_marginals");
     // one coordinate of the set: (state - first) * b + c for a state, or -1 - c for landmark coordinate c
     auto cov = [&](int p, int q) -> double {
       if (p >= 0 && q >= 0) {
@@ -934,9 +952,12 @@ class Marginals {
         if (sp == sq) return S[(size_t)sp * b * b + cp * b + cq];
         return sp < sq ? Sn[(size_t)sp * b * b + cp * b + cq] : Sn[(size_t)sq * b * b + cq * b + cp];
       }
-      if (p < 0 && q < 0) return Slm[(size_t)(-1 - p) * nl + (-1 - q)];
-      if (p >= 0) return Sxl[((size_t)(p / b) * b + p % b) * nl + (-1 - q)];
-      return Sxl[((size_t)(q / b) * b + q % b) * nl + (-1 - p)];
+      if (p < 0 && q < 0) {
+        const int cp = -1 - p, cq = -1 - q;
+        return LL[(((size_t)pos(cp / ld) * nL + pos(cq / ld)) * ld + cp % ld) * ld + cq % ld];
+      }
+      const int st = p >= 0 ? p : q, cl = -1 - (p >= 0 ? q : p);
+      return XL[(((size_t)(st / b) * nL + pos(cl / ld)) * b + st % b) * ld + cl % ld];
     };
     JointMarginal jm;
     jm.keys_ = keys;
@@ -975,6 +996,11 @@ class Marginals {
 
  private:
   struct Var { int state, off, dim; };   // state -1: landmark coordinates off .. off + dim
+  // a set the getters cannot serve (segmented sessions: landmarks beyond the neighbouring fat blocks) is the caller's error
+  void served(int rc, const char *what) const {
+    if (rc == GPSLAM_E_INVALID) throw std::invalid_argument(std::string("jointMarginalCovariance: ") + gpslam_hip_last_error(s_.h));
+    detail::check(rc, s_.h, what);
+  }
   Var var_of(Key k) const {
     auto it = s_.values.raw().find(k);
     if (it == s_.values.raw().end()) throw std::invalid_argument("Marginals: key not in the Values");

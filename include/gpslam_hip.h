@@ -80,7 +80,8 @@ enum {
  * gpslam_hip_create_v2 (named fields, struct_size first), gpslam_hip_abi_version, gpslam_hip_struct_size.  The v1 config and
  * gpslam_hip_create stay, bit for bit; 2.1 gpslam_hip_add_between_pairs (loop closures); 2.2 gpslam_hip_set_level0_stamps; 2.3
  * gpslam_hip_marginals, gpslam_hip_get_marginals, gpslam_hip_interpolate_covariances; 2.4 gpslam_hip_launch_census (and, added since without a bump,
- * gpslam_hip_set_closure_passes / gpslam_hip_closure_info / gpslam_hip_marginals_keep_closure_columns).  A MAJOR bump changes a struct or a
+ * gpslam_hip_set_closure_passes / gpslam_hip_closure_info / gpslam_hip_marginals_keep_closure_columns / gpslam_hip_marginals_on_segments /
+ * gpslam_hip_get_landmark_marginals / gpslam_hip_get_state_landmark_marginals / gpslam_hip_get_landmark_pair_marginals).  A MAJOR bump changes a struct or a
  * signature, a MINOR bump only adds. */
 #define GPSLAM_HIP_ABI_MAJOR 2
 #define GPSLAM_HIP_ABI_MINOR 4
@@ -419,7 +420,7 @@ int gpslam_hip_interpolate_poses_jac(gpslam_hip_handle *h, int32_t count, const 
  * The three pad coordinates of GPSLAM_ROT3_BIAS's velocity slot report zero rows and columns; the VW family reports its velocity
  * slot as stored, [v; w].  Computed on the device (selected inversion of the block-tridiagonal chain, landmarks and closures as a
  * low-rank term) and kept there.  GPSLAM_E_UNSUPPORTED on fp32 handles, sharded handles, split pieces and the segmented landmark
- * path; GPSLAM_E_NOT_SPD when H is indeterminate (e.g. nothing anchors the chain), as iterate_gn. */
+ * path (unless gpslam_hip_marginals_on_segments asks for it); GPSLAM_E_NOT_SPD when H is indeterminate (e.g. nothing anchors the chain), as iterate_gn. */
 int gpslam_hip_marginals(gpslam_hip_handle *h);
 /* Marginals on a handle whose closures go through the solver in column passes (gpslam_hip_set_closure_passes, P > 1).  There only
  * one slice of Z = A^-1 U^T (A the chain part of H, U the nc = closures * d whitened closure rows) exists at a time, and
@@ -431,12 +432,36 @@ int gpslam_hip_marginals(gpslam_hip_handle *h);
  * from before are stale.  enable == 0 (the default) restores the refusal.  On a handle with P <= 1 the call is accepted and
  * changes nothing.  GPSLAM_E_INVALID on a NULL handle.  The fp32, sharded, split and segmented refusals stay. */
 int gpslam_hip_marginals_keep_closure_columns(gpslam_hip_handle *h, int32_t enable);
+/* Marginals on the segmented landmark path (nested dissection with fat separators: the only path that holds more than 13 planar
+ * landmarks).  gpslam_hip_marginals refuses there by default.  enable != 0 lets it run: a solve's forward half at lambda = 0, then the
+ * selected inversion back through the fat chain and along every segment (marginals_fs.hip).  It keeps, until enable == 0 or destroy,
+ *     G = A_s^-1 H[I_s, B_s] at every interior state:  (N * b + 64) * NCP doubles  ~  N * b * NCP * 8 bytes,  NCP = 2 NB + 1 rounded up to 16
+ * (NB: the fat block size of gpslam_hip_segment_plan; about 3 GB at 1e6 SE(2) states with NB = 28) -- the state-landmark getter
+ * needs it -- and Sigma_{k,k}, Sigma_{k,k+1} of the fat blocks (about 3 K NB^2 doubles).  Fat blocks up to NB = 64 columns; wider ones
+ * answer GPSLAM_E_UNSUPPORTED (the message names NB and the limit).  Callable any time after create, no new compile() is needed;
+ * marginals held from before are stale.  enable == 0 (the default) restores the refusal and frees the buffers.  On a handle that is
+ * not segmented the call is accepted and changes nothing.  The fp32, sharded and split refusals stay.  Iterations after a
+ * gpslam_hip_marginals call are bit-identical to those of a handle that never made it.  GPSLAM_E_INVALID on a NULL handle. */
+int gpslam_hip_marginals_on_segments(gpslam_hip_handle *h, int32_t enable);
 /* copies the window [first, first + count) of S / S_next / S_x_lm (count x b x b, count x b x b, count x b x nl), and S_lm; any pointer
  * may be NULL.  GPSLAM_E_INVALID ("stale") before gpslam_hip_marginals, or after any call that can change states, landmarks,
  * factors or Qc since: set_states, set_landmarks, set_qc, add_*, set_meas_covariance, set_*_robust, clear_factors, compile, iterate_gn, iterate_lm,
  * run_gn, optimize. */
 int gpslam_hip_get_marginals(gpslam_hip_handle *h, int32_t first, int32_t count, double *S, double *S_next, double *S_lm,
                              double *S_x_lm);
+/* On a segmented handle S_lm / S_x_lm do not exist (nl x nl and N b x nl: 80 GB at 1e5 landmark coordinates): a non-NULL S_lm or
+ * S_x_lm answers GPSLAM_E_UNSUPPORTED there, S and S_next work as everywhere.  The landmark blocks come from three getters that
+ * gather on the device what they are asked for; same refusals and staleness rule as gpslam_hip_get_marginals, and they serve dense-border
+ * handles as well (from S_lm / S_x_lm):
+ *   get_landmark_marginals        out count x ld x ld: Sigma_{l,l} of the landmarks first .. first + count - 1
+ *   get_state_landmark_marginals  out count x b x ld:  Sigma_{state[t], landmark[t]}.  Segmented: the landmark must sit in a fat block
+ *                                 next to the state's segment (for a cut state: its own block or a neighbouring one) -- by the
+ *                                 attachment rule that covers every landmark the state observes; dense border: any pair
+ *   get_landmark_pair_marginals   out count x ld x ld: Sigma_{a[t], b[t]}.  Segmented: both in the same or in neighbouring fat blocks
+ * GPSLAM_E_INVALID (the message names the first such item) for a pair that cannot be served or an index out of range. */
+int gpslam_hip_get_landmark_marginals(gpslam_hip_handle *h, int32_t first, int32_t count, double *out);
+int gpslam_hip_get_state_landmark_marginals(gpslam_hip_handle *h, int32_t count, const int32_t *state, const int32_t *landmark, double *out);
+int gpslam_hip_get_landmark_pair_marginals(gpslam_hip_handle *h, int32_t count, const int32_t *a, const int32_t *b, double *out);
 /* Posterior covariance (count x d x d) of the GP-interpolated pose at tau[q] in (left[q], left[q] + 1), batched like
  * interpolate_poses -- the covariance half of the sparse-GP interpolation (Barfoot, Tong & Sarkka, RSS 2014), which GTSAM has no
  * call for:  P(tau) = H_J Sigma_J H_J^T + gp_term * c(dt, tau) * Qc,  H_J = [H1 H2 H3 H4] of interpolate_poses_jac,

@@ -53,6 +53,8 @@ ABI_SYMBOLS = [
     "gpslam_hip_marginals_keep_closure_columns",
     "gpslam_hip_marginals_on_segments", "gpslam_hip_get_landmark_marginals", "gpslam_hip_get_state_landmark_marginals",
     "gpslam_hip_get_landmark_pair_marginals",
+    "gpslam_hip_add_state_gaussians", "gpslam_hip_get_state_gaussians", "gpslam_hip_marginalize_head", "gpslam_hip_get_head_prior",
+    "gpslam_hip_append_states",
 ]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
@@ -190,6 +192,7 @@ class ChainSolver:
         self.d, self.pd = TANGENT_DIM[kind], POSE_DIM[kind]
         self.b = 2 * self.d
         self.N = self.L = self.n_gp = 0
+        self._gp_left = np.zeros(0, dtype=np.int64)     # left states of the GP priors, in the order added (marginalize_head drops those of the head)
         cfg = ConfigV2(struct_size=C.sizeof(ConfigV2), manifold=kind, precision=precision, device=device, chart=chart,
                        landmark_dim=landmark_dim, chunk=chunk, rank=rank, nranks=nranks,
                        force_sharded=1 if force_sharded else 0, upper_chunk=upper_chunk, top_blocks=top_blocks,
@@ -249,12 +252,14 @@ class ChainSolver:
     def add_gp_priors(self, left, dt):
         left, dt = _i32(left), _f64(dt)
         self.n_gp += len(left)
+        self._gp_left = np.concatenate([self._gp_left, left.astype(np.int64)])
         return self._chk(self.lib.gpslam_hip_add_gp_priors(self._h, len(left), _p(left), _p(dt)), "add_gp_priors")
 
     def add_gp_priors_qc(self, left, dt, Qc):
         """GP priors with one Qc_model per factor (count x d x d), as the reference's constructors take it."""
         left, dt, Qc = _i32(left), _f64(dt), _f64(Qc)
         self.n_gp += len(left)
+        self._gp_left = np.concatenate([self._gp_left, left.astype(np.int64)])
         return self._chk(self.lib.gpslam_hip_add_gp_priors_qc(self._h, len(left), _p(left), _p(dt), _p(Qc)), "add_gp_priors_qc")
 
     def set_meas_covariance(self, kind, cov):
@@ -392,8 +397,50 @@ class ChainSolver:
         return self._chk(self.lib.gpslam_hip_add_bearing_range(self._h, len(idx), _p(idx), _p(landmark), _p(bearing),
                                                                _p(rng), _p(sigmas)), "add_bearing_range")
 
+    # ---- fixed-lag smoothing (include/gpslam_hip.h "fixed-lag smoothing")
+    def add_state_gaussians(self, idx, pose_lin, vel_lin, A, c):
+        """gtsam::LinearContainerFactor over (x_i, v_i): r = A [Local(pose_lin, pose_i) ; vel_i - vel_lin] - c per factor, A (count, b, b)."""
+        idx = _i32(idx).reshape(-1)
+        n = len(idx)
+        pose_lin, vel_lin = _f64(pose_lin).reshape(n, self.pd), _f64(vel_lin).reshape(n, self.d)
+        A, c = _f64(A).reshape(n, self.b, self.b), _f64(c).reshape(n, self.b)
+        return self._chk(self.lib.gpslam_hip_add_state_gaussians(self._h, n, _p(idx), _p(pose_lin), _p(vel_lin), _p(A), _p(c)),
+                         "add_state_gaussians")
+
+    def get_state_gaussians(self):
+        """(idx, pose_lin, vel_lin, A, c) of the stored state Gaussians, in the order they stand."""
+        n = self._chk(self.lib.gpslam_hip_get_state_gaussians(self._h, None, None, None, None, None), "get_state_gaussians")
+        idx = np.zeros(n, dtype=np.int32)
+        pose_lin, vel_lin = np.zeros((n, self.pd)), np.zeros((n, self.d))
+        A, c = np.zeros((n, self.b, self.b)), np.zeros((n, self.b))
+        self._chk(self.lib.gpslam_hip_get_state_gaussians(self._h, _p(idx), _p(pose_lin), _p(vel_lin), _p(A), _p(c)), "get_state_gaussians")
+        return idx, pose_lin, vel_lin, A, c
+
+    def marginalize_head(self, k):
+        """Eliminates states 0 .. k - 1 and their factors into a state Gaussian on the new state 0; the handle then needs compile()."""
+        rc = self._chk(self.lib.gpslam_hip_marginalize_head(self._h, int(k)), "marginalize_head")
+        self.N -= int(k)
+        self._gp_left = self._gp_left[self._gp_left >= int(k)] - int(k)
+        self.n_gp = len(self._gp_left)
+        return rc
+
+    def get_head_prior(self):
+        """(pose_lin, vel_lin, Lambda, gamma) of the last marginalize_head, as the device computed them."""
+        pose_lin, vel_lin = np.zeros(self.pd), np.zeros(self.d)
+        Lam, gam = np.zeros((self.b, self.b)), np.zeros(self.b)
+        self._chk(self.lib.gpslam_hip_get_head_prior(self._h, _p(pose_lin), _p(vel_lin), _p(Lam), _p(gam)), "get_head_prior")
+        return pose_lin, vel_lin, Lam, gam
+
+    def append_states(self, pose, vel):
+        """n more states behind the last one; the factors stay, the handle needs compile()."""
+        pose, vel = _f64(pose).reshape(-1, self.pd), _f64(vel).reshape(-1, self.d)
+        rc = self._chk(self.lib.gpslam_hip_append_states(self._h, pose.shape[0], _p(pose), _p(vel)), "append_states")
+        self.N += pose.shape[0]
+        return rc
+
     def clear_factors(self):
         self.n_gp = 0
+        self._gp_left = np.zeros(0, dtype=np.int64)
         return self._chk(self.lib.gpslam_hip_clear_factors(self._h), "clear_factors")
 
     def compile(self):

@@ -156,6 +156,8 @@ int gpslam_hip_destroy(gpslam_hip_handle *h) {
   marginals_release(h);
   for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri}) s->release();
   h->clo.release();
+  h->sg.release();
+  h->fl_out.release(); h->fl_flag.release();
   for (MeasSet &s : h->ms) s.release();
   h->fs.release();
   h->lm_gL.release();
@@ -543,6 +545,7 @@ int gpslam_hip_clear_factors(gpslam_hip_handle *h) {
   for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri, &h->clo.fac}) { s->idx.clear(); s->meas.clear(); s->sig.clear(); }
   h->clo.second.clear();
   h->clo.rob.clear();
+  h->sg.clear();
   for (MeasSet &s : h->ms) {
     s.rob.clear();
     s.idx.clear(); s.lm.clear(); s.meas.clear(); s.sig.clear(); s.dt.clear(); s.tau.clear(); s.aux.clear(); s.aidx.clear(); s.sqi.clear();

@@ -80,6 +80,18 @@ struct Closures {
   void release() { fac.release(); for (DevBuf *b : {&d_second, &A, &Y, &d_rob, &w, &W, &X}) b->release(); }
 };
 
+// joint Gaussian factors on one state (gpslam_hip_add_state_gaussians; fixedlag.hip): r = A [Local(pose_lin, pose_i) ; vel_i - vel_lin] - c,
+// b full-width rows [A | 0] on left state idx.  The prior gpslam_hip_marginalize_head leaves on the new state 0 is one of them
+struct StateGauss {
+  std::vector<int32_t> idx;
+  std::vector<double> lin;     // per factor [pose_lin (pd) | vel_lin (d)]
+  std::vector<double> A, c;    // per factor b x b row-major, b
+  DevBuf d_idx, d_lin, d_A, d_c, d_row0;
+  int count() const { return (int)idx.size(); }
+  void clear() { idx.clear(); lin.clear(); A.clear(); c.clear(); }
+  void release() { for (DevBuf *b : {&d_idx, &d_lin, &d_A, &d_c, &d_row0}) b->release(); }
+};
+
 // Which kernels serve a compiled graph, and in which form.  make_plan() (api_impl.inc) fills one per compile(), once the row layout
 // is known, and nothing else writes it; what a single launch then does is launch_form(handle, LaunchMode) below.
 enum class Level0 { Column, Rows, Fused };     // level-0 elimination: k_chunk_forward, k_chunk_forward_rows, or k_fused_level0 where the mode asks for it
@@ -148,6 +160,9 @@ struct gpslam_hip_handle {
   SimpleSet pri, vpri, btw, lpri;
   Closures clo;
   MeasSet ms[kNumMeasKinds];
+  StateGauss sg;
+  std::vector<double> hp;     // gpslam_hip_get_head_prior: [pose_lin | vel_lin | Lambda | gamma] of the last marginalize_head, or empty
+  DevBuf fl_out, fl_flag;     // marginalize_head: [D_k^left | g_k^left | Lambda | g'_k | pose_k | vel_k] and the recursion's flag
   // row table
   int M = 0;
   DevBuf rowLR, rowE, rowM, rowLm, rowptr;
@@ -256,6 +271,12 @@ void closures_collect(gpslam_hip_handle *h, int p, bool keep_z);
 int closures_add(gpslam_hip_handle *h);
 // row length of W = U [X | Z] (CloPass::ldw)
 inline int clo_ldw(const gpslam_hip_handle *h) { return 1 + h->nl + h->clo.nc; }
+
+// State Gaussians (fixedlag.hip; fp64 only: compile() refuses them on an fp32 handle).  state_gauss_upload: compile()'s share (row0: the
+// first row of each factor in the full-width table).  state_gauss_eval: the rows [A | 0], their error entries (pass 0) and the error
+// partial sums, nblocks(count, 128) of them, on stream st.
+int state_gauss_upload(gpslam_hip_handle *h, const std::vector<int> &row0);
+void state_gauss_eval(gpslam_hip_handle *h, int pass, double *partial, hipStream_t st);
 
 #define HIPCHK(call)                                                                          \
   do {                                                                                        \

@@ -41,3 +41,6 @@ int marginals_assemble(gpslam_hip_handle *h);
 int marginals_border(gpslam_hip_handle *h);
 // the same on the segmented landmark path (marginals_fs.hip): fs_forward at lambda = 0 in the two-launch form, Y into the caller's buffer
 int marginals_fs_forward(gpslam_hip_handle *h, void *Y);
+// gpslam_hip_marginalize_head (fixedlag.hip): the rows and the records [D | O | g] of the current linearisation in the row form (the d = 3
+// GP priors as rows: the head's share of block k is summed from the tables)
+int fixedlag_assemble(gpslam_hip_handle *h);

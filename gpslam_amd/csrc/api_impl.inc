@@ -268,6 +268,10 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
     closures_eval(h, m, pass, reinterpret_cast<double *>(part + off), side);   // (RowT == double here)
     off += 1;
   }
+  if (kIsF64 && h->sg.count() > 0) {   // joint Gaussians on one state (fixedlag.hip): rows [A | 0] and their error
+    state_gauss_eval(h, pass, reinterpret_cast<double *>(part + off), side);   // (RowT == double here)
+    off += nblocks(h->sg.count(), 128);
+  }
   // (landmark priors have no Jacobian rows: on an fp32 handle their error belongs to the fp64 error pass alone)
   if (!kIsF64) {
   } else if (h->lpri.count() > 0 && h->fs.active) {   // tens of thousands of landmark priors: grid-stride, one partial per block
@@ -1113,6 +1117,7 @@ int check_stored_indices(gpslam_hip_handle *h) {
   for (const MeasSet &s : h->ms)
     if (bad(s.idx, s.two ? ml : N - 1) || (s.haslm && bad(s.lm, h->L - 1)))
       return fail(h, GPSLAM_E_INVALID, "a stored measurement factor refers to a state / landmark that no longer exists");
+  if (bad(h->sg.idx, N - 1)) return fail(h, GPSLAM_E_INVALID, "a stored state Gaussian refers to a state that no longer exists (set_states shrank the problem)");
   return 0;
 }
 
@@ -1170,6 +1175,13 @@ int choose_landmark_path(gpslam_hip_handle *h, bool &segmented) {
     if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "robust noise models (set_meas_robust / set_between_pairs_robust) on a sharded handle");
     if (h->fs.split) return fail(h, GPSLAM_E_UNSUPPORTED, "robust noise models (set_meas_robust / set_between_pairs_robust) on a piece of a split chain");
   }
+  if (h->sg.count() > 0) {   // joint Gaussians on one state (fixedlag.hip): the fp64 factor kernel of one unsharded handle with the dense border
+    if (!kIsF64) return fail(h, GPSLAM_E_UNSUPPORTED, "state Gaussians (add_state_gaussians) on an fp32 handle");
+    if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "state Gaussians (add_state_gaussians) on a sharded handle");
+    if (h->fs.split) return fail(h, GPSLAM_E_UNSUPPORTED, "state Gaussians (add_state_gaussians) on a piece of a split chain");
+    if (segmented) return fail(h, GPSLAM_E_UNSUPPORTED, "state Gaussians (add_state_gaussians) together with the segmented landmark elimination");
+    if (h->mf == ROT3_BIAS) return fail(h, GPSLAM_E_UNSUPPORTED, "state Gaussians (add_state_gaussians) on a GPSLAM_ROT3_BIAS handle (the pad coordinates of its velocity slot)");
+  }
   if (segmented) {
     if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "the segmented landmark elimination splits across GPUs through gpslam_hip_fs_set_split (pieces joined at shared cut states), not through nranks > 1");
     h->R = 1;   // no landmark columns inside the chain solver
@@ -1180,7 +1192,7 @@ int choose_landmark_path(gpslam_hip_handle *h, bool &segmented) {
 // Where every factor's rows sit in the two row tables, and what the record forms need to know about that placement
 struct RowLayout {
   std::vector<int> rowptr, crowptr;                                        // N + 2 row pointers: full-width table, compact table
-  std::vector<int> gp_row0, r_pri, r_vpri, r_btw, r_ms[kNumMeasKinds];    // first row of every factor
+  std::vector<int> gp_row0, r_pri, r_vpri, r_sg, r_btw, r_ms[kNumMeasKinds];    // first row of every factor
   std::vector<int> gpidx, btwidx;          // N + 2 entries: the GP prior / between factor whose left state is s, or -1
   bool one_gp = true, one_btw = true;      // at most one GP prior / between factor per left state
   bool gp_rows_lead = true, btw_rows_trail = true;
@@ -1194,13 +1206,14 @@ bool index_by_left(const std::vector<int32_t> &left, int N, std::vector<int> &id
   }
   return one;
 }
-// rows grouped by left state; inside a state: GP, pose prior, velocity prior, between, measurements.  Pose priors and between
+// rows grouped by left state; inside a state: GP, pose prior, velocity prior, state Gaussian, between, measurements.  Pose priors and between
 // factors are velocity-free: their rows go to the compact table.
 void layout_rows(gpslam_hip_handle *h, RowLayout &lay) {
   const int N = h->N, d = h->d, b = h->b;
   std::vector<int> rows_in(N + 1, 0), crows_in(N + 1, 0);
   for (int32_t l : h->gp_left) rows_in[l] += b;
   for (int32_t i : h->vpri.idx) rows_in[i] += d;
+  for (int32_t i : h->sg.idx) rows_in[i] += b;
   for (int32_t i : h->pri.idx) crows_in[i] += d;
   for (int32_t i : h->btw.idx) crows_in[i] += d;
   for (MeasSet &s : h->ms) for (int32_t i : s.idx) rows_in[i] += s.rows;
@@ -1217,6 +1230,7 @@ void layout_rows(gpslam_hip_handle *h, RowLayout &lay) {
   place(cursor, h->gp_left, b, lay.gp_row0);
   place(ccursor, h->pri.idx, d, lay.r_pri);
   place(cursor, h->vpri.idx, d, lay.r_vpri);
+  place(cursor, h->sg.idx, b, lay.r_sg);
   place(ccursor, h->btw.idx, d, lay.r_btw);
   for (int fk = 0; fk < kNumMeasKinds; fk++) place(cursor, h->ms[fk].idx, h->ms[fk].rows, lay.r_ms[fk]);
   // What the record decoders assume about this placement (k_assemble_ghost's `rp_s += B`, k_fused_level0's `p0 += B` / `q1 -= Dh`):
@@ -1266,9 +1280,10 @@ int upload_factors(gpslam_hip_handle *h, const RowLayout &lay, int &npart) {
   if ((rc = upload_set(h, h->btw, lay.r_btw))) return rc;
   if ((rc = upload_set(h, h->lpri, std::vector<int>()))) return rc;
   if (h->clo.n > 0 && (rc = closures_upload(h))) return rc;
+  if (h->sg.count() > 0 && (rc = state_gauss_upload(h, lay.r_sg))) return rc;
   // (one k_gp launch per distinct Qc, each rounding its factor count up to whole blocks: at most one extra slot per group)
   npart = nblocks((int)h->gp_left.size(), 128) + gp_ngroups(h) + nblocks(h->pri.count(), 128) + nblocks(h->vpri.count(), 128) +
-          nblocks(h->btw.count(), 128) + 1 + 256 + 1;   // (+ 1: the loop closures' error)
+          nblocks(h->btw.count(), 128) + 1 + 256 + 1 + nblocks(h->sg.count(), 128);   // (+ 1: the loop closures' error)
   for (int fk = 0; fk < kNumMeasKinds; fk++) {
     MeasSet &s = h->ms[fk];
     if ((rc = upload(h, s.d_idx, s.idx))) return rc;
@@ -1512,6 +1527,7 @@ int make_plan(gpslam_hip_handle *h, const RowLayout &lay) {
     // -- those kinds that read two states (the interpolated ones) apply the pending update themselves from the old buffer
     for (int fk = 0; fk < kNumMeasKinds && ok; fk++) ok = h->ms[fk].count() == 0 || se3 || h->ms[fk].two;
     for (int f = 0; f < ngp && ok; f++) ok = h->gp_left[f] < N - 1;     // (one per left state: rec_ok)
+    ok = ok && h->sg.count() == 0;      // (the state Gaussians' kernel reads the stored states: it applies no pending update)
     p.fold_retract = ok && !plan_bit(h, GPSLAM_PLAN_SEPARATE_RETRACT);
   }
   {   // interpolated measurement rows as 16-double lines next to the records (k_fused_level0<4>, kernels.hpp kIRow*): every
@@ -1519,7 +1535,7 @@ int make_plan(gpslam_hip_handle *h, const RowLayout &lay) {
       // record holds X, J and F of that interval); no landmarks (fused), no velocity priors
     const MeasSet &g = h->ms[FK_INTERP_GPS];
     // (a robust GPS factor needs |e| over its three rows before any of them is final: the row form through k_meas, as GPSLAM_PLAN_MEAS_ROWS)
-    bool ok = se3 && !plan_bit(h, GPSLAM_PLAN_MEAS_ROWS) && g.rob.empty() && h->vpri.count() == 0 && g.count() > 0;
+    bool ok = se3 && !plan_bit(h, GPSLAM_PLAN_MEAS_ROWS) && g.rob.empty() && h->vpri.count() == 0 && h->sg.count() == 0 && g.count() > 0;
     for (int fk = 0; fk < kNumMeasKinds && ok; fk++) ok = (fk == FK_INTERP_GPS) || h->ms[fk].count() == 0;
     for (size_t f = 0; f < g.idx.size() && ok; f++) ok = lay.gpidx[g.idx[f]] >= 0;
     p.lines = ok;
@@ -1728,6 +1744,14 @@ int marginals_assemble(gpslam_hip_handle *h) {
   int rc;
   if ((rc = launch_factors(h, LaunchMode{}, 0, 0))) return rc;
   return launch_assemble(h, LaunchMode{}, false);
+}
+// gpslam_hip_marginalize_head (fixedlag.hip): the same in the row form -- the d = 3 GP priors as rows, so that the tables hold every row
+int fixedlag_assemble(gpslam_hip_handle *h) {
+  LaunchMode m;
+  m.d3_rows = true;
+  int rc;
+  if ((rc = launch_factors(h, m, 0, 0))) return rc;
+  return launch_assemble(h, m, false);
 }
 // ... and the solver's right-hand sides at lambda = 0: the closure columns Z = A^-1 J_c^T, the landmark columns corrected for the
 // closures, and the landmark Schur complement S of the whole chain -- launch_solve without the landmark solve (the states stay).

@@ -17,6 +17,7 @@
 // the analogue of GTSAM's exceptions; HIP failures throw std::runtime_error.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -326,7 +327,7 @@ class Values {
 // ---------------------------------------------------------------- factors
 namespace detail {
 enum FType { F_GP, F_POSE_PRIOR, F_VEL_PRIOR, F_LM_PRIOR, F_BETWEEN, F_INTERP_RANGE, F_RANGE, F_INTERP_ATT, F_INTERP_GPS, F_ODOM2D, F_BEARING_RANGE, F_INTERP_PROJ,
-             F_BIAS_PRIOR, F_BIAS_BETWEEN, F_AHRS, F_ATTITUDE };
+             F_BIAS_PRIOR, F_BIAS_BETWEEN, F_AHRS, F_ATTITUDE, F_STATE_GAUSS };
 struct Desc {   // what a factor hands to the graph compiler
   FType type;
   int manifold = -1;                 // GPSLAM_* the factor requires, -1 = any
@@ -629,9 +630,14 @@ struct Session {
     if (rc < 0) throw std::runtime_error("gpslam_hip_create_v2 failed: no usable HIP device (there is no CPU fallback)");
     check(gpslam_hip_set_states(h, N, P.data(), V.data()), h, "set_states");
     if (L > 0) check(gpslam_hip_set_landmarks(h, L, LM.data()), h, "set_landmarks");
-    // ---- factors
-    bool qc_set = false;
-    int closures = 0;                  // BetweenFactors between non-adjacent states
+    add_factors(graph);
+    finish(0);
+  }
+
+  bool qc_set = false;
+  int closures = 0;                  // BetweenFactors between non-adjacent states
+  // the factors of `graph` onto the handle: build(), and BatchFixedLagSmoother::update for the factors that arrive later
+  void add_factors(const NonlinearFactorGraph &graph) {
     std::vector<double> qc_used;
     for (auto &fp : graph.factors()) {
       const Desc f = fp->describe();
@@ -737,10 +743,20 @@ struct Session {
         case F_INTERP_PROJ: { set_qc(f.Qc); int32_t l = adjacent(f.k[0], f.k[2]), m = lm_of(f.k[4]);
           check((f.aux.size() == 9 ? gpslam_hip_add_interp_projection_ds2 : gpslam_hip_add_interp_projection)(h, 1, &l, &m, f.meas.data(), f.sig.data(), &f.dt, &f.tau, f.aux.data(), sens), h,
                 "add_interp_projection"); gaussian(GPSLAM_MEAS_INTERP_PROJECTION); } break;
+        case F_STATE_GAUSS: {   // gtsam::LinearContainerFactor over (x_s, v_s): meas = [pose_lin | vel_lin], aux = A, sig = c
+          if (vw || bias) throw std::invalid_argument("LinearContainerFactor: not on Pose3VW or AHRS graphs");
+          if (symbolIndex(f.k[0]) != symbolIndex(f.k[1])) throw std::invalid_argument("LinearContainerFactor: pose and velocity keys of a state must share their index");
+          if ((int)f.meas.size() != pd + d || (int)f.aux.size() != 4 * d * d || (int)f.sig.size() != 2 * d)
+            throw std::invalid_argument("LinearContainerFactor: A must be 2d x 2d and b 2d for the manifold of the Values");
+          int32_t st = state_of(f.k[0]);
+          check(gpslam_hip_add_state_gaussians(h, 1, &st, f.meas.data(), f.meas.data() + pd, f.aux.data(), f.sig.data()), h, "add_state_gaussians");
+        } break;
       }
     }
-    // states whose velocity is not a variable of the user's graph: pin a zero velocity (decoupled, zero error)
-    for (int s = 0; s < N; s++) {
+  }
+  // states from `first` on whose velocity is not a variable of the user's graph: pin a zero velocity (decoupled, zero error); compile
+  void finish(int first) {
+    for (int s = first; s < N; s++) {
       if (has_vel[s]) continue;
       std::vector<double> z(d, 0.0), one(d, 1.0);
       int32_t idx = s;
@@ -868,6 +884,148 @@ class LevenbergMarquardtOptimizer : public NonlinearOptimizer {
  private:
   LevenbergMarquardtParams lm_;
   double lambda_;
+};
+
+// ---------------------------------------------------------------- fixed-lag smoothing
+/// gtsam::LinearContainerFactor (gtsam/nonlinear/LinearContainerFactor.h) over the two keys of one state: a Gaussian |A xi - b|^2 / 2
+/// on xi = [Local(lin_x, x) ; v - lin_v], linearised with the constant Jacobian A as LinearContainerFactor::linearize does (exact at
+/// the linearisation point, first order away from it).  A is 2d x 2d, b 2d; maps to gpslam_hip_add_state_gaussians.
+class LinearContainerFactor : public NonlinearFactor {
+ public:
+  template <typename POSE, typename VEL>
+  LinearContainerFactor(Key poseKey, Key velKey, const Matrix &A, const Vector &b, const POSE &lin_pose, const VEL &lin_vel) {
+    if (A.rows != A.cols || (size_t)A.rows != b.size()) throw std::invalid_argument("LinearContainerFactor: A must be square and b of its size");
+    d_.type = detail::F_STATE_GAUSS; d_.k[0] = poseKey; d_.k[1] = velKey;
+    d_.meas = detail::VT<POSE>::pack(lin_pose);
+    const std::vector<double> lv = detail::VT<VEL>::pack(lin_vel);
+    d_.meas.insert(d_.meas.end(), lv.begin(), lv.end());
+    d_.aux = A.a; d_.sig = b;
+  }
+  size_t size() const override { return 2; }
+  NonlinearFactor::shared_ptr clone() const override { return std::make_shared<LinearContainerFactor>(*this); }
+  detail::Desc describe() const override { return d_; }
+  bool equals(const NonlinearFactor &expected, double tol = 1e-9) const override {
+    const LinearContainerFactor *e = dynamic_cast<const LinearContainerFactor *>(&expected);
+    return e != nullptr && detail::desc_equals(d_, e->d_, tol, false);
+  }
+  void print(const std::string &s = "", const KeyFormatter &kf = DefaultKeyFormatter) const override {
+    std::cout << s << "LinearContainerFactor" << std::endl << "  keys = { " << kf(d_.k[0]) << " " << kf(d_.k[1]) << " }" << std::endl;
+  }
+ protected:
+  detail::Desc d_;
+};
+
+/// gtsam::BatchFixedLagSmoother (gtsam_unstable/nonlinear/BatchFixedLagSmoother.h) on a chain: update() adds the new factors and
+/// values, marginalises the leading states whose time stamp is older than (latest - lag) into a Gaussian on the oldest kept state
+/// (gpslam_hip_marginalize_head: elimination at the current linearisation, as GTSAM's), re-compiles and optimises with the
+/// Levenberg-Marquardt parameters.  New states continue the chain: their pose keys carry larger indices than every key seen so far.
+class BatchFixedLagSmoother {
+ public:
+  typedef std::map<Key, double> KeyTimestampMap;
+  struct Result { int iterations = 0; double error = 0.0; int marginalized = 0; };
+  explicit BatchFixedLagSmoother(double smootherLag = 0.0, const LevenbergMarquardtParams &params = LevenbergMarquardtParams())
+      : lag_(smootherLag), params_(params) {}
+  double smootherLag() const { return lag_; }
+  const KeyTimestampMap &timestamps() const { return stamps_; }
+  gpslam_hip_handle *handle() const { return s_ ? s_->h : nullptr; }
+
+  Result update(const NonlinearFactorGraph &newFactors = NonlinearFactorGraph(), const Values &newTheta = Values(),
+                const KeyTimestampMap &timestamps = KeyTimestampMap()) {
+    for (auto &kv : timestamps) stamps_[kv.first] = kv.second;
+    std::map<uint64_t, Key> pose_keys;                      // of the new values, in chain order
+    for (auto &kv : newTheta.raw()) {
+      const unsigned char c = symbolChr(kv.first);
+      const bool point = kv.second.type == detail::T_POINT2 || kv.second.type == detail::T_POINT3;
+      if (!point && c != 'v' && c != 'w' && c != 'b') pose_keys[symbolIndex(kv.first)] = kv.first;
+    }
+    if (!s_) {
+      s_.reset(new detail::Session());
+      s_->build(newFactors, newTheta);
+    } else {
+      extend(newFactors, newTheta, pose_keys);
+    }
+    for (auto &kv : pose_keys) keys_.push_back(kv.second);
+    // the leading states that fell out of the lag
+    Result r;
+    double latest = -INFINITY;
+    for (Key k : keys_) { auto it = stamps_.find(k); if (it != stamps_.end()) latest = std::max(latest, it->second); }
+    auto old = [&](Key k) { auto it = stamps_.find(k); return it != stamps_.end() && it->second < latest - lag_; };
+    int k = 0;
+    while (k < (int)keys_.size() && old(keys_[k])) k++;
+    for (size_t i = k; i < keys_.size(); i++)
+      if (old(keys_[i])) throw std::invalid_argument("BatchFixedLagSmoother: key " + DefaultKeyFormatter(keys_[i]) + " is older than the lag but not at the head of the chain");
+    k = std::min(k, (int)keys_.size() - 1);
+    if (k >= 1) {
+      detail::check(gpslam_hip_marginalize_head(s_->h, k), s_->h, "marginalize_head");
+      for (int i = 0; i < k; i++) {
+        const uint64_t idx = s_->state_index[i];
+        for (auto it = s_->values.raw().begin(); it != s_->values.raw().end();) {
+          const bool point = it->second.type == detail::T_POINT2 || it->second.type == detail::T_POINT3;
+          if (!point && symbolIndex(it->first) == idx) { stamps_.erase(it->first); it = s_->values.raw().erase(it); } else ++it;
+        }
+      }
+      s_->state_index.erase(s_->state_index.begin(), s_->state_index.begin() + k);
+      s_->has_vel.erase(s_->has_vel.begin(), s_->has_vel.begin() + k);
+      keys_.erase(keys_.begin(), keys_.begin() + k);
+      s_->N -= k;
+      detail::check(gpslam_hip_compile(s_->h), s_->h, "compile");
+      r.marginalized = k;
+    }
+    gpslam_hip_params p;
+    gpslam_hip_default_params(&p);
+    p.use_lm = 1; p.max_iterations = params_.maxIterations; p.relative_error_tol = params_.relativeErrorTol;
+    p.absolute_error_tol = params_.absoluteErrorTol; p.error_tol = params_.errorTol; p.lambda_initial = params_.lambdaInitial;
+    p.lambda_factor = params_.lambdaFactor; p.lambda_upper_bound = params_.lambdaUpperBound; p.lambda_lower_bound = params_.lambdaLowerBound;
+    p.min_model_fidelity = params_.minModelFidelity;
+    gpslam_hip_stats st;
+    detail::check(gpslam_hip_optimize(s_->h, &p, &st), s_->h, "optimize");
+    r.iterations = st.iterations; r.error = st.error_after;
+    return r;
+  }
+  /// the current estimate of every variable still in the window (and of the landmarks)
+  Values calculateEstimate() {
+    if (!s_) return Values();
+    s_->pull();
+    return s_->values;
+  }
+
+ private:
+  void extend(const NonlinearFactorGraph &newFactors, const Values &newTheta, const std::map<uint64_t, Key> &pose_keys) {
+    detail::Session &s = *s_;
+    if (s.vw || s.bias) throw std::invalid_argument("BatchFixedLagSmoother: Pose3VW and AHRS graphs cannot be extended");
+    const int n = (int)pose_keys.size(), first = s.N;
+    std::vector<double> P((size_t)n * s.pd), V((size_t)n * s.d, 0.0);
+    int i = 0;
+    for (auto &kv : pose_keys) {
+      if (kv.first <= s.state_index.back()) throw std::invalid_argument("BatchFixedLagSmoother: new states must continue the chain (larger key indices)");
+      const detail::Value &val = newTheta.raw().at(kv.second);
+      if (detail::Session::manifold_of(val.type) != s.manifold) throw std::invalid_argument("mixed pose types");
+      std::memcpy(&P[(size_t)i * s.pd], val.d.data(), sizeof(double) * s.pd);
+      const auto vi = newTheta.raw().find(Symbol('v', kv.first));
+      const bool hv = vi != newTheta.raw().end();
+      if (hv) {
+        if ((int)vi->second.d.size() != s.d) throw std::invalid_argument("velocity dimension does not match the pose manifold");
+        std::memcpy(&V[(size_t)i * s.d], vi->second.d.data(), sizeof(double) * s.d);
+      }
+      s.state_index.push_back(kv.first);
+      s.has_vel.push_back(hv);
+      i++;
+    }
+    for (auto &kv : newTheta.raw()) {
+      if (kv.second.type == detail::T_POINT2 || kv.second.type == detail::T_POINT3) throw std::invalid_argument("BatchFixedLagSmoother: landmarks arrive with the first update");
+      if (s.values.exists(kv.first)) throw std::invalid_argument("BatchFixedLagSmoother: key already exists");
+      s.values.raw()[kv.first] = kv.second;
+    }
+    if (n > 0) detail::check(gpslam_hip_append_states(s.h, n, P.data(), V.data()), s.h, "append_states");
+    s.N += n;
+    s.add_factors(newFactors);
+    s.finish(first);
+  }
+  double lag_;
+  LevenbergMarquardtParams params_;
+  std::unique_ptr<detail::Session> s_;
+  std::vector<Key> keys_;          // pose keys of the states in the window, in chain order
+  KeyTimestampMap stamps_;
 };
 
 // ---------------------------------------------------------------- gtsam::Marginals (gtsam/nonlinear/Marginals.h, GTSAM 4.0)

@@ -81,7 +81,8 @@ enum {
  * gpslam_hip_create stay, bit for bit; 2.1 gpslam_hip_add_between_pairs (loop closures); 2.2 gpslam_hip_set_level0_stamps; 2.3
  * gpslam_hip_marginals, gpslam_hip_get_marginals, gpslam_hip_interpolate_covariances; 2.4 gpslam_hip_launch_census (and, added since without a bump,
  * gpslam_hip_set_closure_passes / gpslam_hip_closure_info / gpslam_hip_marginals_keep_closure_columns / gpslam_hip_marginals_on_segments /
- * gpslam_hip_get_landmark_marginals / gpslam_hip_get_state_landmark_marginals / gpslam_hip_get_landmark_pair_marginals).  A MAJOR bump changes a struct or a
+ * gpslam_hip_get_landmark_marginals / gpslam_hip_get_state_landmark_marginals / gpslam_hip_get_landmark_pair_marginals /
+ * gpslam_hip_add_state_gaussians / gpslam_hip_get_state_gaussians / gpslam_hip_marginalize_head / gpslam_hip_get_head_prior / gpslam_hip_append_states).  A MAJOR bump changes a struct or a
  * signature, a MINOR bump only adds. */
 #define GPSLAM_HIP_ABI_MAJOR 2
 #define GPSLAM_HIP_ABI_MINOR 4
@@ -340,6 +341,50 @@ int gpslam_hip_get_between_pairs_weights(gpslam_hip_handle *h, double *w);
  * r >= 0 and finite; NONE gives 1 and r^2 / 2. */
 int gpslam_hip_robust_eval(int32_t loss, double k, double r, double *w, double *rho);
 
+/* ---- fixed-lag smoothing (added without an ABI bump: a binding detects these entry points by their presence) ----
+ * The reference's method is incremental GP regression; these calls let a handle slide along a live trajectory instead of growing for
+ * ever: the old states are eliminated at the current linearisation and the Gaussian they leave on the oldest kept state stays in the
+ * graph, as gtsam::BatchFixedLagSmoother does it with a gtsam::LinearContainerFactor (gtsam_unstable/nonlinear/BatchFixedLagSmoother.h,
+ * gtsam/nonlinear/LinearContainerFactor.h; third party).  All of them want an fp64 handle that is single (not sharded, not a piece of
+ * a split chain) and off the segmented landmark path: GPSLAM_E_UNSUPPORTED with a message otherwise.
+ *
+ * A joint Gaussian factor on ONE state -- gtsam::LinearContainerFactor over the keys (x_i, v_i).  Per factor: a linearisation point
+ * (pose_lin in the layout of set_states, vel_lin d doubles), A (b x b row-major, b = 2d; any finite matrix, zero rows allowed) and
+ * c (b); a value that is not finite in any of the four: GPSLAM_E_INVALID.  With xi = [Local(pose_lin, pose_i) ; vel_i - vel_lin] in the handle's chart (GPSLAM_VELOCITY_WORLD_VW: the plain
+ * difference of the stored [v; w]) the whitened residual is r = A xi - c and the cost |r|^2 / 2.  The Jacobian is the CONSTANT A on
+ * state i's columns [pose tangent | velocity] -- what LinearContainerFactor::linearize does: exact at xi = 0, first order away from
+ * it (the derivative of Local is taken as the identity).  b full-width rows [A | 0] on left state i, behind the velocity priors'
+ * (gpslam_hip_get_rows lists them there; a graph without such a factor keeps its order); i = N - 1 is allowed.  Gauss-Newton,
+ * Levenberg-Marquardt, optimize, error, normal_equations and marginals include them; clear_factors drops them.  compile() answers
+ * GPSLAM_E_UNSUPPORTED on a GPSLAM_ROT3_BIAS handle that carries one. */
+int gpslam_hip_add_state_gaussians(gpslam_hip_handle *h, int32_t count, const int32_t *idx, const double *pose_lin, const double *vel_lin,
+                                   const double *A, const double *c);
+/* the stored factors in the order they stand (any pointer may be NULL); returns the count */
+int gpslam_hip_get_state_gaussians(gpslam_hip_handle *h, int32_t *idx, double *pose_lin, double *vel_lin, double *A, double *c);
+/* Marginalise the head: states 0 .. k - 1 (1 <= k <= N - 1) of a compiled handle.  The head is every stored factor that touches a
+ * state < k: GP priors, between factors, odometry and two-state measurement factors with left < k; unary factors and single-state
+ * measurements with idx < k; state Gaussians with idx < k (the previous head prior among them).  A factor on state k alone or on
+ * the interval (k, k + 1) is not in it.  With q(delta_0 .. delta_k) = |J_h delta + r_h|^2 / 2 the head's whitened linearisation at
+ * the current states (lambda = 0 and the robust weights, as gpslam_hip_marginals linearises),
+ *     min over delta_0 .. delta_{k-1} of q  =  delta_k^T Lambda delta_k / 2 + gamma^T delta_k + const
+ * is computed on the device (a pending update of run_gn is applied first).  Then the handle holds a state Gaussian on the new state 0
+ * with the current (pose_k, vel_k) as linearisation point, A^T A = Lambda and A^T c = -gamma; states 0 .. k - 1 and every head
+ * factor are gone, the remaining state indices are k lower (landmark indices stay), N is N - k, and the handle needs compile():
+ * until then the iteration calls answer GPSLAM_E_NOT_COMPILED; marginals held from before are stale.  The constant of the minimum is
+ * dropped, as GTSAM's elimination drops it: gpslam_hip_error is lower afterwards.  Lambda is symmetrised and factorised by Cholesky
+ * with diagonal pivoting; pivots below b * eps * max|diag| of the head's own share of block k (before the subtraction) become zero
+ * rows of A, so a head without absolute information (Lambda ~ 0) works.
+ * Refusals, all before anything changes (the handle then iterates exactly as if the call had not been made): k out of range
+ * GPSLAM_E_INVALID; not compiled GPSLAM_E_NOT_COMPILED; GPSLAM_E_UNSUPPORTED for a head factor that names a landmark (the message
+ * names kind and factor), for a loop closure with first < k or second < k, and on fp32 / sharded / split / segmented /
+ * GPSLAM_ROT3_BIAS handles.  GPSLAM_E_NOT_SPD when a pivot block of the head is not positive definite. */
+int gpslam_hip_marginalize_head(gpslam_hip_handle *h, int32_t k);
+/* linearisation point, Lambda (b x b) and gamma (b) of the last successful marginalize_head, as the device computed them (any
+ * pointer may be NULL); GPSLAM_E_INVALID before the first one */
+int gpslam_hip_get_head_prior(gpslam_hip_handle *h, double *pose_lin, double *vel_lin, double *Lambda, double *gamma);
+/* n more states behind the last one (layouts of set_states), placed on the device; the factors stay; the handle needs compile() */
+int gpslam_hip_append_states(gpslam_hip_handle *h, int32_t n, const double *pose, const double *vel);
+
 /* drop every factor added so far (states, landmarks and Qc stay); the handle needs a new compile() */
 int gpslam_hip_clear_factors(gpslam_hip_handle *h);
 
@@ -388,7 +433,7 @@ int gpslam_hip_optimize(gpslam_hip_handle *h, const gpslam_hip_params *p, gpslam
 int gpslam_hip_normal_equations(gpslam_hip_handle *h, double *D, double *O, double *g, double *B);
 /* whitened Jacobian rows of the current linearisation (what NoiseModelFactor::linearize produces after
  * WhitenSystem): rowLR M x 4d = [d/dx_left | d/dx_right], rowE M, rowM M x landmark_dim, rowLm M (landmark id or -1).
- * Row order: first the rows with velocity columns, grouped by left state (inside a state: GP priors, velocity priors,
+ * Row order: first the rows with velocity columns, grouped by left state (inside a state: GP priors, velocity priors, state Gaussians,
  * then interpolated range, range, attitude, GPS, odometry2d, bearing-range, projection, each in the order they were
  * added); then the velocity-free rows (pose priors, between factors; the device keeps them in a half-width table),
  * again grouped by left state, expanded to full width.  Any output pointer may be NULL; n_rows receives M. */

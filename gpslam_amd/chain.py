@@ -55,6 +55,8 @@ ABI_SYMBOLS = [
     "gpslam_hip_get_landmark_pair_marginals",
     "gpslam_hip_add_state_gaussians", "gpslam_hip_get_state_gaussians", "gpslam_hip_marginalize_head", "gpslam_hip_get_head_prior",
     "gpslam_hip_append_states",
+    "gpslam_hip_add_border_gaussians", "gpslam_hip_get_border_gaussians", "gpslam_hip_marginalize_head_onto_landmarks",
+    "gpslam_hip_get_head_prior_border",
 ]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
@@ -430,6 +432,42 @@ class ChainSolver:
         Lam, gam = np.zeros((self.b, self.b)), np.zeros(self.b)
         self._chk(self.lib.gpslam_hip_get_head_prior(self._h, _p(pose_lin), _p(vel_lin), _p(Lam), _p(gam)), "get_head_prior")
         return pose_lin, vel_lin, Lam, gam
+
+    def add_border_gaussians(self, idx, pose_lin, vel_lin, lm_lin, A, c):
+        """gtsam::LinearContainerFactor over (x_i, v_i, every landmark): r = A [Local(pose_lin, pose_i) ; vel_i - vel_lin ; l - lm_lin] - c
+        per factor, A (count, n, n), n = b + L * landmark_dim."""
+        idx = _i32(idx).reshape(-1)
+        m, nl = len(idx), self.L * self.ld
+        n = self.b + nl
+        pose_lin, vel_lin, lm_lin = _f64(pose_lin).reshape(m, self.pd), _f64(vel_lin).reshape(m, self.d), _f64(lm_lin).reshape(m, nl)
+        A, c = _f64(A).reshape(m, n, n), _f64(c).reshape(m, n)
+        return self._chk(self.lib.gpslam_hip_add_border_gaussians(self._h, m, _p(idx), _p(pose_lin), _p(vel_lin), _p(lm_lin), _p(A), _p(c)),
+                         "add_border_gaussians")
+
+    def get_border_gaussians(self):
+        """(idx, pose_lin, vel_lin, lm_lin, A, c) of the stored border Gaussians, in the order they stand."""
+        m = self._chk(self.lib.gpslam_hip_get_border_gaussians(self._h, None, None, None, None, None, None), "get_border_gaussians")
+        nl = self.L * self.ld
+        n = self.b + nl
+        idx = np.zeros(m, dtype=np.int32)
+        pose_lin, vel_lin, lm_lin = np.zeros((m, self.pd)), np.zeros((m, self.d)), np.zeros((m, nl))
+        A, c = np.zeros((m, n, n)), np.zeros((m, n))
+        if m:
+            self._chk(self.lib.gpslam_hip_get_border_gaussians(self._h, _p(idx), _p(pose_lin), _p(vel_lin), _p(lm_lin), _p(A), _p(c)),
+                      "get_border_gaussians")
+        return idx, pose_lin, vel_lin, lm_lin, A, c
+
+    def marginalize_head_onto_landmarks(self, enable=True):
+        """marginalize_head accepts head factors that name landmarks and leaves a border Gaussian on (state 0, landmarks)."""
+        return self._chk(self.lib.gpslam_hip_marginalize_head_onto_landmarks(self._h, 1 if enable else 0), "marginalize_head_onto_landmarks")
+
+    def get_head_prior_border(self):
+        """(lm_lin, Lambda, gamma) over (state, landmarks) of the last marginalize_head onto the landmarks, as the device computed them."""
+        nl = self.L * self.ld
+        n = self.b + nl
+        lm_lin, Lam, gam = np.zeros((self.L, self.ld)), np.zeros((n, n)), np.zeros(n)
+        self._chk(self.lib.gpslam_hip_get_head_prior_border(self._h, _p(lm_lin), _p(Lam), _p(gam)), "get_head_prior_border")
+        return lm_lin, Lam, gam
 
     def append_states(self, pose, vel):
         """n more states behind the last one; the factors stay, the handle needs compile()."""

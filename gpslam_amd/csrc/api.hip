@@ -157,7 +157,8 @@ int gpslam_hip_destroy(gpslam_hip_handle *h) {
   for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri}) s->release();
   h->clo.release();
   h->sg.release();
-  h->fl_out.release(); h->fl_flag.release();
+  h->bg.release();
+  h->fl_out.release(); h->fl_flag.release(); h->fl_head.release();
   for (MeasSet &s : h->ms) s.release();
   h->fs.release();
   h->lm_gL.release();
@@ -546,6 +547,7 @@ int gpslam_hip_clear_factors(gpslam_hip_handle *h) {
   h->clo.second.clear();
   h->clo.rob.clear();
   h->sg.clear();
+  h->bg.clear();
   for (MeasSet &s : h->ms) {
     s.rob.clear();
     s.idx.clear(); s.lm.clear(); s.meas.clear(); s.sig.clear(); s.dt.clear(); s.tau.clear(); s.aux.clear(); s.aidx.clear(); s.sqi.clear();

@@ -92,6 +92,21 @@ struct StateGauss {
   void release() { for (DevBuf *b : {&d_idx, &d_lin, &d_A, &d_c, &d_row0}) b->release(); }
 };
 
+// joint Gaussian factors on one state AND every landmark of the handle (gpslam_hip_add_border_gaussians; fixedlag.hip): n = b + nl,
+// r = A [Local(pose_lin, pose_i) ; vel_i - vel_lin ; l - lm_lin] - c.  They have no rows in the tables (a row names one landmark):
+// their blocks go into record idx behind the assembly and into the landmark Schur complement behind its reduction.  The prior
+// gpslam_hip_marginalize_head leaves on a handle with landmarks (gpslam_hip_marginalize_head_onto_landmarks) is one of them
+struct BorderGauss {
+  int nl = 0;                  // landmark coordinates of the stored factors (the handle's L * landmark_dim when they were added)
+  std::vector<int32_t> idx;
+  std::vector<double> lin;     // per factor [pose_lin (pd) | vel_lin (d) | lm_lin (nl)]
+  std::vector<double> A, c;    // per factor n x n row-major, n
+  DevBuf d_idx, d_lin, d_A, d_c, d_r;   // d_r: count x n residuals of the last pass
+  int count() const { return (int)idx.size(); }
+  void clear() { idx.clear(); lin.clear(); A.clear(); c.clear(); nl = 0; }
+  void release() { for (DevBuf *b : {&d_idx, &d_lin, &d_A, &d_c, &d_r}) b->release(); }
+};
+
 // Which kernels serve a compiled graph, and in which form.  make_plan() (api_impl.inc) fills one per compile(), once the row layout
 // is known, and nothing else writes it; what a single launch then does is launch_form(handle, LaunchMode) below.
 enum class Level0 { Column, Rows, Fused };     // level-0 elimination: k_chunk_forward, k_chunk_forward_rows, or k_fused_level0 where the mode asks for it
@@ -161,8 +176,13 @@ struct gpslam_hip_handle {
   Closures clo;
   MeasSet ms[kNumMeasKinds];
   StateGauss sg;
+  BorderGauss bg;
+  bool fl_onto_lm = false;    // gpslam_hip_marginalize_head_onto_landmarks
+  std::vector<double> hpb;    // gpslam_hip_get_head_prior_border: [lm_lin (nl) | Lambda (n x n) | gamma (n)] of the last joint marginalize_head, or empty
+  int hpb_nl = 0;             // ... and its nl
+  DevBuf fl_head;             // marginalize_head onto landmarks: [H_LL^head (nl x nl) | g_L^head (nl)]
   std::vector<double> hp;     // gpslam_hip_get_head_prior: [pose_lin | vel_lin | Lambda | gamma] of the last marginalize_head, or empty
-  DevBuf fl_out, fl_flag;     // marginalize_head: [D_k^left | g_k^left | Lambda | g'_k | pose_k | vel_k] and the recursion's flag
+  DevBuf fl_out, fl_flag;     // marginalize_head: [D_k^left | g_k^left | B_k^left | Lambda | g'_k | pose_k | vel_k | landmarks] and the recursion's flag
   // row table
   int M = 0;
   DevBuf rowLR, rowE, rowM, rowLm, rowptr;
@@ -277,6 +297,16 @@ inline int clo_ldw(const gpslam_hip_handle *h) { return 1 + h->nl + h->clo.nc; }
 // partial sums, nblocks(count, 128) of them, on stream st.
 int state_gauss_upload(gpslam_hip_handle *h, const std::vector<int> &row0);
 void state_gauss_eval(gpslam_hip_handle *h, int pass, double *partial, hipStream_t st);
+
+// Border Gaussians (fixedlag.hip; fp64 only, dense landmark border).  border_gauss_upload: compile()'s share.  border_gauss_eval: the
+// residuals (pass 0 only: kept on the device as the linearisation's, an error-only pass at a trial point leaves them alone) and the
+// error, one partial sum, on stream st.  border_gauss_inject: behind the assembly, A_x^T A_x,
+// A_x^T (c - A xi) and A_x^T A_L into record idx (the gradient copy too if save_g).  border_gauss_schur: behind k_lm_reduce, the
+// factor's share of [S | gL] -- k_lm_t forms B^T Z from the rows, and this factor has none.
+int border_gauss_upload(gpslam_hip_handle *h);
+void border_gauss_eval(gpslam_hip_handle *h, int pass, double *partial, hipStream_t st);
+void border_gauss_inject(gpslam_hip_handle *h, bool save_g);
+void border_gauss_schur(gpslam_hip_handle *h);
 
 #define HIPCHK(call)                                                                          \
   do {                                                                                        \

@@ -272,6 +272,10 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
     state_gauss_eval(h, pass, reinterpret_cast<double *>(part + off), side);   // (RowT == double here)
     off += nblocks(h->sg.count(), 128);
   }
+  if (kIsF64 && h->bg.count() > 0) {   // joint Gaussians on one state and the landmarks (fixedlag.hip): residuals and their error
+    border_gauss_eval(h, pass, reinterpret_cast<double *>(part + off), side);
+    off += 1;
+  }
   // (landmark priors have no Jacobian rows: on an fp32 handle their error belongs to the fp64 error pass alone)
   if (!kIsF64) {
   } else if (h->lpri.count() > 0 && h->fs.active) {   // tens of thousands of landmark priors: grid-stride, one partial per block
@@ -329,6 +333,7 @@ int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g, int 
     k_assemble_ghost<Real, BB, 4, RowT><<<dim3(nblocks(waves, 4)), dim3(256), 0, h->stream>>>(a);   // 1 / 8 / 16 waves per block measured slower
   });
   if (h->clo.n > 0) closures_inject(h, save_g, pass);   // the closures' columns of U^T into the records of their states
+  if (kIsF64 && h->bg.count() > 0) border_gauss_inject(h, save_g);   // the border Gaussians' blocks into the records of their states
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -532,6 +537,7 @@ int launch_landmarks_reduce(gpslam_hip_handle *h, double lambda) {
   if (h->nlmrows > 0) k_lm_t<Real, RowT><<<dim3(nblocks(h->nlmrows * h->R, 128)), dim3(128), 0, h->stream>>>(a);
   if (h->nlmchunks > 0) k_lm_reduce_part<Real, RowT><<<dim3(h->nlmchunks), dim3(256), 0, h->stream>>>(a);
   k_lm_reduce<Real, RowT><<<dim3(h->nl * h->R), dim3(64), 0, h->stream>>>(a);
+  if (kIsF64 && h->bg.count() > 0) border_gauss_schur(h);   // the border Gaussians have no rows: their share of [S | gL]
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1118,6 +1124,9 @@ int check_stored_indices(gpslam_hip_handle *h) {
     if (bad(s.idx, s.two ? ml : N - 1) || (s.haslm && bad(s.lm, h->L - 1)))
       return fail(h, GPSLAM_E_INVALID, "a stored measurement factor refers to a state / landmark that no longer exists");
   if (bad(h->sg.idx, N - 1)) return fail(h, GPSLAM_E_INVALID, "a stored state Gaussian refers to a state that no longer exists (set_states shrank the problem)");
+  if (bad(h->bg.idx, N - 1)) return fail(h, GPSLAM_E_INVALID, "a stored border Gaussian refers to a state that no longer exists (set_states shrank the problem)");
+  if (h->bg.count() > 0 && h->bg.nl != h->L * h->ld)
+    return fail(h, GPSLAM_E_INVALID, "a stored border Gaussian spans another number of landmarks than the handle has (set_landmarks changed it)");
   return 0;
 }
 
@@ -1181,6 +1190,14 @@ int choose_landmark_path(gpslam_hip_handle *h, bool &segmented) {
     if (h->fs.split) return fail(h, GPSLAM_E_UNSUPPORTED, "state Gaussians (add_state_gaussians) on a piece of a split chain");
     if (segmented) return fail(h, GPSLAM_E_UNSUPPORTED, "state Gaussians (add_state_gaussians) together with the segmented landmark elimination");
     if (h->mf == ROT3_BIAS) return fail(h, GPSLAM_E_UNSUPPORTED, "state Gaussians (add_state_gaussians) on a GPSLAM_ROT3_BIAS handle (the pad coordinates of its velocity slot)");
+  }
+  if (h->bg.count() > 0) {   // joint Gaussians on one state and the landmarks (fixedlag.hip): as the state Gaussians, on the dense border
+    if (!kIsF64) return fail(h, GPSLAM_E_UNSUPPORTED, "border Gaussians (add_border_gaussians) on an fp32 handle");
+    if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "border Gaussians (add_border_gaussians) on a sharded handle");
+    if (h->fs.split) return fail(h, GPSLAM_E_UNSUPPORTED, "border Gaussians (add_border_gaussians) on a piece of a split chain");
+    if (segmented) return fail(h, GPSLAM_E_UNSUPPORTED, "border Gaussians (add_border_gaussians) together with the segmented landmark elimination");
+    if (h->mf == ROT3_BIAS) return fail(h, GPSLAM_E_UNSUPPORTED, "border Gaussians (add_border_gaussians) on a GPSLAM_ROT3_BIAS handle (the pad coordinates of its velocity slot)");
+    if (passes) return fail(h, GPSLAM_E_UNSUPPORTED, "border Gaussians (add_border_gaussians) together with loop closures in column passes (set_closure_passes): the final pass's right-hand sides are the closures' alone");
   }
   if (segmented) {
     if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "the segmented landmark elimination splits across GPUs through gpslam_hip_fs_set_split (pieces joined at shared cut states), not through nranks > 1");
@@ -1281,9 +1298,10 @@ int upload_factors(gpslam_hip_handle *h, const RowLayout &lay, int &npart) {
   if ((rc = upload_set(h, h->lpri, std::vector<int>()))) return rc;
   if (h->clo.n > 0 && (rc = closures_upload(h))) return rc;
   if (h->sg.count() > 0 && (rc = state_gauss_upload(h, lay.r_sg))) return rc;
+  if (kIsF64 && h->bg.count() > 0 && (rc = border_gauss_upload(h))) return rc;
   // (one k_gp launch per distinct Qc, each rounding its factor count up to whole blocks: at most one extra slot per group)
   npart = nblocks((int)h->gp_left.size(), 128) + gp_ngroups(h) + nblocks(h->pri.count(), 128) + nblocks(h->vpri.count(), 128) +
-          nblocks(h->btw.count(), 128) + 1 + 256 + 1 + nblocks(h->sg.count(), 128);   // (+ 1: the loop closures' error)
+          nblocks(h->btw.count(), 128) + 1 + 256 + 1 + nblocks(h->sg.count(), 128) + 1;   // (+ 1: the loop closures' error; + 1: the border Gaussians')
   for (int fk = 0; fk < kNumMeasKinds; fk++) {
     MeasSet &s = h->ms[fk];
     if ((rc = upload(h, s.d_idx, s.idx))) return rc;

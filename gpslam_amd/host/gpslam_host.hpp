@@ -327,12 +327,13 @@ class Values {
 // ---------------------------------------------------------------- factors
 namespace detail {
 enum FType { F_GP, F_POSE_PRIOR, F_VEL_PRIOR, F_LM_PRIOR, F_BETWEEN, F_INTERP_RANGE, F_RANGE, F_INTERP_ATT, F_INTERP_GPS, F_ODOM2D, F_BEARING_RANGE, F_INTERP_PROJ,
-             F_BIAS_PRIOR, F_BIAS_BETWEEN, F_AHRS, F_ATTITUDE, F_STATE_GAUSS };
+             F_BIAS_PRIOR, F_BIAS_BETWEEN, F_AHRS, F_ATTITUDE, F_STATE_GAUSS, F_BORDER_GAUSS };
 struct Desc {   // what a factor hands to the graph compiler
   FType type;
   int manifold = -1;                 // GPSLAM_* the factor requires, -1 = any
   Key k[5] = {0, 0, 0, 0, 0};        // pose1, vel1, pose2, vel2, landmark (as applicable)
   Key kw[2] = {0, 0};                // omega1, omega2 of the *Pose3VW factors
+  std::vector<Key> lmk;              // F_BORDER_GAUSS: the landmark keys, in the order of the factor's columns
   bool vw = false;                   // world-frame (v, w) velocity family
   std::vector<double> meas, sig, sensor, aux;
   std::vector<double> cov;           // measurement factors with a noiseModel::Gaussian (full covariance): rows x rows, else empty
@@ -353,6 +354,7 @@ inline bool desc_equals(const Desc &a, const Desc &b, double tol, bool gp) {
   if (a.type != b.type || a.manifold != b.manifold || a.vw != b.vw) return false;
   for (int i = 0; i < 5; i++) if (a.k[i] != b.k[i]) return false;
   for (int i = 0; i < 2; i++) if (a.kw[i] != b.kw[i]) return false;
+  if (a.lmk != b.lmk) return false;
   if (!close(a.meas, b.meas, tol) || !close(a.sig, b.sig, tol) || !close(a.cov, b.cov, tol)) return false;
   if (!close(a.sensor, b.sensor, tol) || !close(a.aux, b.aux, tol)) return false;
   if (a.robust != b.robust || !(std::fabs(a.robust_k - b.robust_k) < tol || a.robust_k == b.robust_k)) return false;
@@ -751,6 +753,18 @@ struct Session {
           int32_t st = state_of(f.k[0]);
           check(gpslam_hip_add_state_gaussians(h, 1, &st, f.meas.data(), f.meas.data() + pd, f.aux.data(), f.sig.data()), h, "add_state_gaussians");
         } break;
+        case F_BORDER_GAUSS: {   // gtsam::LinearContainerFactor over (x_s, v_s, l_0 .. l_{L-1}): meas = [pose_lin | vel_lin | lm_lin], aux = A, sig = c
+          if (vw || bias) throw std::invalid_argument("LinearContainerFactor: not on Pose3VW or AHRS graphs");
+          if (symbolIndex(f.k[0]) != symbolIndex(f.k[1])) throw std::invalid_argument("LinearContainerFactor: pose and velocity keys of a state must share their index");
+          if ((int)f.lmk.size() != L) throw std::invalid_argument("LinearContainerFactor: a factor over a state and landmarks names every landmark of the Values");
+          for (int i = 0; i < L; i++)
+            if (lm_of(f.lmk[i]) != i) throw std::invalid_argument("LinearContainerFactor: the landmark keys must stand in the order of their indices");
+          const int n = 2 * d + L * ld;
+          if ((int)f.meas.size() != pd + d + L * ld || (int)f.aux.size() != n * n || (int)f.sig.size() != n)
+            throw std::invalid_argument("LinearContainerFactor: A must be n x n and b n, n = 2d + the landmarks' coordinates");
+          int32_t st = state_of(f.k[0]);
+          check(gpslam_hip_add_border_gaussians(h, 1, &st, f.meas.data(), f.meas.data() + pd, f.meas.data() + pd + d, f.aux.data(), f.sig.data()), h, "add_border_gaussians");
+        } break;
       }
     }
   }
@@ -901,7 +915,25 @@ class LinearContainerFactor : public NonlinearFactor {
     d_.meas.insert(d_.meas.end(), lv.begin(), lv.end());
     d_.aux = A.a; d_.sig = b;
   }
-  size_t size() const override { return 2; }
+  /// ... over (x, v, l_0 .. l_{L-1}): xi = [Local(lin_x, x) ; v - lin_v ; l - lin_l], A n x n, b n, n = 2d + the landmarks' coordinates.  The
+  /// landmark keys are every landmark of the graph, in the order of their indices; maps to gpslam_hip_add_border_gaussians -- what
+  /// BatchFixedLagSmoother leaves behind on a graph with landmarks.
+  template <typename POSE, typename VEL, typename POINT>
+  LinearContainerFactor(Key poseKey, Key velKey, const std::vector<Key> &landmarkKeys, const Matrix &A, const Vector &b, const POSE &lin_pose,
+                        const VEL &lin_vel, const std::vector<POINT> &lin_landmarks) {
+    if (A.rows != A.cols || (size_t)A.rows != b.size()) throw std::invalid_argument("LinearContainerFactor: A must be square and b of its size");
+    if (landmarkKeys.size() != lin_landmarks.size()) throw std::invalid_argument("LinearContainerFactor: one linearisation point per landmark key");
+    d_.type = detail::F_BORDER_GAUSS; d_.k[0] = poseKey; d_.k[1] = velKey; d_.lmk = landmarkKeys;
+    d_.meas = detail::VT<POSE>::pack(lin_pose);
+    const std::vector<double> lv = detail::VT<VEL>::pack(lin_vel);
+    d_.meas.insert(d_.meas.end(), lv.begin(), lv.end());
+    for (const POINT &pt : lin_landmarks) {
+      const std::vector<double> lp = detail::VT<POINT>::pack(pt);
+      d_.meas.insert(d_.meas.end(), lp.begin(), lp.end());
+    }
+    d_.aux = A.a; d_.sig = b;
+  }
+  size_t size() const override { return 2 + d_.lmk.size(); }
   NonlinearFactor::shared_ptr clone() const override { return std::make_shared<LinearContainerFactor>(*this); }
   detail::Desc describe() const override { return d_; }
   bool equals(const NonlinearFactor &expected, double tol = 1e-9) const override {
@@ -917,7 +949,8 @@ class LinearContainerFactor : public NonlinearFactor {
 
 /// gtsam::BatchFixedLagSmoother (gtsam_unstable/nonlinear/BatchFixedLagSmoother.h) on a chain: update() adds the new factors and
 /// values, marginalises the leading states whose time stamp is older than (latest - lag) into a Gaussian on the oldest kept state
-/// (gpslam_hip_marginalize_head: elimination at the current linearisation, as GTSAM's), re-compiles and optimises with the
+/// (gpslam_hip_marginalize_head: elimination at the current linearisation, as GTSAM's) -- on a graph with landmarks into a Gaussian on
+/// that state and the landmarks where marginalizeOntoLandmarks() asked for it (gpslam_hip_marginalize_head_onto_landmarks) --, re-compiles and optimises with the
 /// Levenberg-Marquardt parameters.  New states continue the chain: their pose keys carry larger indices than every key seen so far.
 class BatchFixedLagSmoother {
  public:
@@ -926,6 +959,13 @@ class BatchFixedLagSmoother {
   explicit BatchFixedLagSmoother(double smootherLag = 0.0, const LevenbergMarquardtParams &params = LevenbergMarquardtParams())
       : lag_(smootherLag), params_(params) {}
   double smootherLag() const { return lag_; }
+  /// On a graph with landmarks (range, bearing-range, projection factors) the head's prior must span the oldest kept state AND the
+  /// landmarks, as GTSAM's does: gpslam_hip_marginalize_head_onto_landmarks.  Off by default, as in the C ABI: a smoother that was not
+  /// asked keeps refusing a head factor that names a landmark, with the ABI's message.  Any time; a graph without landmarks is unaffected.
+  void marginalizeOntoLandmarks(bool on = true) {
+    onto_landmarks_ = on;
+    if (s_) detail::check(gpslam_hip_marginalize_head_onto_landmarks(s_->h, on ? 1 : 0), s_->h, "marginalize_head_onto_landmarks");
+  }
   const KeyTimestampMap &timestamps() const { return stamps_; }
   gpslam_hip_handle *handle() const { return s_ ? s_->h : nullptr; }
 
@@ -941,6 +981,7 @@ class BatchFixedLagSmoother {
     if (!s_) {
       s_.reset(new detail::Session());
       s_->build(newFactors, newTheta);
+      if (onto_landmarks_) detail::check(gpslam_hip_marginalize_head_onto_landmarks(s_->h, 1), s_->h, "marginalize_head_onto_landmarks");
     } else {
       extend(newFactors, newTheta, pose_keys);
     }
@@ -1023,6 +1064,7 @@ class BatchFixedLagSmoother {
   }
   double lag_;
   LevenbergMarquardtParams params_;
+  bool onto_landmarks_ = false;
   std::unique_ptr<detail::Session> s_;
   std::vector<Key> keys_;          // pose keys of the states in the window, in chain order
   KeyTimestampMap stamps_;

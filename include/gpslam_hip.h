@@ -82,7 +82,8 @@ enum {
  * gpslam_hip_marginals, gpslam_hip_get_marginals, gpslam_hip_interpolate_covariances; 2.4 gpslam_hip_launch_census (and, added since without a bump,
  * gpslam_hip_set_closure_passes / gpslam_hip_closure_info / gpslam_hip_marginals_keep_closure_columns / gpslam_hip_marginals_on_segments /
  * gpslam_hip_get_landmark_marginals / gpslam_hip_get_state_landmark_marginals / gpslam_hip_get_landmark_pair_marginals /
- * gpslam_hip_add_state_gaussians / gpslam_hip_get_state_gaussians / gpslam_hip_marginalize_head / gpslam_hip_get_head_prior / gpslam_hip_append_states).  A MAJOR bump changes a struct or a
+ * gpslam_hip_add_state_gaussians / gpslam_hip_get_state_gaussians / gpslam_hip_marginalize_head / gpslam_hip_get_head_prior / gpslam_hip_append_states /
+ * gpslam_hip_add_border_gaussians / gpslam_hip_get_border_gaussians / gpslam_hip_marginalize_head_onto_landmarks / gpslam_hip_get_head_prior_border).  A MAJOR bump changes a struct or a
  * signature, a MINOR bump only adds. */
 #define GPSLAM_HIP_ABI_MAJOR 2
 #define GPSLAM_HIP_ABI_MINOR 4
@@ -377,13 +378,52 @@ int gpslam_hip_get_state_gaussians(gpslam_hip_handle *h, int32_t *idx, double *p
  * Refusals, all before anything changes (the handle then iterates exactly as if the call had not been made): k out of range
  * GPSLAM_E_INVALID; not compiled GPSLAM_E_NOT_COMPILED; GPSLAM_E_UNSUPPORTED for a head factor that names a landmark (the message
  * names kind and factor), for a loop closure with first < k or second < k, and on fp32 / sharded / split / segmented /
- * GPSLAM_ROT3_BIAS handles.  GPSLAM_E_NOT_SPD when a pivot block of the head is not positive definite. */
+ * GPSLAM_ROT3_BIAS handles.  GPSLAM_E_NOT_SPD when a pivot block of the head is not positive definite.
+ * The refusal of head factors that name a landmark is the default; gpslam_hip_marginalize_head_onto_landmarks (below) lifts it: the
+ * prior then spans the oldest kept state and the landmarks. */
 int gpslam_hip_marginalize_head(gpslam_hip_handle *h, int32_t k);
 /* linearisation point, Lambda (b x b) and gamma (b) of the last successful marginalize_head, as the device computed them (any
  * pointer may be NULL); GPSLAM_E_INVALID before the first one */
 int gpslam_hip_get_head_prior(gpslam_hip_handle *h, double *pose_lin, double *vel_lin, double *Lambda, double *gamma);
 /* n more states behind the last one (layouts of set_states), placed on the device; the factors stay; the handle needs compile() */
 int gpslam_hip_append_states(gpslam_hip_handle *h, int32_t n, const double *pose, const double *vel);
+
+/* ---- fixed-lag smoothing with landmarks: the head's prior over the oldest kept state AND the landmarks ----
+ * What gtsam::BatchFixedLagSmoother leaves on a range / bearing-range / projection graph: a gtsam::LinearContainerFactor over the
+ * keys (x_k, v_k, l_0 .. l_{L-1}).  fp64 only, one unsharded handle on the DENSE landmark border (nl = L * landmark_dim <= 27).
+ *
+ * A joint Gaussian factor on ONE state and ALL landmarks of the handle.  n = b + nl; per factor a linearisation point (pose_lin,
+ * vel_lin as for the state Gaussians, lm_lin nl doubles: the landmarks in index order), A (n x n row-major; any finite matrix, zero
+ * rows allowed) and c (n); lm_lin is count x nl.  With xi = [Local(pose_lin, pose_i) ; vel_i - vel_lin ; l - lm_lin] (the landmarks'
+ * plain difference) the whitened residual is r = A xi - c, the cost |r|^2 / 2, the Jacobian the CONSTANT A: exact at xi = 0, first
+ * order away from it, as documented for the state Gaussians.  A value that is not finite in any array: GPSLAM_E_INVALID; a handle
+ * without landmarks: GPSLAM_E_INVALID.  compile() answers GPSLAM_E_INVALID when a stored factor's nl no longer matches the handle's
+ * (set_landmarks changed L) and GPSLAM_E_UNSUPPORTED, each with a message, on fp32, sharded, split, segmented and GPSLAM_ROT3_BIAS
+ * handles, and together with loop closures in column passes (gpslam_hip_set_closure_passes with more than one pass).  Gauss-Newton, Levenberg-Marquardt, optimize, error, normal_equations (the factor's share of D_i, g_i, B_i) and marginals
+ * include it; clear_factors drops it.  The factor has NO rows in gpslam_hip_get_rows: a row of the tables names one landmark, this
+ * factor names all of them -- its blocks A_x^T A_x, A_x^T (c - A xi), A_x^T A_L go into record i behind the assembly, and
+ * A_L^T A_L, A_L^T (c - A xi) and the cross term with the chain's solution into the landmark system behind its reduction. */
+int gpslam_hip_add_border_gaussians(gpslam_hip_handle *h, int32_t count, const int32_t *idx, const double *pose_lin, const double *vel_lin,
+                                    const double *lm_lin, const double *A, const double *c);
+/* the stored factors in the order they stand (any pointer may be NULL); returns the count.  The arrays hold n = b + nl of the STORED
+ * factors: when set_landmarks has changed the handle's nl since, a call with lm_lin, A or c answers GPSLAM_E_INVALID and writes nothing */
+int gpslam_hip_get_border_gaussians(gpslam_hip_handle *h, int32_t *idx, double *pose_lin, double *vel_lin, double *lm_lin, double *A, double *c);
+/* enable != 0: gpslam_hip_marginalize_head accepts head factors that name landmarks, and border Gaussians with idx < k (the previous
+ * head prior among them).  On a handle with landmarks it then leaves a BORDER Gaussian on the new state 0 -- linearisation point the
+ * current (pose_k, vel_k, landmarks), A^T A = Lambda, A^T c = -gamma with Lambda, gamma over (delta_k, delta_l) from the recursion
+ * of k_head_schur_border; pivots at or below n * eps * max|diag| of the head's own share of [D_k^left ; H_LL^head] become zero rows
+ * of A (Lambda is rank-deficient as a rule: landmarks the head never saw have zero rows, a range-only head has a gauge).  On a handle
+ * without landmarks it leaves the state Gaussian, exactly as with the option off.  The head is every stored factor that touches a
+ * state < k; landmark priors touch no state and stay in the graph, landmark indices stay, and a landmark no tail factor sees stays
+ * too, determined by the prior.  Every other refusal of gpslam_hip_marginalize_head stays, made before anything changes.  Default 0:
+ * the refusal of such head factors, message unchanged (a border Gaussian with idx < k is then refused likewise).  Two more cases:
+ * a handle whose closures go in column passes answers GPSLAM_E_UNSUPPORTED (compile() would refuse the factor it leaves); a handle of
+ * block size 4 (GPSLAM_LINEAR2: no factor of that manifold names a landmark) keeps leaving the state Gaussian, which is the whole marginal. */
+int gpslam_hip_marginalize_head_onto_landmarks(gpslam_hip_handle *h, int32_t enable);
+/* lm_lin (nl), Lambda (n x n) and gamma (n), n = b + nl, of the last marginalize_head if it was one onto the landmarks, as the device
+ * computed them (any pointer may be NULL); GPSLAM_E_INVALID otherwise, and when set_landmarks has changed the handle's nl since.  gpslam_hip_get_head_prior then returns the state block
+ * Lambda_xx and gamma_x: its sizes never change. */
+int gpslam_hip_get_head_prior_border(gpslam_hip_handle *h, double *lm_lin, double *Lambda, double *gamma);
 
 /* drop every factor added so far (states, landmarks and Qc stay); the handle needs a new compile() */
 int gpslam_hip_clear_factors(gpslam_hip_handle *h);
@@ -436,7 +476,8 @@ int gpslam_hip_normal_equations(gpslam_hip_handle *h, double *D, double *O, doub
  * Row order: first the rows with velocity columns, grouped by left state (inside a state: GP priors, velocity priors, state Gaussians,
  * then interpolated range, range, attitude, GPS, odometry2d, bearing-range, projection, each in the order they were
  * added); then the velocity-free rows (pose priors, between factors; the device keeps them in a half-width table),
- * again grouped by left state, expanded to full width.  Any output pointer may be NULL; n_rows receives M. */
+ * again grouped by left state, expanded to full width.  Any output pointer may be NULL; n_rows receives M.  Border Gaussians
+ * (gpslam_hip_add_border_gaussians) have no rows here: a row names one landmark, they name all of them. */
 int gpslam_hip_get_rows(gpslam_hip_handle *h, int32_t *n_rows, double *rowLR, double *rowE, double *rowM,
                         int32_t *rowLm);
 /* solve the block-tridiagonal SPD system D/O/g (host arrays as above, N x b) with the device solver; x: N x b */

@@ -9,6 +9,9 @@ SE(3) GP chain with odometry (synthetic.pose3_chain), windows of 1e4 and 1e5 sta
   rocprofv3 --kernel-trace run of a child process (--schur-child) that makes nothing but those calls;
   two Gauss-Newton iterations of a fresh window as it is, and of the same window with a state Gaussian whose A is zero on state 0 --
   the same solution, but compile() turns Plan::fold_retract and Plan::lines off: what carrying a head prior costs an iteration.
+With --landmarks: a Plaza-like SE(2) window (synthetic.pose2_range_chain: odometry, interpolated ranges at Plaza's rate, 4 beacons seen
+from everywhere) slid by 100 with the head marginalised onto the landmarks (gpslam_hip_marginalize_head_onto_landmarks): the cost of
+marginalize_head, of k_head_schur_border alone (the kernel trace of a child process) and of two iterations with the border Gaussian.
 Prints one JSON line per window; profiles/fixed_lag.txt keeps a run."""
 import argparse
 import csv
@@ -141,15 +144,109 @@ def bench(W, step, slides):
     return out
 
 
+# ---------------------------------------------------------------- the landmark case
+RANGE_KEYS = ("range_lm", "range_z", "range_sigma", "range_dt", "range_tau")
+
+
+def lm_window_of(p, lo, hi, new_from=None):
+    out = window_of(p, lo, hi, new_from)
+    idx = p["range_left"]
+    m = (idx >= lo) & (idx + 1 < hi)
+    if new_from is not None:
+        m &= idx + 1 >= new_from
+    out["range_left"] = (idx[m] - lo).astype(np.int32)
+    for o in RANGE_KEYS:
+        out[o] = p[o][m]
+    for key in ("landmarks", "lprior_idx", "lprior", "lprior_sig"):
+        out[key] = p[key]
+    return out
+
+
+def lm_solver(w):
+    dev = S.apply(w, gp.ChainSolver(w["kind"], landmark_dim=2))
+    dev.marginalize_head_onto_landmarks()
+    return dev
+
+
+def border_calls(W, step, timed=None):
+    """marginalize_head(step) onto the landmarks on fresh windows of W states, SCHUR_REPS times"""
+    p = S.pose2_range_chain(W, L=4)
+    for _ in range(SCHUR_REPS):
+        d2 = lm_solver(lm_window_of(p, 0, W))
+        d2.iterate_gn()
+        t = ms(lambda: d2.marginalize_head(step))
+        if timed is not None:
+            timed.append(t)
+        d2.close()
+
+
+def border_kernel_us(W, step):
+    tmp = tempfile.mkdtemp(prefix="fixed_lag_trace_")
+    try:
+        subprocess.run(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "t", "--", sys.executable, os.path.abspath(__file__),
+                        "--border-child", str(W), "--step", str(step)], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+        rows = []
+        for path in glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True):
+            rows += [r for r in csv.DictReader(open(path)) if "k_head_schur_border" in r["Kernel_Name"]]
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    if len(rows) != SCHUR_REPS:
+        raise RuntimeError("the kernel trace holds %d launches of k_head_schur_border, expected %d" % (len(rows), SCHUR_REPS))
+    return round(min((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows), 2)
+
+
+def bench_landmarks(W, step, slides):
+    p = S.pose2_range_chain(W + step * (slides + 1), L=4)
+    dev = lm_solver(lm_window_of(p, 0, W))
+    for _ in range(2):
+        dev.iterate_gn()
+    rows = {k: [] for k in ("marginalize", "append_add", "compile", "two_gn")}
+    lo, hi = 0, W
+    for _ in range(slides):
+        rows["marginalize"].append(ms(lambda: dev.marginalize_head(step)))
+        new = lm_window_of(p, lo + step, hi + step, new_from=hi)
+
+        def grow():
+            dev.append_states(p["pose"][hi:hi + step], p["vel"][hi:hi + step])
+            add_factors(dev, new)
+            dev.add_interp_range(new["range_left"], new["range_lm"], new["range_z"], new["range_sigma"], new["range_dt"], new["range_tau"])
+        rows["append_add"].append(ms(grow))
+        rows["compile"].append(ms(dev.compile))
+        rows["two_gn"].append(ms(lambda: (dev.iterate_gn(), dev.iterate_gn())))
+        lo, hi = lo + step, hi + step
+    out = dict(case="landmarks", window=W, step=step, slides=slides, beacons=4, **{k: round(statistics.median(v), 3) for k, v in rows.items()})
+    dev.close()
+    timed = []
+    border_calls(W, step, timed)
+    out["marginalize_head_fresh"] = round(min(timed), 3)
+    d3 = lm_solver(lm_window_of(p, 0, W))
+    d3.iterate_gn()
+    out["two_gn_plain"] = round(statistics.median(ms(lambda: (d3.iterate_gn(), d3.iterate_gn())) for _ in range(7)), 3)
+    d3.close()
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, nargs="+", default=[10000, 100000])
     ap.add_argument("--step", type=int, default=100)
     ap.add_argument("--slides", type=int, default=5)
     ap.add_argument("--schur-child", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--landmarks", action="store_true", help="the Plaza-like SE(2) window with 4 beacons instead (default window 4000)")
+    ap.add_argument("--border-child", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.schur_child:
         schur_calls(a.schur_child)
+        sys.exit(0)
+    if a.border_child:
+        border_calls(a.border_child, a.step)
+        sys.exit(0)
+    if a.landmarks:
+        for W in ([4000] if a.windows == [10000, 100000] else a.windows):
+            kernel = border_kernel_us(W, a.step)          # (a child process of its own, before this one opens the device)
+            res = bench_landmarks(W, a.step, a.slides)
+            res["k_head_schur_border_us"] = kernel
+            print(json.dumps(res), flush=True)
         sys.exit(0)
     for W in a.windows:
         kernel = schur_kernel_us(W)          # (a child process of its own, before this one opens the device)

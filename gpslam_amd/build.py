@@ -19,8 +19,8 @@ LIB = os.path.join(LIBDIR, "libgpslam_hip.so")
 # were one 3.5-minute translation unit), the upper solver levels, the marginals (gtsam::Marginals: selected inversion of the chain)
 # and their closure term on handles in column passes (marginals_clo.hip), the marginals of the segmented landmark path
 # (marginals_fs.hip: fp64 only), the loop closures' launches (closures.hip: fp64 only), and fixed-lag smoothing (fixedlag.hip: state
-# Gaussians, the head's marginalisation; fp64 only)
-SOURCES = ["api.hip", "api_impl64.hip", "api_impl32.hip", "upper.hip", "marginals.hip", "marginals_clo.hip", "marginals_fs.hip", "closures.hip", "fixedlag.hip"]
+# Gaussians, the head's marginalisation; fp64 only), and the marginals of any two states with the closure gate (marginals_pairs.hip)
+SOURCES = ["api.hip", "api_impl64.hip", "api_impl32.hip", "upper.hip", "marginals.hip", "marginals_clo.hip", "marginals_fs.hip", "closures.hip", "fixedlag.hip", "marginals_pairs.hip"]
 HEADERS = ["kernels.hpp", "closures.hpp", "factors.hpp", "lie.hpp", "devbuf.hpp", "fatsep.hpp", "dpp.hpp", "cr_step.hpp", "cr_quad.hpp", "upper.hpp", "api_common.hpp", "robust.hpp",
            "api_decl.inc", os.path.join("..", "..", "include", "gpslam_hip.h")]
 # what each translation unit includes (an edit to upper.hip does not recompile the others)
@@ -28,7 +28,7 @@ IMPL = HEADERS + ["api_impl.inc", "api_iterate.inc"]
 CLO = HEADERS + ["marginals_clo.hpp"]
 MGFS = HEADERS + ["marginals_fs.hpp"]
 DEPS = {"api.hip": HEADERS, "api_impl64.hip": IMPL, "api_impl32.hip": IMPL,
-        "upper.hip": ["dpp.hpp", "cr_step.hpp", "cr_quad.hpp", "upper.hpp"], "marginals.hip": CLO + ["marginals_fs.hpp"], "marginals_clo.hip": CLO, "marginals_fs.hip": MGFS, "closures.hip": CLO, "fixedlag.hip": HEADERS}
+        "upper.hip": ["dpp.hpp", "cr_step.hpp", "cr_quad.hpp", "upper.hpp"], "marginals.hip": CLO + ["marginals_fs.hpp"], "marginals_clo.hip": CLO, "marginals_fs.hip": MGFS, "closures.hip": CLO, "fixedlag.hip": HEADERS, "marginals_pairs.hip": CLO}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"]
 
 

@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "gpslam_hip_append_states",
     "gpslam_hip_add_border_gaussians", "gpslam_hip_get_border_gaussians", "gpslam_hip_marginalize_head_onto_landmarks",
     "gpslam_hip_get_head_prior_border",
+    "gpslam_hip_marginals_keep_pair_terms", "gpslam_hip_get_state_pair_marginals", "gpslam_hip_gate_between_pairs",
 ]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
@@ -670,6 +671,37 @@ class ChainSolver:
         out = np.zeros((len(a), self.ld, self.ld))
         self._chk(self.lib.gpslam_hip_get_landmark_pair_marginals(self._h, len(a), _p(a), _p(b), _p(out)), "get_landmark_pair_marginals")
         return out
+
+    def marginals_keep_pair_terms(self, enable=True):
+        """Let get_state_pair_marginals / gate_between_pairs run on a handle with landmarks or closures: marginals() then copies
+        their columns at every state, one more device buffer of N * b * (nl + closures * d) doubles (column passes: N * b * nl).
+        Any time after create, before marginals(); a handle without landmarks and closures needs no call.  enable=False frees it."""
+        return self._chk(self.lib.gpslam_hip_marginals_keep_pair_terms(self._h, 1 if enable else 0), "marginals_keep_pair_terms")
+
+    def get_state_pair_marginals(self, a, b):
+        """Sigma_{a, b} (count, b, b; rows: state a) for pairs of ANY two states after marginals().  a == b and adjacent pairs are
+        get_marginals' blocks to the bit; Sigma_{b,a} is the transpose of Sigma_{a,b} to the bit."""
+        a, b = _i32(a), _i32(b)
+        if len(a) != len(b):
+            raise ValueError("get_state_pair_marginals: a and b differ in length")
+        out = np.zeros((len(a), self.b, self.b))
+        self._chk(self.lib.gpslam_hip_get_state_pair_marginals(self._h, len(a), _p(a), _p(b), _p(out)), "get_state_pair_marginals")
+        return out
+
+    def gate_between_pairs(self, first, second, measured, sigmas):
+        """The chi-square gate of loop-closure candidates that are not in the graph (arguments as add_between_pairs), at the current
+        states and the held marginals.  Returns (chi2 (count,), err (count, d), innov_cov (count, d, d)): the unwhitened
+        BetweenFactor error e, P = diag(sigma^2) + [H1 H2] Sigma [H1 H2]^T over the two states' pose blocks, and e^T P^-1 e."""
+        first, second, measured, sigmas = _i32(first), _i32(second), _f64(measured), _f64(sigmas)
+        if len(first) != len(second):
+            raise ValueError("gate_between_pairs: first and second differ in length")
+        n = len(first)
+        if measured.size != n * self.pd or sigmas.size != n * self.d:
+            raise ValueError("gate_between_pairs: measured must be count x %d and sigmas count x %d" % (self.pd, self.d))
+        chi2, err, cov = np.zeros(n), np.zeros((n, self.d)), np.zeros((n, self.d, self.d))
+        self._chk(self.lib.gpslam_hip_gate_between_pairs(self._h, n, _p(first), _p(second), _p(measured), _p(sigmas), _p(chi2), _p(err), _p(cov)),
+                  "gate_between_pairs")
+        return chi2, err, cov
 
     def get_marginals(self, first=0, count=None, cross=False):
         """Blocks of the last marginals() call for states [first, first + count): S (count, b, b) = Sigma_{i,i} and S_next

@@ -243,6 +243,12 @@ struct gpslam_hip_handle {
   // K - 1 of them Sigma_{k,k+1}) and G = A_s^-1 H[I_s, B_s] at every interior state (mg_G: (N b + 64) rows of NCP doubles)
   bool mg_on_segments = false;
   DevBuf mg_fsD, mg_fsP, mg_G;
+  // gpslam_hip_marginals_keep_pair_terms: the marginals copy Y = [W | Z] -- columns 1 .. R - 1 of the level-0 solution, which later
+  // calls may rewrite -- into mg_Y (N x mg_Ym x b doubles; in column passes only the nl landmark columns W) for the pair getters
+  // (marginals_pairs.hip); mg_pairs_ok: the last gpslam_hip_marginals left what gpslam_hip_get_state_pair_marginals needs
+  bool mg_keep_pairs = false, mg_pairs_ok = false;
+  int mg_Ym = 0;
+  DevBuf mg_Y;
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch
@@ -258,6 +264,10 @@ int marginals_closure_term(gpslam_hip_handle *h);
 int marginals_fs(gpslam_hip_handle *h);
 void marginals_fs_release(gpslam_hip_handle *h);
 int marginals_fs_gather(gpslam_hip_handle *h, int mode, int32_t count, const int32_t *a, const int32_t *b, double *out);
+// behind gpslam_hip_marginals' last kernel: the copy of Y for the pair getters (marginals_pairs.hip; nothing without the opt-in)
+int marginals_pairs_keep(gpslam_hip_handle *h);
+// the refusals and the staleness rule of every marginals getter (marginals.hip)
+int marginals_getter_check(gpslam_hip_handle *h);
 
 // What the launches of one call do: each entry point builds the mode it means and hands it to the launch helpers.
 // LaunchMode{}: row tables (d = 3 records where the graph has them), level 0 unfused, every reduction at once, untimed.

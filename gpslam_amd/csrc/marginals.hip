@@ -13,7 +13,9 @@
 //       gpslam_hip_marginals_keep_closure_columns) Z is kept slice by slice and its term has kernels of its own (marginals_clo.hip);
 //   (d) batched posterior covariances of GP-interpolated poses (k_mg_interp behind k_interp_query's H1..H4);
 //   (e) a handle on the segmented landmark path (gpslam_hip_marginals_on_segments) takes none of (b), (c): marginals_fs.hip inverts
-//       through the nested dissection and leaves Sigma_{i,i}, Sigma_{i,i+1} where (d) and get_marginals read them.
+//       through the nested dissection and leaves Sigma_{i,i}, Sigma_{i,i+1} where (d) and get_marginals read them;
+//   (f) Sigma_{a,b} of any two states and the closure gate over it walk what (b), (c) leave (marginals_pairs.hip), from a copy of Y
+//       taken behind k_mg_finish when gpslam_hip_marginals_keep_pair_terms asked for it.
 // fp64 only; no atomics, every sum in a fixed order: two calls give bit-identical blocks.
 #include "api_common.hpp"
 #include "marginals_clo.hpp"
@@ -364,10 +366,16 @@ int mg_stale(gpslam_hip_handle *h) {
 
 }  // namespace
 
+int marginals_getter_check(gpslam_hip_handle *h) {
+  const int rc = mg_refuse(h);
+  return rc ? rc : mg_stale(h);
+}
+
 void marginals_release(gpslam_hip_handle *h) {
-  for (DevBuf *b : {&h->mg_fac, &h->mg_S, &h->mg_Sn, &h->mg_up, &h->mg_K, &h->mg_Slm, &h->mg_Sxl, &h->mg_Z, &h->mg_Minv}) b->release();
+  for (DevBuf *b : {&h->mg_fac, &h->mg_S, &h->mg_Sn, &h->mg_up, &h->mg_K, &h->mg_Slm, &h->mg_Sxl, &h->mg_Z, &h->mg_Minv, &h->mg_Y}) b->release();
   marginals_fs_release(h);
   h->marg_ok = false;
+  h->mg_pairs_ok = false;
   h->marg_N = 0;
 }
 
@@ -398,6 +406,7 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
   if ((rc = mg_refuse(h))) return rc;
   (void)hipSetDevice(h->cfg.device);
   h->marg_ok = false;
+  h->mg_pairs_ok = false;
   if (h->fs.active) return marginals_fs(h);
   const int N = h->N, B = h->b, BB = B * B, R = h->R, m = R - 1;
   // levels: n_0 = N, n_{l+1} = ceil(n_l / kMgChunk), down to one block; the levels above 0 live in one buffer
@@ -485,6 +494,7 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
     dispatch_b(B, [&](auto tag) { k_mg_finish<decltype(tag)::value><<<dim3(nblocks(N * B, 256)), dim3(256), 0, h->stream>>>(f); });
   }
   HIPCHK(hipGetLastError());
+  if ((rc = marginals_pairs_keep(h))) return rc;   // (gpslam_hip_marginals_keep_pair_terms: Y before a later call rewrites it)
   int flag = 0;
   HIPCHK(hipMemcpyAsync(&flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));

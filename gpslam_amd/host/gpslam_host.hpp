@@ -1097,7 +1097,8 @@ class JointMarginal {
 
 /// gtsam::Marginals(graph, values): the Gauss-Newton Hessian of the whole graph at `values`, inverted on the device
 /// (gpslam_hip_marginals).  Served: single keys (x, v, w, b and landmark keys), joint sets whose state keys belong to one
-/// state or to two adjacent states, with any landmarks; other sets throw std::invalid_argument.  On a graph that takes the segmented
+/// state or to two adjacent states, with any landmarks; other sets throw std::invalid_argument unless serveAnyStates() was called
+/// (then: any states; betweenChiSquared() gates a loop-closure candidate over the same covariances).  On a graph that takes the segmented
 /// landmark path (more than 13 planar landmarks) the landmarks of a set must sit in the same or in neighbouring fat blocks, and next to
 /// the segment of the set's states -- every landmark a state observes does; sets beyond that throw std::invalid_argument as well.
 class Marginals {
@@ -1124,6 +1125,7 @@ class Marginals {
       if (v.state >= 0) { lo = lo < 0 ? v.state : std::min(lo, v.state); hi = std::max(hi, v.state); }
       vars.push_back(v);
     }
+    if (lo >= 0 && hi - lo > 1 && any_states_) return joint_any_states(keys, vars);
     if (lo >= 0 && hi - lo > 1)
       throw std::invalid_argument("jointMarginalCovariance: the keys span non-adjacent states; only one state or two adjacent states (with any landmarks) are served");
     const int b = 2 * s_.d, ld = s_.ld, first = lo < 0 ? 0 : lo, count = lo < 0 ? 0 : hi - lo + 1;
@@ -1191,11 +1193,85 @@ class Marginals {
     }
     return r;
   }
+  /// Opt-in: serve joint sets over ANY states (gtsam::Marginals does; here the default throws beyond two adjacent states).  Keeps
+  /// one more device buffer (gpslam_hip_marginals_keep_pair_terms) and recomputes the marginals; afterwards a set's state blocks come
+  /// from gpslam_hip_get_state_pair_marginals.  Dense-border and landmark-free sessions; a session on the segmented landmark path
+  /// throws std::invalid_argument.
+  void serveAnyStates() {
+    int32_t plan[8] = {0};
+    detail::check(gpslam_hip_segment_plan(s_.h, plan), s_.h, "segment_plan");
+    if (plan[0]) throw std::invalid_argument("serveAnyStates: joint marginals over any states are not served on the segmented landmark path");
+    detail::check(gpslam_hip_marginals_keep_pair_terms(s_.h, 1), s_.h, "marginals_keep_pair_terms");
+    detail::check(gpslam_hip_marginals(s_.h), s_.h, "marginals");
+    any_states_ = true;
+  }
+  /// The chi-square gate of a loop-closure candidate BetweenFactor<Pose>(a, b, measured, Diagonal::Sigmas(sigmas)) that is not in
+  /// the graph: e^T (R + [H1 H2] Sigma [H1 H2]^T)^-1 e at the values and the marginals held (gpslam_hip_gate_between_pairs).
+  /// Needs serveAnyStates() on a graph with landmarks or loop closures.
+  template <typename Pose> double betweenChiSquared(Key a, Key b, const Pose &measured, const Vector &sigmas) const {
+    if (s_.bias) throw std::invalid_argument("betweenChiSquared: not served on AHRS graphs (rotation and bias states)");
+    if ((int)sigmas.size() != s_.d) throw std::invalid_argument("betweenChiSquared: sigmas must have the pose's tangent dimension");
+    const int32_t s1 = s_.state_of(a), s2 = s_.state_of(b);
+    const std::vector<double> m = detail::VT<Pose>::pack(measured);
+    double chi2 = 0.0;
+    const int rc = gpslam_hip_gate_between_pairs(s_.h, 1, &s1, &s2, m.data(), sigmas.data(), &chi2, nullptr, nullptr);
+    if (rc == GPSLAM_E_INVALID) throw std::invalid_argument(std::string("betweenChiSquared: ") + gpslam_hip_last_error(s_.h));
+    detail::check(rc, s_.h, "gate_between_pairs");
+    return chi2;
+  }
   /// the C-ABI handle behind these marginals
   gpslam_hip_handle *handle() const { return s_.h; }
 
  private:
   struct Var { int state, off, dim; };   // state -1: landmark coordinates off .. off + dim
+  // serveAnyStates(): a set over any states, every state pair from one gpslam_hip_get_state_pair_marginals call, the landmarks from
+  // the getters the default path uses
+  JointMarginal joint_any_states(const KeyVector &keys, const std::vector<Var> &vars) const {
+    const int b = 2 * s_.d, ld = s_.ld;
+    std::vector<int32_t> sts, lms;
+    for (const Var &v : vars) {
+      if (v.state >= 0 && std::find(sts.begin(), sts.end(), v.state) == sts.end()) sts.push_back(v.state);
+      if (v.state < 0 && std::find(lms.begin(), lms.end(), v.off / ld) == lms.end()) lms.push_back(v.off / ld);
+    }
+    const int nS = (int)sts.size(), nL = (int)lms.size();
+    auto spos = [&](int st) { return (int)(std::find(sts.begin(), sts.end(), st) - sts.begin()); };
+    auto lpos = [&](int lm) { return (int)(std::find(lms.begin(), lms.end(), lm) - lms.begin()); };
+    std::vector<int32_t> sa, sb, pa, pb, xs, xl;
+    for (int u = 0; u < nS; u++)
+      for (int v = 0; v < nS; v++) { sa.push_back(sts[u]); sb.push_back(sts[v]); }
+    for (int u = 0; u < nL; u++)
+      for (int v = 0; v < nL; v++) { pa.push_back(lms[u]); pb.push_back(lms[v]); }
+    for (int u = 0; u < nS; u++)
+      for (int v = 0; v < nL; v++) { xs.push_back(sts[u]); xl.push_back(lms[v]); }
+    std::vector<double> SS(std::max<size_t>(sa.size() * b * b, 1)), LL(std::max<size_t>(pa.size() * ld * ld, 1)), XL(std::max<size_t>(xs.size() * b * ld, 1));
+    served(gpslam_hip_get_state_pair_marginals(s_.h, (int32_t)sa.size(), sa.data(), sb.data(), SS.data()), "get_state_pair_marginals");
+    served(gpslam_hip_get_landmark_pair_marginals(s_.h, (int32_t)pa.size(), pa.data(), pb.data(), LL.data()), "get_landmark_pair_marginals");
+    served(gpslam_hip_get_state_landmark_marginals(s_.h, (int32_t)xs.size(), xs.data(), xl.data(), XL.data()), "get_state_landmark_marginals");
+    // one coordinate of the set: (position of its state) * b + c, or -1 - c for landmark coordinate c
+    auto cov = [&](int p, int q) -> double {
+      if (p >= 0 && q >= 0) return SS[(((size_t)(p / b) * nS + q / b) * b + p % b) * b + q % b];
+      if (p < 0 && q < 0) {
+        const int cp = -1 - p, cq = -1 - q;
+        return LL[(((size_t)lpos(cp / ld) * nL + lpos(cq / ld)) * ld + cp % ld) * ld + cq % ld];
+      }
+      const int st = p >= 0 ? p : q, cl = -1 - (p >= 0 ? q : p);
+      return XL[(((size_t)(st / b) * nL + lpos(cl / ld)) * b + st % b) * ld + cl % ld];
+    };
+    JointMarginal jm;
+    jm.keys_ = keys;
+    std::vector<int> coord;
+    for (const Var &v : vars) {
+      jm.off_.push_back((int)coord.size());
+      jm.dim_.push_back(v.dim);
+      for (int c = 0; c < v.dim; c++) coord.push_back(v.state >= 0 ? spos(v.state) * b + v.off + c : -1 - (v.off + c));
+    }
+    const int n = (int)coord.size();
+    jm.full_ = Matrix(n, n);
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < n; j++) jm.full_(i, j) = cov(coord[i], coord[j]);
+    return jm;
+  }
+  bool any_states_ = false;
   // a set the getters cannot serve (segmented sessions: landmarks beyond the neighbouring fat blocks) is the caller's error
   void served(int rc, const char *what) const {
     if (rc == GPSLAM_E_INVALID) throw std::invalid_argument(std::string("jointMarginalCovariance: ") + gpslam_hip_last_error(s_.h));

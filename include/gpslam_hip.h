@@ -83,7 +83,8 @@ enum {
  * gpslam_hip_set_closure_passes / gpslam_hip_closure_info / gpslam_hip_marginals_keep_closure_columns / gpslam_hip_marginals_on_segments /
  * gpslam_hip_get_landmark_marginals / gpslam_hip_get_state_landmark_marginals / gpslam_hip_get_landmark_pair_marginals /
  * gpslam_hip_add_state_gaussians / gpslam_hip_get_state_gaussians / gpslam_hip_marginalize_head / gpslam_hip_get_head_prior / gpslam_hip_append_states /
- * gpslam_hip_add_border_gaussians / gpslam_hip_get_border_gaussians / gpslam_hip_marginalize_head_onto_landmarks / gpslam_hip_get_head_prior_border).  A MAJOR bump changes a struct or a
+ * gpslam_hip_add_border_gaussians / gpslam_hip_get_border_gaussians / gpslam_hip_marginalize_head_onto_landmarks / gpslam_hip_get_head_prior_border /
+ * gpslam_hip_marginals_keep_pair_terms / gpslam_hip_get_state_pair_marginals / gpslam_hip_gate_between_pairs).  A MAJOR bump changes a struct or a
  * signature, a MINOR bump only adds. */
 #define GPSLAM_HIP_ABI_MAJOR 2
 #define GPSLAM_HIP_ABI_MINOR 4
@@ -548,6 +549,34 @@ int gpslam_hip_get_marginals(gpslam_hip_handle *h, int32_t first, int32_t count,
 int gpslam_hip_get_landmark_marginals(gpslam_hip_handle *h, int32_t first, int32_t count, double *out);
 int gpslam_hip_get_state_landmark_marginals(gpslam_hip_handle *h, int32_t count, const int32_t *state, const int32_t *landmark, double *out);
 int gpslam_hip_get_landmark_pair_marginals(gpslam_hip_handle *h, int32_t count, const int32_t *a, const int32_t *b, double *out);
+/* Sigma_{a,b} of ANY two states (Marginals::jointMarginalCovariance over states that are far apart on the chain; the covariance a
+ * chi-square gate of a loop-closure candidate needs).  Sigma_xx = A^-1 + (low-rank term), A the block-tridiagonal chain part: A^-1_{a,b}
+ * comes from the factorisation the selected inversion leaves on the device (marginals_pairs.hip: k_mg_pair, a few hundred b x b
+ * products per pair at 1e6 states, whatever |a - b|), the low-rank term from Y = [W | Z] of the two states.  Y lives in a solver buffer
+ * that later calls (normal_equations, get_rows, error, linearize_*, interpolate_*) rewrite, so on a handle with landmarks or closures
+ * the pair getters need enable != 0 BEFORE gpslam_hip_marginals, which then copies it into one more device buffer of
+ *     N * b * m doubles,  m = nl + closures * d  (column passes: m = nl; Z is what gpslam_hip_marginals_keep_closure_columns keeps)
+ * (259 MB at 1e5 Pose3 states with 7 landmarks of dimension 3 and one closure, m = 27, the widest border; allocated
+ * inside gpslam_hip_marginals, freed by enable == 0 and by destroy).  A handle with m = 0 needs no copy: there the getters work
+ * without this call.  Callable any time after create, no new compile() is needed; marginals held from before are stale.
+ * Iterations and every output of gpslam_hip_get_marginals are bit-identical with and without it.  GPSLAM_E_INVALID on a NULL handle. */
+int gpslam_hip_marginals_keep_pair_terms(gpslam_hip_handle *h, int32_t enable);
+/* out: count x b x b, block t = Sigma_{a[t], b[t]} (rows: state a[t]) in the columns of gpslam_hip_normal_equations; the pad
+ * coordinates of GPSLAM_ROT3_BIAS report zero rows and columns.  a == b is S[a] and |a - b| == 1 is S_next (transposed when a > b)
+ * of gpslam_hip_get_marginals, to the bit; every other pair is computed for (min, max) and transposed on output, so that
+ * Sigma_{b,a} = Sigma_{a,b}^T to the bit.  No atomics, fixed order: reruns are bit-identical.  Same refusals and staleness rule as
+ * gpslam_hip_get_marginals; in addition GPSLAM_E_UNSUPPORTED on the segmented landmark path (even with
+ * gpslam_hip_marginals_on_segments), GPSLAM_E_INVALID on a handle with landmarks or closures whose last gpslam_hip_marginals ran
+ * without gpslam_hip_marginals_keep_pair_terms, and for an index out of range (the message names the first such item). */
+int gpslam_hip_get_state_pair_marginals(gpslam_hip_handle *h, int32_t count, const int32_t *a, const int32_t *b, double *out);
+/* The chi-square gate of loop-closure candidates that are NOT in the graph, in the argument layout of gpslam_hip_add_between_pairs
+ * (measured count x pose_dim, sigmas count x d), at the current states and the held marginals:
+ *   err        count x d      (may be NULL) the unwhitened BetweenFactor error e
+ *   innov_cov  count x d x d  (may be NULL) P = diag(sigma^2) + [H1 H2] Sigma^{pp}_{(first, second)} [H1 H2]^T, pp: the pose-tangent blocks
+ *   chi2       count          e^T P^-1 e by a d x d Cholesky; GPSLAM_E_NOT_SPD on a non-positive pivot
+ * first == second answers GPSLAM_E_INVALID; adjacent states are allowed.  Refusals and staleness as gpslam_hip_get_state_pair_marginals. */
+int gpslam_hip_gate_between_pairs(gpslam_hip_handle *h, int32_t count, const int32_t *first, const int32_t *second,
+                                  const double *measured, const double *sigmas, double *chi2, double *err, double *innov_cov);
 /* Posterior covariance (count x d x d) of the GP-interpolated pose at tau[q] in (left[q], left[q] + 1), batched like
  * interpolate_poses -- the covariance half of the sparse-GP interpolation (Barfoot, Tong & Sarkka, RSS 2014), which GTSAM has no
  * call for:  P(tau) = H_J Sigma_J H_J^T + gp_term * c(dt, tau) * Qc,  H_J = [H1 H2 H3 H4] of interpolate_poses_jac,

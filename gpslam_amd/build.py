@@ -22,13 +22,12 @@ LIB = os.path.join(LIBDIR, "libgpslam_hip.so")
 # Gaussians, the head's marginalisation; fp64 only), and the marginals of any two states with the closure gate (marginals_pairs.hip)
 SOURCES = ["api.hip", "api_impl64.hip", "api_impl32.hip", "upper.hip", "marginals.hip", "marginals_clo.hip", "marginals_fs.hip", "closures.hip", "fixedlag.hip", "marginals_pairs.hip"]
 HEADERS = ["kernels.hpp", "closures.hpp", "factors.hpp", "lie.hpp", "devbuf.hpp", "fatsep.hpp", "dpp.hpp", "cr_step.hpp", "cr_quad.hpp", "upper.hpp", "api_common.hpp", "robust.hpp",
-           "api_decl.inc", os.path.join("..", "..", "include", "gpslam_hip.h")]
+           "marginals.hpp", "api_decl.inc", os.path.join("..", "..", "include", "gpslam_hip.h")]
 # what each translation unit includes (an edit to upper.hip does not recompile the others)
 IMPL = HEADERS + ["api_impl.inc", "api_iterate.inc"]
-CLO = HEADERS + ["marginals_clo.hpp"]
-MGFS = HEADERS + ["marginals_fs.hpp"]
+MGDEV = HEADERS + ["marginals_dev.hpp"]   # the marginals' units, and closures.hip for k_mg_keep_z
 DEPS = {"api.hip": HEADERS, "api_impl64.hip": IMPL, "api_impl32.hip": IMPL,
-        "upper.hip": ["dpp.hpp", "cr_step.hpp", "cr_quad.hpp", "upper.hpp"], "marginals.hip": CLO + ["marginals_fs.hpp"], "marginals_clo.hip": CLO, "marginals_fs.hip": MGFS, "closures.hip": CLO, "fixedlag.hip": HEADERS, "marginals_pairs.hip": CLO}
+        "upper.hip": ["dpp.hpp", "cr_step.hpp", "cr_quad.hpp", "upper.hpp"], "marginals.hip": MGDEV, "marginals_clo.hip": MGDEV, "marginals_fs.hip": MGDEV, "closures.hip": MGDEV, "fixedlag.hip": HEADERS, "marginals_pairs.hip": MGDEV}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"]
 
 

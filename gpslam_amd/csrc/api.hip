@@ -146,31 +146,16 @@ int gpslam_hip_destroy(gpslam_hip_handle *h) {
   if (!h) return 0;
   (void)hipSetDevice(h->cfg.device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  DevBuf *bufs[] = {&h->pose, &h->vel, &h->lmk, &h->pose_bak, &h->vel_bak, &h->lmk_bak, &h->d_gp_left, &h->d_gp_dt,
-                    &h->d_gp_row0, &h->rowLR, &h->rowE, &h->rowC, &h->rowCE, &h->crowptr, &h->rowM, &h->rowLm, &h->rowptr, &h->partial, &h->lmrow,
-                    &h->lmrow_state, &h->lmrow_ptr, &h->lm_t, &h->lm_S, &h->lm_dL, &h->lm_chunk_lm, &h->lm_chunk_j0, &h->lm_chunk_j1, &h->lm_chunk_ptr, &h->lm_part, &h->gsave, &h->dvec,
-                    &h->halo_add, &h->iface_send, &h->iface_recv, &h->top_blk, &h->top_x, &h->scal, &h->flag,
-                    &h->api_e, &h->api_H, &h->gps, &h->gpidx, &h->dU, &h->gsave2, &h->partial2, &h->brec, &h->btwidx,
-                    &h->rowI, &h->irowptr, &h->coll_s, &h->coll_r, &h->simd_cnt};
-  for (DevBuf *b : bufs) b->release();
-  marginals_release(h);
-  for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri}) s->release();
-  h->clo.release();
-  h->sg.release();
-  h->bg.release();
-  h->fl_out.release(); h->fl_flag.release(); h->fl_head.release();
-  for (MeasSet &s : h->ms) s.release();
-  h->fs.release();
-  h->lm_gL.release();
-  for (Level &v : h->lv) { v.blk.release(); v.add.release(); v.x.release(); }
   for (int i = 0; i < 6; i++) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   if (h->ev_l0a) (void)hipEventDestroy(h->ev_l0a);
   if (h->ev_l0b) (void)hipEventDestroy(h->ev_l0b);
   if (h->aux_stream) { (void)hipStreamSynchronize(h->aux_stream); (void)hipStreamDestroy(h->aux_stream); }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+  // the handle's own stream goes before the buffers: it was drained above, hipFree needs no stream, and nothing of the handle is
+  // read between the two statements
   if (h->stream && h->own_stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // every DevBuf frees itself, with the handle's device still current
   return 0;
 }
 
@@ -188,8 +173,8 @@ int gpslam_hip_set_stream(gpslam_hip_handle *h, void *stream) {
 }
 
 int gpslam_hip_set_qc(gpslam_hip_handle *h, const double *Qc) {
-  if (h) h->marg_ok = false;   // the marginals of gpslam_hip_marginals are stale from here on
   if (!h || !Qc) return GPSLAM_E_INVALID;
+  h->mg.invalidate();
   double U[36], Qpad[36];
   if (h->mf == ROT3_BIAS) {   // Qc is the 3 x 3 of GaussianProcessPriorRot3; bias and pad components: identity (see GpPrior<ROT3_BIAS>)
     std::memset(Qpad, 0, sizeof(Qpad));
@@ -207,8 +192,8 @@ int gpslam_hip_set_qc(gpslam_hip_handle *h, const double *Qc) {
 }
 
 int gpslam_hip_set_states(gpslam_hip_handle *h, int32_t N, const double *pose, const double *vel) {
-  if (h) h->marg_ok = false;   // the marginals of gpslam_hip_marginals are stale from here on
   if (!h || N <= 0 || !pose || !vel) return GPSLAM_E_INVALID;
+  h->mg.invalidate();
   (void)hipSetDevice(h->cfg.device);
   const bool same = (N == h->N) && h->pose.p;
   if (N != h->N) h->compiled = false;
@@ -233,8 +218,8 @@ int gpslam_hip_set_states(gpslam_hip_handle *h, int32_t N, const double *pose, c
 }
 
 int gpslam_hip_set_halo_state(gpslam_hip_handle *h, const double *pose, const double *vel) {
-  if (h) h->marg_ok = false;   // the marginals of gpslam_hip_marginals are stale from here on
   if (!h || h->N <= 0 || !pose || !vel || !h->pose.p) return GPSLAM_E_INVALID;
+  h->mg.invalidate();
   (void)hipSetDevice(h->cfg.device);
   std::vector<double> pv(h->pd), vv(h->d);
   for (int k = 0; k < h->pd; k++) pv[k] = pose[k];
@@ -262,8 +247,8 @@ int gpslam_hip_get_states(gpslam_hip_handle *h, double *pose, double *vel) {
 }
 
 int gpslam_hip_set_landmarks(gpslam_hip_handle *h, int32_t L, const double *pts) {
-  if (h) h->marg_ok = false;   // the marginals of gpslam_hip_marginals are stale from here on
   if (!h || L < 0 || (L > 0 && (!pts || h->ld == 0))) return GPSLAM_E_INVALID;
+  h->mg.invalidate();
   (void)hipSetDevice(h->cfg.device);
   if (L != h->L) h->compiled = false;
   h->L = L;
@@ -289,7 +274,7 @@ int gpslam_hip_add_gp_priors(gpslam_hip_handle *h, int32_t count, const int32_t 
   h->gp_dt.insert(h->gp_dt.end(), dt, dt + count);
   h->gp_q.insert(h->gp_q.end(), (size_t)count, 0);
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 int gpslam_hip_add_gp_priors_qc(gpslam_hip_handle *h, int32_t count, const int32_t *left, const double *dt, const double *Qc) {
@@ -324,7 +309,7 @@ int gpslam_hip_add_gp_priors_qc(gpslam_hip_handle *h, int32_t count, const int32
   h->gp_dt.insert(h->gp_dt.end(), dt, dt + count);
   h->gp_q.insert(h->gp_q.end(), q.begin(), q.end());
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 int gpslam_hip_set_meas_covariance(gpslam_hip_handle *h, int32_t kind, int32_t count, const double *cov) {
@@ -340,7 +325,7 @@ int gpslam_hip_set_meas_covariance(gpslam_hip_handle *h, int32_t kind, int32_t c
       s.sig[(size_t)(n - count + k)] = std::sqrt(cov[k]);
     }
     h->compiled = false;
-    h->marg_ok = false;
+    h->mg.invalidate();
     return 0;
   }
   std::vector<double> R((size_t)count * rows * rows, 0.0);
@@ -353,7 +338,7 @@ int gpslam_hip_set_meas_covariance(gpslam_hip_handle *h, int32_t kind, int32_t c
   }
   std::memcpy(&s.sqi[(size_t)(n - count) * rows * rows], R.data(), R.size() * sizeof(double));
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 // (loss, k) of `count` factors behind `first` of a table of n entries (created on first use; dropped again when no entry is left)
@@ -375,7 +360,7 @@ static int set_robust(gpslam_hip_handle *h, std::vector<double> &tab, int n, int
   for (size_t q = 0; q < tab.size(); q += 2) any = any || tab[q] != 0.0;
   if (!any) tab.clear();      // nothing but NONE: the handle is what it was before the first call
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 int gpslam_hip_set_meas_robust(gpslam_hip_handle *h, int32_t kind, int32_t count, const int32_t *loss, const double *k) {
@@ -432,7 +417,7 @@ int gpslam_hip_add_between_pairs(gpslam_hip_handle *h, int32_t count, const int3
     if (!h->clo.rob.empty()) h->clo.rob.insert(h->clo.rob.end(), 2, 0.0);
   }
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 int gpslam_hip_set_closure_passes(gpslam_hip_handle *h, int32_t max_passes, int32_t closures_per_pass) {
@@ -441,7 +426,7 @@ int gpslam_hip_set_closure_passes(gpslam_hip_handle *h, int32_t max_passes, int3
   h->clo.max_passes = max_passes < 1 ? 1 : max_passes;
   h->clo.per_pass = closures_per_pass;
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 int gpslam_hip_closure_info(gpslam_hip_handle *h, int32_t out4[4]) {
@@ -554,7 +539,7 @@ int gpslam_hip_clear_factors(gpslam_hip_handle *h) {
     s.any_aux = false;
   }
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 
@@ -629,10 +614,7 @@ static int interpolate_impl(gpslam_hip_handle *h, int32_t count, const int32_t *
   std::vector<double> coef((size_t)count * 4);
   for (int q = 0; q < count; q++) interp_coef(dt[q], tau[q], &coef[4 * (size_t)q]);
   std::vector<int> li(left, left + count);
-  struct Scratch {   // query buffers live for this call only
-    DevBuf left, coef, out, outH;
-    ~Scratch() { left.release(); coef.release(); out.release(); outH.release(); }
-  } sc;
+  struct { DevBuf left, coef, out, outH; } sc;   // this call's own buffers
   int rc;
   if ((rc = upload(h, sc.left, li))) return rc;
   if ((rc = upload(h, sc.coef, coef))) return rc;
@@ -693,10 +675,7 @@ int gpslam_hip_interpolate_velocities(gpslam_hip_handle *h, int32_t count, const
     coef[4 * (size_t)q + 3] = p22;
   }
   std::vector<int> li(left, left + count);
-  struct Scratch {
-    DevBuf left, coef, out, outH;
-    ~Scratch() { left.release(); coef.release(); out.release(); outH.release(); }
-  } sc;
+  struct { DevBuf left, coef, out, outH; } sc;   // this call's own buffers
   int rc;
   if ((rc = upload(h, sc.left, li))) return rc;
   if ((rc = upload(h, sc.coef, coef))) return rc;
@@ -724,10 +703,7 @@ int gpslam_hip_body_centric_velocity(gpslam_hip_handle *h, int32_t which, int32_
     if (!(dt[q] != 0.0)) return fail(h, GPSLAM_E_INVALID, "delta_t must not be zero");
   if (count == 0) return 0;
   (void)hipSetDevice(h->cfg.device);
-  struct Scratch {
-    DevBuf a, b, t, o;
-    ~Scratch() { a.release(); b.release(); t.release(); o.release(); }
-  } sc;
+  struct { DevBuf a, b, t, o; } sc;   // this call's own buffers
   const size_t np = (size_t)count * 12 * sizeof(double);
   HIPCHK(sc.a.reserve(np)); HIPCHK(sc.b.reserve(np));
   HIPCHK(sc.t.reserve((size_t)count * sizeof(double))); HIPCHK(sc.o.reserve((size_t)count * 6 * sizeof(double)));
@@ -744,14 +720,14 @@ int gpslam_hip_body_centric_velocity(gpslam_hip_handle *h, int32_t which, int32_
 // ---- precision dispatch: the handle was created GPSLAM_FP64 or GPSLAM_FP32.  The one forwarder: null check, then the namespace.
 #define GPS_BY_PRECISION(name, h, ...) \
   (!(h) ? GPSLAM_E_INVALID : (h)->cfg.precision == GPSLAM_FP32 ? impl32::name(h, ##__VA_ARGS__) : impl64::name(h, ##__VA_ARGS__))
-// in front of every forwarder that moves the estimate (a step, a trial, a reject): covariances held from before are stale
-static void invalidates_marginals(gpslam_hip_handle *h) { if (h) h->marg_ok = false; }
+// ... with h->mg.invalidate() behind the null check: every forwarder that moves the estimate (a step, a trial, a reject) or rebuilds
+// the graph's tables (compile) -- covariances held from before are stale
+#define GPS_BY_PRECISION_STALE(name, h, ...) (!(h) ? GPSLAM_E_INVALID : ((h)->mg.invalidate(), GPS_BY_PRECISION(name, h, ##__VA_ARGS__)))
 
 int gpslam_hip_compile(gpslam_hip_handle *h) {
   if (!h) return GPSLAM_E_INVALID;
-  h->marg_ok = false;
-  if (h->marg_N != 0 && h->marg_N != h->N) marginals_release(h);   // (the marginals' buffers are sized by N)
-  return GPS_BY_PRECISION(gpslam_hip_compile, h);
+  h->mg.fit(h->N);   // freed now if N changed: the marginals' buffers are sized by N, and the next call may be far off
+  return GPS_BY_PRECISION_STALE(gpslam_hip_compile, h);
 }
 int gpslam_hip_linearize_gp(gpslam_hip_handle *h, double *errors, double *jacobians) {
   return GPS_BY_PRECISION(gpslam_hip_linearize_gp, h, errors, jacobians);
@@ -763,20 +739,16 @@ int gpslam_hip_error(gpslam_hip_handle *h, double *err) { return GPS_BY_PRECISIO
 int gpslam_hip_get_meas_weights(gpslam_hip_handle *h, int32_t kind, double *w) { return GPS_BY_PRECISION(gpslam_hip_get_meas_weights, h, kind, w); }
 int gpslam_hip_get_between_pairs_weights(gpslam_hip_handle *h, double *w) { return GPS_BY_PRECISION(gpslam_hip_get_between_pairs_weights, h, w); }
 int gpslam_hip_iterate_gn(gpslam_hip_handle *h, gpslam_hip_stats *st) {
-  invalidates_marginals(h);
-  return GPS_BY_PRECISION(gpslam_hip_iterate_gn, h, st);
+  return GPS_BY_PRECISION_STALE(gpslam_hip_iterate_gn, h, st);
 }
 int gpslam_hip_run_gn(gpslam_hip_handle *h, int32_t iters, gpslam_hip_stats *st, double *out5) {
-  invalidates_marginals(h);
-  return GPS_BY_PRECISION(gpslam_hip_run_gn, h, iters, st, out5);
+  return GPS_BY_PRECISION_STALE(gpslam_hip_run_gn, h, iters, st, out5);
 }
 int gpslam_hip_iterate_lm(gpslam_hip_handle *h, double *lambda, const gpslam_hip_params *p, gpslam_hip_stats *st) {
-  invalidates_marginals(h);
-  return GPS_BY_PRECISION(gpslam_hip_iterate_lm, h, lambda, p, st);
+  return GPS_BY_PRECISION_STALE(gpslam_hip_iterate_lm, h, lambda, p, st);
 }
 int gpslam_hip_optimize(gpslam_hip_handle *h, const gpslam_hip_params *p, gpslam_hip_stats *st) {
-  invalidates_marginals(h);
-  return GPS_BY_PRECISION(gpslam_hip_optimize, h, p, st);
+  return GPS_BY_PRECISION_STALE(gpslam_hip_optimize, h, p, st);
 }
 int gpslam_hip_normal_equations(gpslam_hip_handle *h, double *D, double *O, double *g, double *B) {
   return GPS_BY_PRECISION(gpslam_hip_normal_equations, h, D, O, g, B);
@@ -797,8 +769,7 @@ int gpslam_hip_interface_recv(gpslam_hip_handle *h, void **dev_ptr, size_t *byte
   return GPS_BY_PRECISION(gpslam_hip_interface_recv, h, dev_ptr, bytes);
 }
 int gpslam_hip_iterate_phase1(gpslam_hip_handle *h, double lambda) {
-  invalidates_marginals(h);
-  return GPS_BY_PRECISION(gpslam_hip_iterate_phase1, h, lambda);
+  return GPS_BY_PRECISION_STALE(gpslam_hip_iterate_phase1, h, lambda);
 }
 int gpslam_hip_iterate_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) { return GPS_BY_PRECISION(gpslam_hip_iterate_phase2, h, st); }
 int gpslam_hip_iterate_phase2a(gpslam_hip_handle *h) { return GPS_BY_PRECISION(gpslam_hip_iterate_phase2a, h); }
@@ -826,7 +797,7 @@ int gpslam_hip_fs_set_split(gpslam_hip_handle *h, int32_t rank, int32_t nranks, 
   h->fs.first_lm.assign(first_lm, first_lm + n_first);
   h->fs.last_lm.assign(last_lm, last_lm + n_last);
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 int gpslam_hip_fs_split_info(gpslam_hip_handle *h, int32_t out4[4]) { return GPS_BY_PRECISION(gpslam_hip_fs_split_info, h, out4); }
@@ -834,19 +805,17 @@ int gpslam_hip_fs_set_top(gpslam_hip_handle *h, int32_t nb_top) { return GPS_BY_
 int gpslam_hip_fs_interface(gpslam_hip_handle *h, void **send, size_t *send_bytes, void **recv, size_t *recv_bytes) {
   return GPS_BY_PRECISION(gpslam_hip_fs_interface, h, send, send_bytes, recv, recv_bytes);
 }
-int gpslam_hip_fs_phase1(gpslam_hip_handle *h, double lambda) { invalidates_marginals(h); return GPS_BY_PRECISION(gpslam_hip_fs_phase1, h, lambda); }
+int gpslam_hip_fs_phase1(gpslam_hip_handle *h, double lambda) { return GPS_BY_PRECISION_STALE(gpslam_hip_fs_phase1, h, lambda); }
 int gpslam_hip_fs_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st) { return GPS_BY_PRECISION(gpslam_hip_fs_phase2, h, st); }
 int gpslam_hip_fs_lm_trial_phase1(gpslam_hip_handle *h, double lambda) {
-  invalidates_marginals(h);
-  return GPS_BY_PRECISION(gpslam_hip_fs_lm_trial_phase1, h, lambda);
+  return GPS_BY_PRECISION_STALE(gpslam_hip_fs_lm_trial_phase1, h, lambda);
 }
 int gpslam_hip_fs_lm_trial_phase2(gpslam_hip_handle *h, double *out6) { return GPS_BY_PRECISION(gpslam_hip_fs_lm_trial_phase2, h, out6); }
 int gpslam_hip_lm_begin(gpslam_hip_handle *h) { return GPS_BY_PRECISION(gpslam_hip_lm_begin, h); }
 int gpslam_hip_lm_trial_phase1(gpslam_hip_handle *h, double lambda) {
-  invalidates_marginals(h);
-  return GPS_BY_PRECISION(gpslam_hip_lm_trial_phase1, h, lambda);
+  return GPS_BY_PRECISION_STALE(gpslam_hip_lm_trial_phase1, h, lambda);
 }
 int gpslam_hip_lm_trial_phase2(gpslam_hip_handle *h, double *out6) { return GPS_BY_PRECISION(gpslam_hip_lm_trial_phase2, h, out6); }
-int gpslam_hip_lm_reject(gpslam_hip_handle *h) { invalidates_marginals(h); return GPS_BY_PRECISION(gpslam_hip_lm_reject, h); }
+int gpslam_hip_lm_reject(gpslam_hip_handle *h) { return GPS_BY_PRECISION_STALE(gpslam_hip_lm_reject, h); }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // api_common.hpp -- what the translation units of the library's host side share (api.hip: the C ABI; api_impl64.hip / api_impl32.hip:
-// api_impl.inc + api_iterate.inc once per row precision; closures.hip, marginals.hip, marginals_clo.hip, marginals_fs.hip): the handle, the host helpers and the kernel launchers
+// api_impl.inc + api_iterate.inc once per row precision; closures.hip, fixedlag.hip, the four marginals*.hip): the handle, the host helpers and the
+// kernel launchers.  The marginals' state is marginals.hpp's (h->mg); device buffers free themselves (devbuf.hpp: no list names them)
 // (round 3: api.hip was one 3.5-minute translation unit; the fp64 and fp32 halves compile side by side now)
 #pragma once
 // api.hip -- host side of libgpslam_hip.so: the opaque handle, the graph-compile pass and the C ABI
@@ -22,6 +23,7 @@
 #include "devbuf.hpp"
 #include "kernels.hpp"
 #include "closures.hpp"
+#include "marginals.hpp"
 #include "fatsep.hpp"
 #include "upper.hpp"
 
@@ -40,7 +42,6 @@ struct SimpleSet {  // PriorFactor / BetweenFactor style factors: index + measur
   int width = 0;  // doubles per measurement
   DevBuf d_idx, d_meas, d_sig, d_row0;
   int count() const { return (int)idx.size(); }
-  void release() { d_idx.release(); d_meas.release(); d_sig.release(); d_row0.release(); }
 };
 
 struct MeasSet {  // measurement factors (kernels.hpp FKind)
@@ -62,7 +63,6 @@ struct MeasSet {  // measurement factors (kernels.hpp FKind)
   DevBuf d_rob, d_w;                   // the loss table and the weights w(r) of the last pass that was asked for them
   DevBuf d_irow0;                      // first row of each factor in the table of 16-double interpolated rows (Plan::lines)
   int count() const { return (int)idx.size(); }
-  void release() { d_idx.release(); d_lm.release(); d_meas.release(); d_sig.release(); d_coef.release(); d_row0.release(); d_aux.release(); d_aidx.release(); d_sqi.release(); d_irow0.release(); d_rob.release(); d_w.release(); }
 };
 
 // loop closures (gpslam_hip_add_between_pairs; closures.hpp, launched by closures.hip): fac.idx = first state, second = second state
@@ -77,7 +77,6 @@ struct Closures {
   // of them -- P > 1: slices of `slice` closures, W = U [X | Z] and pass 0's X kept between the passes
   int max_passes = 1, per_pass = 0, slice = 0, P = 0;
   DevBuf W, X;
-  void release() { fac.release(); for (DevBuf *b : {&d_second, &A, &Y, &d_rob, &w, &W, &X}) b->release(); }
 };
 
 // joint Gaussian factors on one state (gpslam_hip_add_state_gaussians; fixedlag.hip): r = A [Local(pose_lin, pose_i) ; vel_i - vel_lin] - c,
@@ -89,7 +88,6 @@ struct StateGauss {
   DevBuf d_idx, d_lin, d_A, d_c, d_row0;
   int count() const { return (int)idx.size(); }
   void clear() { idx.clear(); lin.clear(); A.clear(); c.clear(); }
-  void release() { for (DevBuf *b : {&d_idx, &d_lin, &d_A, &d_c, &d_row0}) b->release(); }
 };
 
 // joint Gaussian factors on one state AND every landmark of the handle (gpslam_hip_add_border_gaussians; fixedlag.hip): n = b + nl,
@@ -104,7 +102,6 @@ struct BorderGauss {
   DevBuf d_idx, d_lin, d_A, d_c, d_r;   // d_r: count x n residuals of the last pass
   int count() const { return (int)idx.size(); }
   void clear() { idx.clear(); lin.clear(); A.clear(); c.clear(); nl = 0; }
-  void release() { for (DevBuf *b : {&d_idx, &d_lin, &d_A, &d_c, &d_r}) b->release(); }
 };
 
 // Which kernels serve a compiled graph, and in which form.  make_plan() (api_impl.inc) fills one per compile(), once the row layout
@@ -229,45 +226,14 @@ struct gpslam_hip_handle {
   int pend_dmax_n = 0, pend_dmax_slot = 0;      // pending: maxima in `partial2`
   double l0_ms = 0.0;         // the level-0 forward launch, accumulated over the last timed run: the dominant kernel INSIDE an iteration
   double ph_lambda = 0.0;
-  // gpslam_hip_marginals (marginals.hip): blocks of H^-1 at the states of the last call; marg_ok is cleared by every call that
-  // can change states, landmarks, factors or Qc
-  bool marg_ok = false;
-  int marg_N = 0;
-  DevBuf mg_fac, mg_S, mg_Sn, mg_up, mg_K, mg_Slm, mg_Sxl;
-  // gpslam_hip_marginals_keep_closure_columns: on a handle in column passes (clo.P > 1) the marginals keep Z = A^-1 U^T at every
-  // state (mg_Z: mg_zrows(N, b) rows of mg_ldz(clo.nc) doubles) and the inverse of I + U Z (mg_Minv: mg_ldz(clo.nc) squared)
-  bool mg_keep_z = false;
-  DevBuf mg_Z, mg_Minv;
-  // gpslam_hip_marginals_on_segments: the marginals run on the segmented landmark path (marginals_fs.hip) and keep the fat chain's
-  // selected inverse (mg_fsD: K blocks Sigma_{k,k}; mg_fsP: one block Sigma_{left,right} per link of the cyclic reduction, the first
-  // K - 1 of them Sigma_{k,k+1}) and G = A_s^-1 H[I_s, B_s] at every interior state (mg_G: (N b + 64) rows of NCP doubles)
-  bool mg_on_segments = false;
-  DevBuf mg_fsD, mg_fsP, mg_G;
-  // gpslam_hip_marginals_keep_pair_terms: the marginals copy Y = [W | Z] -- columns 1 .. R - 1 of the level-0 solution, which later
-  // calls may rewrite -- into mg_Y (N x mg_Ym x b doubles; in column passes only the nl landmark columns W) for the pair getters
-  // (marginals_pairs.hip); mg_pairs_ok: the last gpslam_hip_marginals left what gpslam_hip_get_state_pair_marginals needs
-  bool mg_keep_pairs = false, mg_pairs_ok = false;
-  int mg_Ym = 0;
-  DevBuf mg_Y;
+  Marginals mg;               // gpslam_hip_marginals (marginals.hpp): what the last call left; every call that can change states, landmarks,
+                              // factors or Qc says h->mg.invalidate()
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch
   int dbg_trace_waves = 0;
 #endif
 };
-
-// frees the marginals' buffers (destroy; compile when N changed)
-void marginals_release(gpslam_hip_handle *h);
-// the closure term of the marginals on a handle in column passes (marginals_clo.hip)
-int marginals_closure_term(gpslam_hip_handle *h);
-// the marginals of a handle on the segmented landmark path, and the gather behind the landmark getters (marginals_fs.hip)
-int marginals_fs(gpslam_hip_handle *h);
-void marginals_fs_release(gpslam_hip_handle *h);
-int marginals_fs_gather(gpslam_hip_handle *h, int mode, int32_t count, const int32_t *a, const int32_t *b, double *out);
-// behind gpslam_hip_marginals' last kernel: the copy of Y for the pair getters (marginals_pairs.hip; nothing without the opt-in)
-int marginals_pairs_keep(gpslam_hip_handle *h);
-// the refusals and the staleness rule of every marginals getter (marginals.hip)
-int marginals_getter_check(gpslam_hip_handle *h);
 
 // What the launches of one call do: each entry point builds the mode it means and hands it to the launch helpers.
 // LaunchMode{}: row tables (d = 3 records where the graph has them), level 0 unfused, every reduction at once, untimed.
@@ -291,7 +257,7 @@ struct LaunchMode {
 // of U^T into the records (U^T r into the gradient copy if save_g); pass == P in column passes: the final pass's right-hand sides
 // U^T Y.  closures_correct: one pass -- Y = (I + U Z)^-1 ([r | 0] - U X) and X += Z Y, between the chain's back-substitution and the
 // landmark Schur complement.  Column passes (launch_solve_passes, api_impl.inc): closures_collect behind pass p's backward sweep
-// (keep_z: the slice of Z into h->mg_Z first; pass 0: X saved; W gathered; behind the last pass the wide solve for Y),
+// (keep_z: the slice of Z into h->mg.Z first; pass 0: X saved; W gathered; behind the last pass the wide solve for Y),
 // closures_add behind the final pass.
 int closures_upload(gpslam_hip_handle *h);
 void closures_eval(gpslam_hip_handle *h, const LaunchMode &m, int pass, double *partial, hipStream_t st);
@@ -534,7 +500,7 @@ int add_simple(gpslam_hip_handle *h, SimpleSet &s, int width, int sigw, int32_t 
   s.meas.insert(s.meas.end(), meas, meas + (size_t)count * width);
   s.sig.insert(s.sig.end(), sig, sig + (size_t)count * sigw);
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 
@@ -582,7 +548,7 @@ int add_meas(gpslam_hip_handle *h, int fk, int rows, int mw, bool two, bool hasl
     if (sensor || calib) s.any_aux = true;
   }
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 

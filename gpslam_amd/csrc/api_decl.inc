@@ -36,7 +36,7 @@ int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, do
 int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot, bool e32);
 // gpslam_hip_marginals (marginals.hip): the assembly of gpslam_hip_normal_equations; then the solver's right-hand sides at
 // lambda = 0 (forward, backward, closure correction) and the landmark Schur complement, without the landmark solve -- on a handle
-// in column passes launch_solve_passes, every slice of Z kept in h->mg_Z on the way (gpslam_hip_marginals_keep_closure_columns)
+// in column passes launch_solve_passes, every slice of Z kept in h->mg.Z on the way (gpslam_hip_marginals_keep_closure_columns)
 int marginals_assemble(gpslam_hip_handle *h);
 int marginals_border(gpslam_hip_handle *h);
 // the same on the segmented landmark path (marginals_fs.hip): fs_forward at lambda = 0 in the two-launch form, Y into the caller's buffer

@@ -853,7 +853,7 @@ int fs_build(gpslam_hip_handle *h, const std::vector<int> &touch_lo, const std::
     HIPCHK(hipMemsetAsync(p.Gev.p, 0, (size_t)std::max(p.ngroups, 1) * ld * b * sizeof(Real), st));
   }
   {   // rows of each landmark that touch its own / the next / the previous cut state, by position of the landmark in fat_lm
-    if (L == 0) {
+    if (L == 0) {   // freed now: without landmarks there are no such rows, and an earlier compile() may have left its tables
       for (DevBuf *bf : {&p.d_fa_ptr, &p.d_fa_it, &p.d_fb_ptr, &p.d_fb_it, &p.d_fc_ptr, &p.d_fc_it}) bf->release();
     } else {
       std::vector<int> ptr[3], it[3];
@@ -937,7 +937,7 @@ int fs_build(gpslam_hip_handle *h, const std::vector<int> &touch_lo, const std::
     }
     HIPCHK(upload_vec(st, p.d_sc_base, sc_base));
     HIPCHK(upload_vec(st, p.d_sc_ptr, sc_ptr));
-    p.Y.release();
+    p.Y.release();   // freed now: the fused sweep never reads Y, and it is the plan's largest buffer
   } else {
     HIPCHK(p.Y.reserve((size_t)N * b * p.NCP * sizeof(Real)));
     HIPCHK(hipMemsetAsync(p.Y.p, 0, (size_t)N * b * p.NCP * sizeof(Real), st));   // padding columns stay zero for good
@@ -987,7 +987,7 @@ int fs_build(gpslam_hip_handle *h, const std::vector<int> &touch_lo, const std::
 
 // Closures in column passes (clo.P > 1): the caller's assembly carried slice 0.  Every pass is the same factorisation at the same
 // lambda; the records are reassembled in front of each one because the elimination works in place.  The marginals run the same
-// passes at lambda = 0 with keep_z (every pass's slice of Z = A^-1 U^T copied into h->mg_Z behind its backward sweep) and without
+// passes at lambda = 0 with keep_z (every pass's slice of Z = A^-1 U^T copied into h->mg.Z behind its backward sweep) and without
 // the landmark solve (the landmark reduction alone ends them: the states stay).  Leaves W = U [X | Z] in clo.W and the corrected
 // landmark columns in the leading columns of the level-0 solution.
 int launch_solve_passes(gpslam_hip_handle *h, const LaunchMode &m, double lambda, bool keep_z, bool solve_landmarks) {
@@ -1438,7 +1438,6 @@ int build_hierarchy(gpslam_hip_handle *h, const Plan &p) {
   }
   const int m1 = h->cfg.upper_chunk > 1 ? h->cfg.upper_chunk : 4;
   const int top = h->cfg.top_blocks > 0 ? h->cfg.top_blocks : 8;
-  for (Level &v : h->lv) { v.blk.release(); v.add.release(); v.x.release(); }
   h->lv.clear();
   const size_t BS = (size_t)2 * b * b + (size_t)b * h->R, AS = (size_t)b * b + (size_t)b * h->R;
   int n = N;
@@ -1451,9 +1450,9 @@ int build_hierarchy(gpslam_hip_handle *h, const Plan &p) {
     // (not on a sharded handle: the padding of the tail would sit between the last state and the next rank's separator)
     if (l == 1 && p.upper_cr && p.rows() && n > kUpG && !sharded(h)) v.m = 4;
     v.nch = nblocks(n, v.m);
-    h->lv.push_back(v);
+    h->lv.push_back(std::move(v));
     if (n <= ((l >= 1 && p.upper_cr) ? kUpG : top)) break;
-    n = v.nch;
+    n = h->lv.back().nch;
   }
   for (size_t l = 0; l < h->lv.size(); l++) {
     Level &v = h->lv[l];
@@ -1773,7 +1772,7 @@ int fixedlag_assemble(gpslam_hip_handle *h) {
 }
 // ... and the solver's right-hand sides at lambda = 0: the closure columns Z = A^-1 J_c^T, the landmark columns corrected for the
 // closures, and the landmark Schur complement S of the whole chain -- launch_solve without the landmark solve (the states stay).
-// On a handle in column passes (gpslam_hip_marginals_keep_closure_columns) every slice of Z is kept in h->mg_Z on the way.
+// On a handle in column passes (gpslam_hip_marginals_keep_closure_columns) every slice of Z is kept in h->mg.Z on the way.
 int marginals_border(gpslam_hip_handle *h) { return launch_solve(h, LaunchMode{}, 0.0, true, false); }
 // ... and on the segmented landmark path (marginals_fs.hip) the forward half at lambda = 0: segment factors, the half-swept border
 // Y = L^-1 G into the marginals' own buffer (zeroed by the caller; a fused_sweep plan has none), the fat chain's cyclic reduction

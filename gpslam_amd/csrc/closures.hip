@@ -2,7 +2,7 @@
 // handles only (compile() refuses the others), so this is compiled once, like the marginals, and both precision namespaces of
 // api_impl.inc call into it (api_common.hpp declares the entry points and says where each one stands in an iteration).
 #include "api_common.hpp"
-#include "marginals_clo.hpp"
+#include "marginals_dev.hpp"
 
 namespace {
 
@@ -103,7 +103,7 @@ void closures_collect(gpslam_hip_handle *h, int p, bool keep_z) {
   const size_t kept = (size_t)h->N * wid * h->b;
   dispatch_b(h->b, [&](auto tag) {
     constexpr int D = decltype(tag)::value / 2;
-    if (keep_z) k_mg_keep_z<D><<<dim3((unsigned)((kept + 255) / 256)), dim3(256), 0, h->stream>>>(a, cp, h->mg_Z.as<double>(), mg_ldz(h->clo.nc));
+    if (keep_z) k_mg_keep_z<D><<<dim3((unsigned)((kept + 255) / 256)), dim3(256), 0, h->stream>>>(a, cp, h->mg.Z.as<double>(), mg_ldz(h->clo.nc));
     if (p == 0) k_clo_save<D><<<dim3(nblocks(clo_nlead(h), 256)), dim3(256), 0, h->stream>>>(a, cp);
     k_clo_gather<D><<<dim3(nblocks(entries, 256)), dim3(256), 0, h->stream>>>(a, cp);
     if (p == h->clo.P - 1) k_clo_solve_wide<D><<<dim3(1), dim3(256), clo_wide_lds(h->clo.nc, a.ncols), h->stream>>>(a, clo_pass(h, 0));

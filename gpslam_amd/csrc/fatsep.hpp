@@ -2153,16 +2153,6 @@ struct FatSepPlan {
   std::vector<int> h_lmrow, h_lmstate, h_lmptr;     // compile(): rows per landmark, sorted by left state
   std::vector<int> h_lm_fat, h_lm_slot;             // host copies of d_lm_fat / d_lm_slot (the marginals' landmark getters)
 
-  void release() {
-    for (DevBuf *b : {&d_cuts, &d_segid, &d_fat_lm_ptr, &d_fat_lm, &d_lm_fat, &d_lm_slot, &d_lmpri_ptr, &d_lmpri, &d_elim, &d_upd,
-                      &fac, &Y, &Aseg, &Dfat, &link, &gfat, &Qbuf, &S1, &S2, &sv, &xfat, &gL, &rhs, &partial,
-                      &send, &recv, &tD, &tlink, &tg, &tQ, &tS1, &tS2, &tsv, &tx, &d_telim, &d_tupd, &d_lm_own, &lm_tmp,
-                      &d_lg_ptr, &d_lg_state, &d_lg_mptr, &d_lg_m, &Gev, &d_sc_base, &d_sc_ptr, &d_se_pk, &d_se_src,
-                      &d_fa_ptr, &d_fa_it, &d_fb_ptr, &d_fb_it, &d_fc_ptr, &d_fc_it, &lmMM})
-      b->release();
-    active = false;
-  }
-
   // Level sets of the block cyclic reduction over K blocks in chain order: every level eliminates every other active block.
   // keep_last: the last block is never eliminated (a piece of a split chain stops at its two end blocks; end_link then is
   // the link between them).  elim: 6 ints per eliminated block, upd: 3 per survivor with an eliminated neighbour (FatLevel).

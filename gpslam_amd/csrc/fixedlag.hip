@@ -590,11 +590,6 @@ const char *widths_ok(gpslam_hip_handle *h) {
 const char *kMeasNames[kNumMeasKinds] = {"interpolated range", "range", "interpolated attitude", "interpolated GPS", "odometry2d", "bearing-range",
                                          "interpolated projection", "AHRS"};
 
-struct Scratch {
-  DevBuf a, b;
-  ~Scratch() { a.release(); b.release(); }
-};
-
 }  // namespace
 
 // ---- what compile() and the factor launches call (api_common.hpp)
@@ -696,7 +691,7 @@ int gpslam_hip_add_border_gaussians(gpslam_hip_handle *h, int32_t count, const i
   s.A.insert(s.A.end(), A, A + (size_t)count * n * n);
   s.c.insert(s.c.end(), c, c + (size_t)count * n);
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 
@@ -761,7 +756,7 @@ int gpslam_hip_add_state_gaussians(gpslam_hip_handle *h, int32_t count, const in
   s.A.insert(s.A.end(), A, A + (size_t)count * b * b);
   s.c.insert(s.c.end(), c, c + (size_t)count * b);
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 
@@ -905,7 +900,7 @@ int gpslam_hip_marginalize_head(gpslam_hip_handle *h, int32_t k) {
   }
   h->pend_upd = false; h->pend_err_n = 0; h->pend_dmax_n = 0;
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 
@@ -929,30 +924,26 @@ int gpslam_hip_append_states(gpslam_hip_handle *h, int32_t n, const double *pose
   if (n == 0) return 0;
   (void)hipSetDevice(h->cfg.device);
   const int N = h->N, pd = h->pd, d = h->d, N2 = N + n, stride2 = N2 + 1;
-  Scratch sc;
-  HIPCHK(sc.a.reserve((size_t)n * pd * sizeof(double)));
-  HIPCHK(sc.b.reserve((size_t)n * d * sizeof(double)));
-  DevBuf pose2, vel2;
-  hipError_t e = pose2.reserve((size_t)pd * stride2 * sizeof(double));
-  if (e == hipSuccess) e = vel2.reserve((size_t)d * stride2 * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpyAsync(sc.a.p, pose, (size_t)n * pd * sizeof(double), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(sc.b.p, vel, (size_t)n * d * sizeof(double), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(pose2.p, 0, (size_t)pd * stride2 * sizeof(double), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(vel2.p, 0, (size_t)d * stride2 * sizeof(double), h->stream);
-  if (e == hipSuccess) {
-    k_move_states<<<dim3(nblocks(pd * N, 256)), dim3(256), 0, h->stream>>>(h->pose.as<double>(), h->stride, 0, pose2.as<double>(), stride2, 0, N, pd);
-    k_move_states<<<dim3(nblocks(d * N, 256)), dim3(256), 0, h->stream>>>(h->vel.as<double>(), h->stride, 0, vel2.as<double>(), stride2, 0, N, d);
-    k_scatter_states<<<dim3(nblocks(pd * n, 256)), dim3(256), 0, h->stream>>>(sc.a.as<double>(), pose2.as<double>(), stride2, N, n, pd);
-    k_scatter_states<<<dim3(nblocks(d * n, 256)), dim3(256), 0, h->stream>>>(sc.b.as<double>(), vel2.as<double>(), stride2, N, n, d);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) { pose2.release(); vel2.release(); return fail(h, GPSLAM_E_HIP, hipGetErrorString(e)); }
-  h->pose.release(); h->vel.release();
-  h->pose = pose2; h->vel = vel2;
+  DevBuf in_pose, in_vel, pose2, vel2;   // (a failure below frees all four on the way out)
+  HIPCHK(in_pose.reserve((size_t)n * pd * sizeof(double)));
+  HIPCHK(in_vel.reserve((size_t)n * d * sizeof(double)));
+  HIPCHK(pose2.reserve((size_t)pd * stride2 * sizeof(double)));
+  HIPCHK(vel2.reserve((size_t)d * stride2 * sizeof(double)));
+  HIPCHK(hipMemcpyAsync(in_pose.p, pose, (size_t)n * pd * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(in_vel.p, vel, (size_t)n * d * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(pose2.p, 0, (size_t)pd * stride2 * sizeof(double), h->stream));
+  HIPCHK(hipMemsetAsync(vel2.p, 0, (size_t)d * stride2 * sizeof(double), h->stream));
+  k_move_states<<<dim3(nblocks(pd * N, 256)), dim3(256), 0, h->stream>>>(h->pose.as<double>(), h->stride, 0, pose2.as<double>(), stride2, 0, N, pd);
+  k_move_states<<<dim3(nblocks(d * N, 256)), dim3(256), 0, h->stream>>>(h->vel.as<double>(), h->stride, 0, vel2.as<double>(), stride2, 0, N, d);
+  k_scatter_states<<<dim3(nblocks(pd * n, 256)), dim3(256), 0, h->stream>>>(in_pose.as<double>(), pose2.as<double>(), stride2, N, n, pd);
+  k_scatter_states<<<dim3(nblocks(d * n, 256)), dim3(256), 0, h->stream>>>(in_vel.as<double>(), vel2.as<double>(), stride2, N, n, d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->pose = std::move(pose2);
+  h->vel = std::move(vel2);
   h->N = N2; h->stride = stride2;
   h->compiled = false;
-  h->marg_ok = false;
+  h->mg.invalidate();
   return 0;
 }
 

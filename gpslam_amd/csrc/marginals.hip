@@ -17,9 +17,10 @@
 //   (f) Sigma_{a,b} of any two states and the closure gate over it walk what (b), (c) leave (marginals_pairs.hip), from a copy of Y
 //       taken behind k_mg_finish when gpslam_hip_marginals_keep_pair_terms asked for it.
 // fp64 only; no atomics, every sum in a fixed order: two calls give bit-identical blocks.
-#include "api_common.hpp"
-#include "marginals_clo.hpp"
-#include "marginals_fs.hpp"
+// What the call leaves is h->mg (marginals.hpp: struct Marginals, the levels' layout MgLevels, the shapes of Z and G); this file has the
+// getters' guard marginals_getter_check and the pivot epilogue marginals_finish_flag that marginals_fs.hip ends with as well; the
+// device helpers shared with the other three units (mg_set, mg_pads) are marginals_dev.hpp's.
+#include "marginals_dev.hpp"
 
 namespace impl64 {
 #include "api_decl.inc"
@@ -30,27 +31,8 @@ namespace impl32 {
 
 namespace {
 
-constexpr int kMgChunk = 16;           // states per chunk at every level (the first one is the chunk's separator)
 constexpr int kMgMaxCols = kMaxRhs - 1;   // landmark coordinates + closure rows (<= 27)
 
-// dst[r][c] = f(r, c) for a B x B row-major matrix in LDS, one wave: every lane evaluates its entries first, then writes them,
-// so f may read dst
-template <int B, typename F> __device__ inline void mg_set(double *dst, F f) {
-  constexpr int NE = (B * B + 63) / 64;
-  double v[NE];
-#pragma unroll
-  for (int t = 0; t < NE; t++) {
-    const int e = threadIdx.x + 64 * t;
-    v[t] = (e < B * B) ? f(e / B, e % B) : 0.0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int t = 0; t < NE; t++) {
-    const int e = threadIdx.x + 64 * t;
-    if (e < B * B) dst[e] = v[t];
-  }
-  __syncthreads();
-}
 template <int B> __device__ inline void mg_store(double *g, const double *l) {
   for (int e = threadIdx.x; e < B * B; e += 64) g[e] = l[e];
 }
@@ -353,14 +335,14 @@ int mg_refuse(gpslam_hip_handle *h) {
   if (h->cfg.precision == GPSLAM_FP32) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: fp32 handles are not supported (fp64 only)");
   if (sharded(h)) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: sharded handles are not supported");
   if (h->fs.active && h->fs.split) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: split pieces are not supported");
-  if (h->fs.active && !h->mg_on_segments) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: the segmented landmark path is not supported");
-  if (h->clo.P > 1 && !h->mg_keep_z)
+  if (h->fs.active && !h->mg.on_segments) return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: the segmented landmark path is not supported");
+  if (h->clo.P > 1 && !h->mg.keep_z)
     return fail(h, GPSLAM_E_UNSUPPORTED, "marginals: loop closures in more than one column pass (set_closure_passes) are not supported: Z = H0^-1 U^T is not kept at every state (unless gpslam_hip_marginals_keep_closure_columns asks for it)");
   return 0;
 }
 
 int mg_stale(gpslam_hip_handle *h) {
-  if (!h->marg_ok) return fail(h, GPSLAM_E_INVALID, "marginals are stale: call gpslam_hip_marginals() after the last change of states, landmarks, factors or Qc");
+  if (!h->mg.ok) return fail(h, GPSLAM_E_INVALID, "marginals are stale: call gpslam_hip_marginals() after the last change of states, landmarks, factors or Qc");
   return 0;
 }
 
@@ -371,32 +353,34 @@ int marginals_getter_check(gpslam_hip_handle *h) {
   return rc ? rc : mg_stale(h);
 }
 
-void marginals_release(gpslam_hip_handle *h) {
-  for (DevBuf *b : {&h->mg_fac, &h->mg_S, &h->mg_Sn, &h->mg_up, &h->mg_K, &h->mg_Slm, &h->mg_Sxl, &h->mg_Z, &h->mg_Minv, &h->mg_Y}) b->release();
-  marginals_fs_release(h);
-  h->marg_ok = false;
-  h->mg_pairs_ok = false;
-  h->marg_N = 0;
+int marginals_finish_flag(gpslam_hip_handle *h) {
+  int flag = 0;
+  HIPCHK(hipMemcpyAsync(&flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (flag) return fail(h, GPSLAM_E_NOT_SPD, "marginals: non-positive pivot (indeterminate system: is the graph anchored?)");
+  h->mg.ok = true;
+  return 0;
 }
 
 extern "C" {
 
 int gpslam_hip_marginals_keep_closure_columns(gpslam_hip_handle *h, int32_t enable) {
   if (!h) return GPSLAM_E_INVALID;
-  h->marg_ok = false;
-  h->mg_keep_z = enable != 0;
-  if (!h->mg_keep_z) {
-    h->mg_Z.release();
-    h->mg_Minv.release();
+  h->mg.invalidate();
+  h->mg.keep_z = enable != 0;
+  if (!h->mg.keep_z) {   // freed now: Z is the marginals' largest buffer (N b x nc) and nothing reads it without the opt-in
+    h->mg.Z.release();
+    h->mg.Minv.release();
   }
   return 0;
 }
 
 int gpslam_hip_marginals_on_segments(gpslam_hip_handle *h, int32_t enable) {
   if (!h) return GPSLAM_E_INVALID;
-  h->marg_ok = false;
-  h->mg_on_segments = enable != 0;
-  if (!h->mg_on_segments) marginals_fs_release(h);
+  h->mg.invalidate();
+  h->mg.on_segments = enable != 0;
+  if (!h->mg.on_segments)   // freed now: G is N b x NCP, and nothing reads the three without the opt-in
+    for (DevBuf *b : {&h->mg.fsD, &h->mg.fsP, &h->mg.G}) b->release();
   return 0;
 }
 
@@ -405,54 +389,45 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
   if (rc) return rc;
   if ((rc = mg_refuse(h))) return rc;
   (void)hipSetDevice(h->cfg.device);
-  h->marg_ok = false;
-  h->mg_pairs_ok = false;
+  h->mg.invalidate();
   if (h->fs.active) return marginals_fs(h);
   const int N = h->N, B = h->b, BB = B * B, R = h->R, m = R - 1;
-  // levels: n_0 = N, n_{l+1} = ceil(n_l / kMgChunk), down to one block; the levels above 0 live in one buffer
-  std::vector<int> n{N};
-  while (n.back() > 1) n.push_back(nblocks(n.back(), kMgChunk));
-  const int top = (int)n.size() - 1;
-  std::vector<size_t> off(n.size() + 1, 0);   // per level >= 1: D, O, add, fac (3), Sd, Sn = 8 B^2 per block
-  for (int l = 1; l <= top; l++) off[l + 1] = off[l] + (size_t)8 * BB * n[l];
-  if (h->marg_N != N) marginals_release(h);
-  HIPCHK(h->mg_fac.reserve((size_t)N * 3 * BB * sizeof(double)));
-  HIPCHK(h->mg_S.reserve((size_t)N * BB * sizeof(double)));
-  HIPCHK(h->mg_Sn.reserve((size_t)N * BB * sizeof(double)));
-  HIPCHK(h->mg_up.reserve(std::max<size_t>(off[top + 1], 1) * sizeof(double)));
-  HIPCHK(h->mg_K.reserve((size_t)std::max(m * m, 1) * sizeof(double)));
-  HIPCHK(h->mg_Slm.reserve((size_t)std::max(h->nl * h->nl, 1) * sizeof(double)));
-  HIPCHK(h->mg_Sxl.reserve((size_t)std::max(N * B * h->nl, 1) * sizeof(double)));
+  const MgLevels lv(N, B);
+  const int top = lv.top;
+  h->mg.fit(N);   // (another N than the last call's: its buffers are freed first, not grown)
+  HIPCHK(h->mg.fac.reserve((size_t)N * 3 * BB * sizeof(double)));
+  HIPCHK(h->mg.S.reserve((size_t)N * BB * sizeof(double)));
+  HIPCHK(h->mg.Sn.reserve((size_t)N * BB * sizeof(double)));
+  HIPCHK(h->mg.up.reserve(std::max<size_t>(lv.total(), 1) * sizeof(double)));
+  HIPCHK(h->mg.K.reserve((size_t)std::max(m * m, 1) * sizeof(double)));
+  HIPCHK(h->mg.Slm.reserve((size_t)std::max(h->nl * h->nl, 1) * sizeof(double)));
+  HIPCHK(h->mg.Sxl.reserve((size_t)std::max(N * B * h->nl, 1) * sizeof(double)));
   const bool passes = h->clo.P > 1;     // (mg_refuse: only with gpslam_hip_marginals_keep_closure_columns)
   const int ldz = mg_ldz(h->clo.nc);
   if (passes) {
     const size_t zbytes = mg_zrows(N, B) * ldz * sizeof(double);
-    HIPCHK(h->mg_Z.reserve(zbytes));
-    HIPCHK(h->mg_Minv.reserve((size_t)ldz * ldz * sizeof(double)));
-    HIPCHK(hipMemsetAsync(h->mg_Z.p, 0, zbytes, h->stream));   // the padding rows and columns: k_mg_clo_finish reads them
+    HIPCHK(h->mg.Z.reserve(zbytes));
+    HIPCHK(h->mg.Minv.reserve((size_t)ldz * ldz * sizeof(double)));
+    HIPCHK(hipMemsetAsync(h->mg.Z.p, 0, zbytes, h->stream));   // the padding rows and columns: k_mg_clo_finish reads them
   }
-  h->marg_N = N;
   HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
   if ((rc = impl64::marginals_assemble(h))) return rc;
   const double *blk = h->lv[0].blk.as<double>();
   const int BS = 2 * BB + B * R;
   auto level = [&](int l) {
     MgLevel a;
-    double *u = h->mg_up.as<double>() + off[l];
+    double *up = h->mg.up.as<double>();
     if (l == 0) {
       a.D = blk; a.O = blk + BB; a.add = nullptr; a.stride = BS;
-      a.fac = h->mg_fac.as<double>(); a.Sd = h->mg_S.as<double>(); a.Sn = h->mg_Sn.as<double>();
+      a.fac = h->mg.fac.as<double>(); a.Sd = h->mg.S.as<double>(); a.Sn = h->mg.Sn.as<double>();
     } else {
-      const size_t nb = (size_t)n[l] * BB;
-      a.D = u; a.O = u + nb; a.add = u + 2 * nb; a.stride = BB;
-      a.fac = u + 3 * nb; a.Sd = u + 6 * nb; a.Sn = u + 7 * nb;
+      a.D = up + lv.D(l); a.O = up + lv.O(l); a.add = up + lv.add(l); a.stride = BB;
+      a.fac = up + lv.fac(l); a.Sd = up + lv.Sd(l); a.Sn = up + lv.Sn(l);
     }
-    a.n = n[l];
+    a.n = lv.n[l];
     a.upD = a.upO = a.upAdd = a.Sd; a.upSd = a.upSn = a.Sd;   // (unused on the top level)
     if (l < top) {
-      double *v = h->mg_up.as<double>() + off[l + 1];
-      const size_t nb = (size_t)n[l + 1] * BB;
-      a.upD = v; a.upO = v + nb; a.upAdd = v + 2 * nb; a.upSd = v + 6 * nb; a.upSn = v + 7 * nb;
+      a.upD = up + lv.D(l + 1); a.upO = up + lv.O(l + 1); a.upAdd = up + lv.add(l + 1); a.upSd = up + lv.Sd(l + 1); a.upSn = up + lv.Sn(l + 1);
     }
     a.flag = h->flag.as<int>();
     return a;
@@ -461,17 +436,17 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
   for (int l = 0; l < top; l++) {
     const MgLevel a = level(l);
     HIPCHK(hipMemsetAsync(a.upAdd, 0, (size_t)BB * sizeof(double), h->stream));
-    dispatch_b(B, [&](auto tag) { k_mg_forward<decltype(tag)::value><<<dim3(n[l + 1]), dim3(64), 0, h->stream>>>(a); });
+    dispatch_b(B, [&](auto tag) { k_mg_forward<decltype(tag)::value><<<dim3(lv.n[l + 1]), dim3(64), 0, h->stream>>>(a); });
   }
   dispatch_b(B, [&](auto tag) { k_mg_top<decltype(tag)::value><<<dim3(1), dim3(64), 0, h->stream>>>(level(top)); });
   for (int l = top - 1; l >= 0; l--) {
     const MgLevel a = level(l);
-    dispatch_b(B, [&](auto tag) { k_mg_backward<decltype(tag)::value><<<dim3(n[l + 1]), dim3(64), 0, h->stream>>>(a); });
+    dispatch_b(B, [&](auto tag) { k_mg_backward<decltype(tag)::value><<<dim3(lv.n[l + 1]), dim3(64), 0, h->stream>>>(a); });
   }
   HIPCHK(hipGetLastError());
   // (c) landmarks and closures: Y = [W | Z] and S from the solver's own right-hand sides, then K
   if (m > 0) {
-    // closures in column passes: Z slice by slice into mg_Z, then - Z M^-1 Z^T on its own; what is left for k_mg_core and
+    // closures in column passes: Z slice by slice into mg.Z, then - Z M^-1 Z^T on its own; what is left for k_mg_core and
     // k_mg_finish is the landmark term (W in the leading columns of the level-0 solution, K = S^-1: no closure reaches k_mg_core)
     if ((rc = impl64::marginals_border(h))) return rc;
     if (passes && (rc = marginals_closure_term(h))) return rc;
@@ -479,28 +454,23 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
       MgCore c;
       c.S = h->lm_S.as<double>(); c.cloA = h->clo.A.as<double>(); c.first = h->clo.fac.d_idx.as<int>(); c.second = h->clo.d_second.as<int>();
       c.x = h->lv[0].x.as<double>(); c.nl = h->nl; c.nclo = passes ? 0 : h->clo.n; c.R = R; c.B = B;
-      c.K = h->mg_K.as<double>(); c.Slm = h->mg_Slm.as<double>(); c.flag = h->flag.as<int>();
+      c.K = h->mg.K.as<double>(); c.Slm = h->mg.Slm.as<double>(); c.flag = h->flag.as<int>();
       dispatch_b(B, [&](auto tag) { k_mg_core<decltype(tag)::value / 2><<<dim3(1), dim3(64), 0, h->stream>>>(c); });
     }
   }
-  const bool pad = h->mf == ROT3_BIAS;
+  const MgPads pads = mg_pads(h);
   const int mfin = passes ? h->nl : m;   // the columns k_mg_finish adds: [W | Z], or W alone behind k_mg_clo_finish
-  if (mfin > 0 || pad) {
+  if (mfin > 0 || pads.npad > 0) {
     MgFinish f;
-    f.Sd = h->mg_S.as<double>(); f.Sn = h->mg_Sn.as<double>(); f.Sxl = h->mg_Sxl.as<double>();
-    f.x = h->lv[0].x.as<double>(); f.K = h->mg_K.as<double>();
+    f.Sd = h->mg.S.as<double>(); f.Sn = h->mg.Sn.as<double>(); f.Sxl = h->mg.Sxl.as<double>();
+    f.x = h->lv[0].x.as<double>(); f.K = h->mg.K.as<double>();
     f.N = N; f.R = R; f.m = mfin; f.nl = h->nl;
-    f.pad0 = pad ? 9 : 0; f.npad = pad ? 3 : 0;
+    f.pad0 = pads.pad0; f.npad = pads.npad;
     dispatch_b(B, [&](auto tag) { k_mg_finish<decltype(tag)::value><<<dim3(nblocks(N * B, 256)), dim3(256), 0, h->stream>>>(f); });
   }
   HIPCHK(hipGetLastError());
   if ((rc = marginals_pairs_keep(h))) return rc;   // (gpslam_hip_marginals_keep_pair_terms: Y before a later call rewrites it)
-  int flag = 0;
-  HIPCHK(hipMemcpyAsync(&flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (flag) return fail(h, GPSLAM_E_NOT_SPD, "marginals: non-positive pivot (indeterminate system: is the graph anchored?)");
-  h->marg_ok = true;
-  return 0;
+  return marginals_finish_flag(h);
 }
 
 int gpslam_hip_get_marginals(gpslam_hip_handle *h, int32_t first, int32_t count, double *S, double *S_next, double *S_lm,
@@ -514,11 +484,11 @@ int gpslam_hip_get_marginals(gpslam_hip_handle *h, int32_t first, int32_t count,
                 "gpslam_hip_get_landmark_marginals, gpslam_hip_get_state_landmark_marginals, gpslam_hip_get_landmark_pair_marginals");
   (void)hipSetDevice(h->cfg.device);
   const size_t BB = (size_t)h->b * h->b, nl = (size_t)h->nl;
-  if (S && count) HIPCHK(hipMemcpyAsync(S, h->mg_S.as<double>() + first * BB, count * BB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (S_next && count) HIPCHK(hipMemcpyAsync(S_next, h->mg_Sn.as<double>() + first * BB, count * BB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (S_lm && nl) HIPCHK(hipMemcpyAsync(S_lm, h->mg_Slm.p, nl * nl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (S && count) HIPCHK(hipMemcpyAsync(S, h->mg.S.as<double>() + first * BB, count * BB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (S_next && count) HIPCHK(hipMemcpyAsync(S_next, h->mg.Sn.as<double>() + first * BB, count * BB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (S_lm && nl) HIPCHK(hipMemcpyAsync(S_lm, h->mg.Slm.p, nl * nl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (S_x_lm && nl && count)
-    HIPCHK(hipMemcpyAsync(S_x_lm, h->mg_Sxl.as<double>() + (size_t)first * h->b * nl, (size_t)count * h->b * nl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(S_x_lm, h->mg.Sxl.as<double>() + (size_t)first * h->b * nl, (size_t)count * h->b * nl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -571,10 +541,7 @@ int gpslam_hip_interpolate_covariances(gpslam_hip_handle *h, int32_t count, cons
   }
   std::vector<int> li(left, left + count);
   std::vector<double> qc(h->Qc, h->Qc + d * d);
-  struct Scratch {
-    DevBuf left, coef, cg, qc, pose, H, out;
-    ~Scratch() { left.release(); coef.release(); cg.release(); qc.release(); pose.release(); H.release(); out.release(); }
-  } sc;
+  struct { DevBuf left, coef, cg, qc, pose, H, out; } sc;   // this call's own buffers
   if ((rc = upload(h, sc.left, li)) || (rc = upload(h, sc.coef, coef)) || (rc = upload(h, sc.cg, cg)) || (rc = upload(h, sc.qc, qc))) return rc;
   HIPCHK(sc.pose.reserve((size_t)count * pd * sizeof(double)));
   HIPCHK(sc.H.reserve((size_t)count * 4 * d * d * sizeof(double)));
@@ -588,7 +555,7 @@ int gpslam_hip_interpolate_covariances(gpslam_hip_handle *h, int32_t count, cons
   });
   MgInterp u;
   u.H = sc.H.as<double>(); u.cg = sc.cg.as<double>(); u.Qc = sc.qc.as<double>(); u.left = sc.left.as<int>();
-  u.Sd = h->mg_S.as<double>(); u.Sn = h->mg_Sn.as<double>(); u.count = count;
+  u.Sd = h->mg.S.as<double>(); u.Sn = h->mg.Sn.as<double>(); u.count = count;
   u.nq = h->mf == ROT3_BIAS ? 3 : d;   // (the bias is held over the interval, not interpolated)
   u.out = sc.out.as<double>();
   dispatch_b(h->b, [&](auto tag) { k_mg_interp<decltype(tag)::value><<<dim3(nblocks(count, 128)), dim3(128), 0, h->stream>>>(u); });

@@ -2,15 +2,17 @@
 // (gpslam_hip_marginals_keep_closure_columns; marginals.hip (c), api_impl.inc launch_solve_passes with keep_z): the closure term
 //   Sigma_{i,i} -= Z_i M^-1 Z_i^T,   Sigma_{i,i+1} -= Z_i M^-1 Z_{i+1}^T,   M = I + 1/2 (U Z + (U Z)^T),
 // with Z = A^-1 U^T kept at every state (k_mg_keep_z) and nc = closures * d up to kCloWideMax = 120.  A translation unit of its
-// own: the kernels of marginals.hip stay what they were, byte for byte.
-#include "api_common.hpp"
-#include "marginals_clo.hpp"
+// own: the kernels of marginals.hip stay what they were, byte for byte.  Z and M^-1 are h->mg.Z, h->mg.Minv; Z's shape (mg_ldz,
+// mg_zrows, kMgGroupRows) is marginals.hpp's, the kernel that fills it (k_mg_keep_z, launched by closures.hip) marginals_dev.hpp's.
+#include "marginals_dev.hpp"
 
 namespace {
 
 // M = I + 1/2 (U Z + (U Z)^T) from W = U [X | Z] exactly as k_clo_solve_wide forms it, inverted in place in dynamic LDS
-// (nc (nc + 1) + 2 nc doubles) by Gauss-Jordan steps without pivoting (mg_inverse's; a non-positive pivot raises the flag): one
-// workgroup of 1024 threads, every entry owned by one thread between two barriers.  Writes the symmetrised inverse, zero-padded to ldz x ldz.
+// (nc (nc + 1) + 2 nc doubles) by Gauss-Jordan steps without pivoting (a non-positive pivot raises the flag): one
+// workgroup of 1024 threads, every entry owned by one thread between two barriers.  The steps are marginals_fs.hip's mgf_gj_inverse with
+// the thread count a constant and the flag never null, written out: through the shared function (templated on the thread count,
+// the flag assumed non-null) the compiler schedules this kernel differently, and its bytes are kept.  Writes the symmetrised inverse, zero-padded to ldz x ldz.
 struct MgCloInv {
   const double *W;              // nc x ldw, U Z in columns nr .. nr + nc - 1
   int ldw, nr, nc, ldz;
@@ -145,18 +147,18 @@ template <int B> __global__ void __launch_bounds__(64 * kMgCloWaves) k_mg_clo_fi
 
 }  // namespace
 
-// behind the column passes of marginals_border (W = U [X | Z] in clo.W, Z in mg_Z) and in front of k_mg_finish: M^-1 into mg_Minv, then the term
+// behind the column passes of marginals_border (W = U [X | Z] in clo.W, Z in mg.Z) and in front of k_mg_finish: M^-1 into mg.Minv, then the term
 int marginals_closure_term(gpslam_hip_handle *h) {
   const int N = h->N, B = h->b, ldz = mg_ldz(h->clo.nc);
   MgCloInv ci;
   ci.W = h->clo.W.as<double>(); ci.ldw = clo_ldw(h); ci.nr = 1 + h->nl; ci.nc = h->clo.nc; ci.ldz = ldz;
-  ci.Minv = h->mg_Minv.as<double>(); ci.flag = h->flag.as<int>();
+  ci.Minv = h->mg.Minv.as<double>(); ci.flag = h->flag.as<int>();
   // (process-wide per kernel: always the size of the widest system, whatever this handle's)
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mg_clo_inverse), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)mg_clo_inverse_lds(kCloWideMax)));
   k_mg_clo_inverse<<<dim3(1), dim3(kMgInvThreads), mg_clo_inverse_lds(h->clo.nc), h->stream>>>(ci);
   MgCloFinish cf;
-  cf.Sd = h->mg_S.as<double>(); cf.Sn = h->mg_Sn.as<double>(); cf.Z = h->mg_Z.as<double>(); cf.Minv = h->mg_Minv.as<double>();
+  cf.Sd = h->mg.S.as<double>(); cf.Sn = h->mg.Sn.as<double>(); cf.Z = h->mg.Z.as<double>(); cf.Minv = h->mg.Minv.as<double>();
   cf.N = N; cf.ldz = ldz; cf.ngroups = (int)(((size_t)N * B + kMgGroupRows - 1) / kMgGroupRows);
   const int grid = std::min(nblocks(cf.ngroups, kMgCloWaves), 256);   // (M^-1 is staged once per workgroup: no more of them than CUs)
   hipError_t ea = hipSuccess;

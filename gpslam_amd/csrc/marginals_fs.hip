@@ -7,21 +7,21 @@
 //   (b) Sigma_FF = S^-1, blocks Sigma_{k,k} and Sigma_{k,k+1}: the top block's inverse (k_mg_fs_top), then the cyclic-reduction levels
 //       in reverse, one workgroup per eliminated block (k_mg_fs_level): with U = P S_ll + Q S_rl, V = P S_lr + Q S_rr,
 //           S_ml = -L_m^-T U,  S_mr = -L_m^-T V,  S_mm = (L_m^-T - S_ml P^T - S_mr Q^T) L_m^-1.
-//       Adjacent pairs live in one buffer indexed by the LINK of the pair (mg_fsP[lk] = Sigma_{left,right}): the pair (l, r) of the
+//       Adjacent pairs live in one buffer indexed by the LINK of the pair (mg.fsP[lk] = Sigma_{left,right}): the pair (l, r) of the
 //       level above is the link the elimination of m created, (l, m) and (m, r) are the links it consumed; links 0 .. K-2 are the
 //       chain's own, so the wanted Sigma_{k,k+1} end up in the first K - 1 blocks;
 //   (c) one backward walk per segment (k_mg_fs_walk): G_j = W_j^T (Y_j - E_j G_{j+1}) over Y in place (G = A_s^-1 H[I_s, B_s]; Y carries
 //       H's own sign, see k_fs_fat_assemble: "direct terms - Schur complements"), and Takahashi's recurrence for A_s^-1 beside it:
-//       Z_jj = W_j^T W_j + M_j Z_{j+1,j+1} M_j^T, Z_{j,j+1} = -M_j Z_{j+1,j+1}, M_j = W_j^T E_j, straight into mg_S / mg_Sn;
+//       Z_jj = W_j^T W_j + M_j Z_{j+1,j+1} M_j^T, Z_{j,j+1} = -M_j Z_{j+1,j+1}, M_j = W_j^T E_j, straight into mg.S / mg.Sn;
 //   (d) Sigma_ii += T_i G_i^T, Sigma_{i,i+1} += T_i G_{i+1}^T, T_i = G_i Sigma_BB(s) on v_mfma_f64_16x16x4_f64 (k_mg_fs_finish, the tiles of
 //       k_mg_clo_finish with a right operand per segment); the cut states and the two state pairs at every cut from Sigma_{i,F} = -T_i
 //       (k_mg_fs_cuts);
 //   (e) Sigma_{i,F} is not stored (N b x nl: 80 GB at config 4): the getters gather what they are asked for from G and Sigma_FF
 //       (k_mg_fs_gather).
 // fp64 only; no atomics, one owner per output entry, every sum in a fixed order: two calls give bit-identical blocks.
-// tests/marginals_segmented_model.py is the same algebra in numpy.
-#include "api_common.hpp"
-#include "marginals_fs.hpp"
+// tests/marginals_segmented_model.py is the same algebra in numpy.  What is kept is h->mg.fsD, fsP, G; the limits and shapes (kMgFsMaxNB,
+// mg_fs_grows, mg_fs_ldz, the gather modes) are marginals.hpp's; the call ends in marginals.hip's marginals_finish_flag.
+#include "marginals_dev.hpp"
 
 namespace impl64 {
 #include "api_decl.inc"
@@ -33,8 +33,9 @@ typedef double mgf_d4 __attribute__((ext_vector_type(4)));
 typedef double mgf_d2 __attribute__((ext_vector_type(2)));
 
 // In-place Gauss-Jordan inverse without pivoting of the n x n matrix S (row stride ls, LDS), the whole workgroup: every entry owned
-// by one thread between two barriers (k_mg_clo_inverse's step).  The pivots of an SPD matrix are its leading Schur complements (a
-// non-positive one raises the flag); a lower-triangular matrix stays lower triangular and its pivots are its diagonal.
+// by one thread between two barriers.  The pivots of an SPD matrix are its leading Schur complements (a non-positive one raises the
+// flag); a lower-triangular matrix stays lower triangular and its pivots are its diagonal.  (k_mg_clo_inverse of marginals_clo.hip
+// has the same steps written out for its constant thread count: see there.)
 __device__ inline void mgf_gj_inverse(double *S, int n, int ls, double *colk, double *rowk, int *flag) {
   const int tid = threadIdx.x, nt = blockDim.x;
   for (int k = 0; k < n; k++) {
@@ -194,7 +195,7 @@ struct MgFsSeg {
   const int *cuts;
   const double *fac;            // N x 2 B^2: [W | E]
   double *G;                    // Y on entry of the walk, G behind it: rows i B + r of NCP doubles
-  double *Sd, *Sn;              // mg_S, mg_Sn
+  double *Sd, *Sn;              // mg.S, mg.Sn
   const double *SD, *SP;
   int N, K, NB, NCP;
   int pad0, npad;
@@ -476,10 +477,6 @@ __global__ void __launch_bounds__(256) k_mg_fs_gather(MgFsGather g) {
 
 }  // namespace
 
-void marginals_fs_release(gpslam_hip_handle *h) {
-  for (DevBuf *b : {&h->mg_fsD, &h->mg_fsP, &h->mg_G}) b->release();
-}
-
 int marginals_fs(gpslam_hip_handle *h) {
   FatSepPlan &p = h->fs;
   const int N = h->N, B = h->b, BB = B * B, K = p.K, NB = p.NB, NCP = p.NCP;
@@ -488,24 +485,23 @@ int marginals_fs(gpslam_hip_handle *h) {
     snprintf(msg, sizeof msg, "marginals on the segmented landmark path: fat blocks of NB = %d columns are wider than the limit of %d", NB, kMgFsMaxNB);
     return fail(h, GPSLAM_E_UNSUPPORTED, msg);
   }
-  if (h->marg_N != N) marginals_release(h);
+  h->mg.fit(N);
   const size_t NB2 = (size_t)NB * NB, gbytes = mg_fs_grows(N, B) * NCP * sizeof(double);
-  HIPCHK(h->mg_S.reserve((size_t)N * BB * sizeof(double)));
-  HIPCHK(h->mg_Sn.reserve((size_t)N * BB * sizeof(double)));
-  HIPCHK(h->mg_fsD.reserve((size_t)K * NB2 * sizeof(double)));
-  HIPCHK(h->mg_fsP.reserve((size_t)p.nlinks * NB2 * sizeof(double)));
-  HIPCHK(h->mg_G.reserve(gbytes));
-  h->marg_N = N;
+  HIPCHK(h->mg.S.reserve((size_t)N * BB * sizeof(double)));
+  HIPCHK(h->mg.Sn.reserve((size_t)N * BB * sizeof(double)));
+  HIPCHK(h->mg.fsD.reserve((size_t)K * NB2 * sizeof(double)));
+  HIPCHK(h->mg.fsP.reserve((size_t)p.nlinks * NB2 * sizeof(double)));
+  HIPCHK(h->mg.G.reserve(gbytes));
   hipStream_t st = h->stream;
   HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), st));
   // Y is zero wherever the sweep does not write (columns before their first right-hand side, padding, the cut states' rows); G is not
-  HIPCHK(hipMemsetAsync(h->mg_G.p, 0, gbytes, st));
+  HIPCHK(hipMemsetAsync(h->mg.G.p, 0, gbytes, st));
   int rc;
   if ((rc = impl64::marginals_assemble(h))) return rc;
-  if ((rc = impl64::marginals_fs_forward(h, h->mg_G.p))) return rc;
+  if ((rc = impl64::marginals_fs_forward(h, h->mg.G.p))) return rc;
   MgFsChain c;
   c.Dfat = p.Dfat.as<double>(); c.link = p.link.as<double>(); c.Qbuf = p.Qbuf.as<double>();
-  c.SD = h->mg_fsD.as<double>(); c.SP = h->mg_fsP.as<double>(); c.NB = NB; c.flag = h->flag.as<int>();
+  c.SD = h->mg.fsD.as<double>(); c.SP = h->mg.fsP.as<double>(); c.NB = NB; c.flag = h->flag.as<int>();
   // (process-wide per kernel: always the size of the widest block, whatever this handle's)
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mg_fs_level), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mg_fs_level_lds(kMgFsMaxNB)));
   k_mg_fs_top<<<dim3(1), dim3(kMgFsThreads), mg_fs_top_lds(NB), st>>>(c, p.top);
@@ -518,11 +514,11 @@ int marginals_fs(gpslam_hip_handle *h) {
   }
   HIPCHK(hipGetLastError());
   MgFsSeg s;
-  s.cuts = p.d_cuts.as<int>(); s.fac = p.fac.as<double>(); s.G = h->mg_G.as<double>();
-  s.Sd = h->mg_S.as<double>(); s.Sn = h->mg_Sn.as<double>(); s.SD = c.SD; s.SP = c.SP;
+  s.cuts = p.d_cuts.as<int>(); s.fac = p.fac.as<double>(); s.G = h->mg.G.as<double>();
+  s.Sd = h->mg.S.as<double>(); s.Sn = h->mg.Sn.as<double>(); s.SD = c.SD; s.SP = c.SP;
   s.N = N; s.K = K; s.NB = NB; s.NCP = NCP;
-  const bool pad = h->mf == ROT3_BIAS;
-  s.pad0 = pad ? 9 : 0; s.npad = pad ? 3 : 0;
+  const MgPads pads = mg_pads(h);
+  s.pad0 = pads.pad0; s.npad = pads.npad;
   const int nseg = K - 1, walk_threads = (NCP + 63) / 64 * 64, ldz = mg_fs_ldz(NB);
   hipError_t ea = hipSuccess;
   dispatch_b(B, [&](auto tag) {
@@ -535,16 +531,11 @@ int marginals_fs(gpslam_hip_handle *h) {
       k_mg_fs_finish<BV><<<dim3(nseg), dim3(64 * kMgFsWaves), mg_fs_finish_lds(ldz), st>>>(s);
     }
     k_mg_fs_cuts<BV><<<dim3(K), dim3(64), 0, st>>>(s);
-    if (pad) k_mg_fs_pads<BV><<<dim3((unsigned)(((size_t)N * BB + 255) / 256)), dim3(256), 0, st>>>(s);
+    if (pads.npad > 0) k_mg_fs_pads<BV><<<dim3((unsigned)(((size_t)N * BB + 255) / 256)), dim3(256), 0, st>>>(s);
   });
   HIPCHK(ea);
   HIPCHK(hipGetLastError());
-  int flag = 0;
-  HIPCHK(hipMemcpyAsync(&flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (flag) return fail(h, GPSLAM_E_NOT_SPD, "marginals: non-positive pivot (indeterminate system: is the graph anchored?)");
-  h->marg_ok = true;
-  return 0;
+  return marginals_finish_flag(h);
 }
 
 // the three landmark getters (marginals.hip has checked refusals, staleness and pointers)
@@ -573,20 +564,16 @@ int marginals_fs_gather(gpslam_hip_handle *h, int mode, int32_t count, const int
     }
     if (!ok) return fail(h, GPSLAM_E_INVALID, msg);
   }
-  struct Scratch {
-    DevBuf a, b, out;
-    ~Scratch() { a.release(); b.release(); out.release(); }
-  } sc;
+  struct { DevBuf a, b, out; } sc;   // this call's own buffers
   int rc;
   std::vector<int> va(a, a + count), vb(b, b + count);
   if ((rc = upload(h, sc.a, va)) || (rc = upload(h, sc.b, vb))) return rc;
   MgFsGather g;
   g.mode = mode; g.dense = seg ? 0 : 1; g.count = count; g.B = h->b; g.ld = h->ld; g.nl = h->nl; g.NB = p.NB; g.NCP = p.NCP;
   g.a = sc.a.as<int>(); g.b = sc.b.as<int>(); g.segid = p.d_segid.as<int>(); g.lm_fat = p.d_lm_fat.as<int>(); g.lm_slot = p.d_lm_slot.as<int>();
-  g.SD = h->mg_fsD.as<double>(); g.SP = h->mg_fsP.as<double>(); g.G = h->mg_G.as<double>();
-  g.Slm = h->mg_Slm.as<double>(); g.Sxl = h->mg_Sxl.as<double>();
-  const bool pad = h->mf == ROT3_BIAS;
-  g.pad0 = pad ? 9 : 0; g.npad = pad ? 3 : 0;
+  g.SD = h->mg.fsD.as<double>(); g.SP = h->mg.fsP.as<double>(); g.G = h->mg.G.as<double>();
+  g.Slm = h->mg.Slm.as<double>(); g.Sxl = h->mg.Sxl.as<double>();
+  g.pad0 = mg_pads(h).pad0; g.npad = mg_pads(h).npad;
   const size_t total = (size_t)count * (state ? h->b : h->ld) * h->ld;
   HIPCHK(sc.out.reserve(total * sizeof(double)));
   g.out = sc.out.as<double>();

@@ -5,7 +5,7 @@
 //   Sigma_xx = A^-1 + (low-rank term), A the block-tridiagonal chain part, so Sigma_{a,b} = A^-1_{a,b} + the same term between rows a, b.
 //
 //   (a) A^-1_{a,b} through the hierarchy of the selected inversion (k_mg_pair, one wave per pair).  The records [P_j^-1 | U_j | V_j] of
-//       mg_fac (level 0) and mg_up (the levels above), with x_j = P_j^-1 r_j - U_j x_{j+1} - V_j x_s, are a block L D L^T of A in the
+//       mg.fac (level 0) and mg.up (the levels above), with x_j = P_j^-1 r_j - U_j x_{j+1} - V_j x_s, are a block L D L^T of A in the
 //       elimination order, and Sigma_top (the top level's one block) closes it.  Hence
 //           A^-1_{a,b} = (L^-1 E_a)^T D^-1 (L^-1 E_b) = sum_i (r^a_i)^T P_i^-1 r^b_i + (r^a_top)^T Sigma_top r^b_top,
 //       r^a, r^b the forward sweeps of the identity block at a and at b:  r_{j+1} -= U_j^T r_j,  r_s -= V_j^T r_j  (the last interior's
@@ -15,38 +15,18 @@
 //       products per interior both sides visit and 2 per interior one side visits -- at most about 6 * 15 per level, whatever |a - b|.
 //       Every address follows from the indices, so the next interior's record is requested into registers before the current one's
 //       arithmetic starts (as k_head_schur does).
-//   (b) the low-rank term and the output rules (k_mg_pair_finish, a thread per pair and row): single pass + Y_a K Y_b^T with mg_K;
-//       column passes + W_a S^-1 W_b^T - Z_a M^-1 Z_b^T with mg_K (= S^-1 there), mg_Z, mg_Minv.  Y = [W | Z] is read from mg_Y, the
+//   (b) the low-rank term and the output rules (k_mg_pair_finish, a thread per pair and row): single pass + Y_a K Y_b^T with mg.K;
+//       column passes + W_a S^-1 W_b^T - Z_a M^-1 Z_b^T with mg.K (= S^-1 there), mg.Z, mg.Minv.  Y = [W | Z] is read from mg.Y, the
 //       copy gpslam_hip_marginals makes under gpslam_hip_marginals_keep_pair_terms (k_mg_keep_y): the solver's own buffer is rewritten
-//       by later calls.  a == b and |a - b| == 1 are copies of mg_S / mg_Sn; every other pair is computed for (min, max) by one code
+//       by later calls.  a == b and |a - b| == 1 are copies of mg.S / mg.Sn; every other pair is computed for (min, max) by one code
 //       path and transposed on output.
 //   (c) the gate (k_mg_gate, a thread per candidate): e, H1, H2 of BetweenFactor at the current states (PoseFactors::between, as
 //       k_clo_eval), P = diag(sigma^2) + [H1 H2] Sigma^{pp} [H1 H2]^T from the three pair blocks, chi2 = e^T P^-1 e by Cholesky.
 // fp64 only; no atomics, every sum in a fixed order: two calls give bit-identical blocks.  tests/marginals_pairs_model.py is (a), (b) in numpy.
-#include "api_common.hpp"
-#include "marginals_clo.hpp"
+// The levels are read through marginals.hpp's MgLevels, the one description of what gpslam_hip_marginals laid out; mg_set is marginals_dev.hpp's.
+#include "marginals_dev.hpp"
 
 namespace {
-
-constexpr int kMgChunk = 16;        // marginals.hip's: states per chunk at every level
-constexpr int kMgMaxLevels = 9;     // 16^8 > 2^31 states
-
-template <int B, typename F> __device__ inline void mp_set(double *dst, F f) {   // (marginals.hip's mg_set: f may read dst)
-  constexpr int NE = (B * B + 63) / 64;
-  double v[NE];
-#pragma unroll
-  for (int t = 0; t < NE; t++) {
-    const int e = threadIdx.x + 64 * t;
-    v[t] = (e < B * B) ? f(e / B, e % B) : 0.0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int t = 0; t < NE; t++) {
-    const int e = threadIdx.x + 64 * t;
-    if (e < B * B) dst[e] = v[t];
-  }
-  __syncthreads();
-}
 
 struct MgPair {
   const double *fac[kMgMaxLevels];   // per level below the top: n[l] x 3 B^2 records [P^-1 | U | V]
@@ -66,10 +46,10 @@ template <int B> __global__ void __launch_bounds__(64) k_mg_pair(MgPair a) {
   if (p[1] - p[0] < 2) return;
   bool has1[2] = {false, false};
   for (int s = 0; s < 2; s++) {
-    mp_set<B>(R0[s], [&](int r, int c) { return r == c ? 1.0 : 0.0; });
-    mp_set<B>(R1[s], [&](int, int) { return 0.0; });
+    mg_set<B>(R0[s], [&](int r, int c) { return r == c ? 1.0 : 0.0; });
+    mg_set<B>(R1[s], [&](int, int) { return 0.0; });
   }
-  mp_set<B>(Acc, [&](int, int) { return 0.0; });
+  mg_set<B>(Acc, [&](int, int) { return 0.0; });
   double pre[3][NE];
   auto request = [&](const double *f) {
 #pragma unroll
@@ -87,7 +67,7 @@ template <int B> __global__ void __launch_bounds__(64) k_mg_pair(MgPair a) {
       c[s] = p[s] / kMgChunk;
       e[s] = min(c[s] * kMgChunk + kMgChunk, n);
       start[s] = (p[s] == c[s] * kMgChunk && !has1[s]) ? e[s] : max(p[s], c[s] * kMgChunk + 1);   // a lone separator sweeps nothing
-      mp_set<B>(Sep[s], [&](int, int) { return 0.0; });
+      mg_set<B>(Sep[s], [&](int, int) { return 0.0; });
     }
     const bool same = c[0] == c[1];
     for (int g = 0; g < (same ? 1 : 2); g++) {
@@ -108,36 +88,36 @@ template <int B> __global__ void __launch_bounds__(64) k_mg_pair(MgPair a) {
           const double *add = (j == p[s]) ? R0[s] : (has1[s] && j == p[s] + 1) ? R1[s] : nullptr;
           if (!add) continue;
           const bool had = nz[s];
-          mp_set<B>(Cur[s], [&](int r, int cc) { return (had ? Cur[s][r * B + cc] : 0.0) + add[r * B + cc]; });
+          mg_set<B>(Cur[s], [&](int r, int cc) { return (had ? Cur[s][r * B + cc] : 0.0) + add[r * B + cc]; });
           nz[s] = true;
         }
         if (same && nz[0] && nz[1]) {
-          mp_set<B>(T, [&](int r, int cc) { double acc = 0.0; for (int q = 0; q < B; q++) acc += Pi[r * B + q] * Cur[1][q * B + cc]; return acc; });
-          mp_set<B>(Acc, [&](int r, int cc) { double acc = Acc[r * B + cc]; for (int q = 0; q < B; q++) acc += Cur[0][q * B + r] * T[q * B + cc]; return acc; });
+          mg_set<B>(T, [&](int r, int cc) { double acc = 0.0; for (int q = 0; q < B; q++) acc += Pi[r * B + q] * Cur[1][q * B + cc]; return acc; });
+          mg_set<B>(Acc, [&](int r, int cc) { double acc = Acc[r * B + cc]; for (int q = 0; q < B; q++) acc += Cur[0][q * B + r] * T[q * B + cc]; return acc; });
         }
         for (int s = s0; s <= s1; s++) {
           if (!nz[s]) continue;
-          mp_set<B>(Sep[s], [&](int r, int cc) { double acc = Sep[s][r * B + cc]; for (int q = 0; q < B; q++) acc -= V[q * B + r] * Cur[s][q * B + cc]; return acc; });
-          mp_set<B>(Cur[s], [&](int r, int cc) { double acc = 0.0; for (int q = 0; q < B; q++) acc -= U[q * B + r] * Cur[s][q * B + cc]; return acc; });
+          mg_set<B>(Sep[s], [&](int r, int cc) { double acc = Sep[s][r * B + cc]; for (int q = 0; q < B; q++) acc -= V[q * B + r] * Cur[s][q * B + cc]; return acc; });
+          mg_set<B>(Cur[s], [&](int r, int cc) { double acc = 0.0; for (int q = 0; q < B; q++) acc -= U[q * B + r] * Cur[s][q * B + cc]; return acc; });
         }
       }
     }
     for (int s = 0; s < 2; s++) {     // the next level's right-hand side: items c[s] (this chunk's separator) and c[s] + 1 (the right one)
       const bool own = p[s] == c[s] * kMgChunk, right = e[s] < n;
       const bool carry = right && nz[s], sepr = right && has1[s] && p[s] + 1 == e[s];
-      mp_set<B>(R0[s], [&](int r, int cc) { return Sep[s][r * B + cc] + (own ? R0[s][r * B + cc] : 0.0); });
-      mp_set<B>(R1[s], [&](int r, int cc) { return (carry ? Cur[s][r * B + cc] : 0.0) + (sepr ? R1[s][r * B + cc] : 0.0); });
+      mg_set<B>(R0[s], [&](int r, int cc) { return Sep[s][r * B + cc] + (own ? R0[s][r * B + cc] : 0.0); });
+      mg_set<B>(R1[s], [&](int r, int cc) { return (carry ? Cur[s][r * B + cc] : 0.0) + (sepr ? R1[s][r * B + cc] : 0.0); });
       p[s] = c[s];
       has1[s] = right;
     }
   }
-  mp_set<B>(Pi, [&](int r, int cc) { return a.Stop[r * B + cc]; });
-  mp_set<B>(T, [&](int r, int cc) { double acc = 0.0; for (int q = 0; q < B; q++) acc += Pi[r * B + q] * R0[1][q * B + cc]; return acc; });
-  mp_set<B>(Acc, [&](int r, int cc) { double acc = Acc[r * B + cc]; for (int q = 0; q < B; q++) acc += R0[0][q * B + r] * T[q * B + cc]; return acc; });
+  mg_set<B>(Pi, [&](int r, int cc) { return a.Stop[r * B + cc]; });
+  mg_set<B>(T, [&](int r, int cc) { double acc = 0.0; for (int q = 0; q < B; q++) acc += Pi[r * B + q] * R0[1][q * B + cc]; return acc; });
+  mg_set<B>(Acc, [&](int r, int cc) { double acc = Acc[r * B + cc]; for (int q = 0; q < B; q++) acc += R0[0][q * B + r] * T[q * B + cc]; return acc; });
   for (int q = threadIdx.x; q < BB; q += 64) a.out[(size_t)t * BB + q] = Acc[q];
 }
 
-// mg_Y[(i m + q) B + k] = x[(i R + 1 + q) B + k], q < m: the columns behind the update column of every state's level-0 solution
+// mg.Y[(i m + q) B + k] = x[(i R + 1 + q) B + k], q < m: the columns behind the update column of every state's level-0 solution
 __global__ void __launch_bounds__(256) k_mg_keep_y(const double *x, double *Y, int N, int R, int m, int B) {
   const int per = m * B;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -150,10 +130,10 @@ struct MgPairFinish {
   const double *chain;          // k_mg_pair's blocks
   const int *a, *b;
   int count, N;
-  const double *Sd, *Sn;        // mg_S, mg_Sn
-  const double *Y, *K;          // mg_Y (N x m x B), mg_K (m x m)
+  const double *Sd, *Sn;        // mg.S, mg.Sn
+  const double *Y, *K;          // mg.Y (N x m x B), mg.K (m x m)
   int m;
-  const double *Z, *Minv;       // column passes: mg_Z, mg_Minv, or null
+  const double *Z, *Minv;       // column passes: mg.Z, mg.Minv, or null
   int nc, ldz;
   int pad0, npad;
   double *out;                  // count x B^2: Sigma_{a[t], b[t]}
@@ -274,12 +254,7 @@ template <int MF> __global__ void __launch_bounds__(64) k_mg_gate(MgGate a) {
   a.chi2[f] = chi;
 }
 
-struct PairScratch {
-  DevBuf a, b, chain, out, meas, sig, err, P, chi2;
-  ~PairScratch() {
-    for (DevBuf *x : {&a, &b, &chain, &out, &meas, &sig, &err, &P, &chi2}) x->release();
-  }
-};
+struct PairScratch { DevBuf a, b, chain, out, meas, sig, err, P, chi2; };   // one getter call's own buffers
 
 int pairs_check(gpslam_hip_handle *h, const char *who) {
   int rc = marginals_getter_check(h);
@@ -288,7 +263,7 @@ int pairs_check(gpslam_hip_handle *h, const char *who) {
     h->err = std::string(who) + ": pairs of states on the segmented landmark path are not supported (the fat chain is not walked for a pair)";
     return GPSLAM_E_UNSUPPORTED;
   }
-  if (!h->mg_pairs_ok) {
+  if (!h->mg.pairs_ok) {
     h->err = std::string(who) + ": the handle has landmarks or closures and the last gpslam_hip_marginals() kept no copy of their columns: call "
              "gpslam_hip_marginals_keep_pair_terms(h, 1), then gpslam_hip_marginals() again";
     return GPSLAM_E_INVALID;
@@ -306,32 +281,26 @@ int pairs_on_device(gpslam_hip_handle *h, PairScratch &sc, const std::vector<int
   bool far = false;
   for (int t = 0; t < count && !far; t++) far = std::abs(a[t] - b[t]) > 1;
   if (far) {
-    // the levels as gpslam_hip_marginals laid them out: n_0 = N, n_{l+1} = ceil(n_l / 16); per level >= 1, 8 B^2 doubles per block in
-    // mg_up: D, O, add, fac (3), Sd, Sn
     MgPair p;
-    std::vector<int> n{N};
-    while (n.back() > 1) n.push_back(nblocks(n.back(), kMgChunk));
-    const int top = (int)n.size() - 1;
-    if (top >= kMgMaxLevels) return fail(h, GPSLAM_E_UNSUPPORTED, "pair marginals: too many levels");
-    size_t off = 0;
-    for (int l = 0; l <= top; l++) {
-      const double *u = h->mg_up.as<double>() + off;
-      if (l < top) { p.fac[l] = l == 0 ? h->mg_fac.as<double>() : u + (size_t)3 * n[l] * BB; p.n[l] = n[l]; }
-      else p.Stop = l == 0 ? h->mg_S.as<double>() : u + (size_t)6 * n[l] * BB;
-      if (l >= 1) off += (size_t)8 * BB * n[l];
+    const MgLevels lv(N, B);    // (as gpslam_hip_marginals laid them out)
+    const int top = lv.top;
+    const double *up = h->mg.up.as<double>();
+    for (int l = 0; l < kMgMaxLevels; l++) {
+      p.fac[l] = l >= top ? nullptr : l == 0 ? h->mg.fac.as<double>() : up + lv.fac(l);
+      p.n[l] = l < top ? lv.n[l] : 0;
     }
-    for (int l = top; l < kMgMaxLevels; l++) { p.fac[l] = nullptr; p.n[l] = 0; }
+    p.Stop = top == 0 ? h->mg.S.as<double>() : up + lv.Sd(top);
     p.top = top; p.a = sc.a.as<int>(); p.b = sc.b.as<int>(); p.count = count; p.out = sc.chain.as<double>();
     dispatch_b(B, [&](auto tag) { k_mg_pair<decltype(tag)::value><<<dim3(count), dim3(64), 0, h->stream>>>(p); });
   }
-  const bool passes = h->clo.P > 1, pad = h->mf == ROT3_BIAS;
+  const bool passes = h->clo.P > 1;
   MgPairFinish f;
   f.chain = sc.chain.as<double>(); f.a = sc.a.as<int>(); f.b = sc.b.as<int>(); f.count = count; f.N = N;
-  f.Sd = h->mg_S.as<double>(); f.Sn = h->mg_Sn.as<double>();
-  f.Y = h->mg_Y.as<double>(); f.K = h->mg_K.as<double>(); f.m = h->mg_Ym;
-  f.Z = passes ? h->mg_Z.as<double>() : nullptr; f.Minv = passes ? h->mg_Minv.as<double>() : nullptr;
+  f.Sd = h->mg.S.as<double>(); f.Sn = h->mg.Sn.as<double>();
+  f.Y = h->mg.Y.as<double>(); f.K = h->mg.K.as<double>(); f.m = h->mg.Ym;
+  f.Z = passes ? h->mg.Z.as<double>() : nullptr; f.Minv = passes ? h->mg.Minv.as<double>() : nullptr;
   f.nc = passes ? h->clo.nc : 0; f.ldz = passes ? mg_ldz(h->clo.nc) : 0;
-  f.pad0 = pad ? 9 : 0; f.npad = pad ? 3 : 0;
+  f.pad0 = mg_pads(h).pad0; f.npad = mg_pads(h).npad;
   f.out = sc.out.as<double>();
   dispatch_b(B, [&](auto tag) { k_mg_pair_finish<decltype(tag)::value><<<dim3(nblocks(count * B, 256)), dim3(256), 0, h->stream>>>(f); });
   HIPCHK(hipGetLastError());
@@ -342,18 +311,18 @@ int pairs_on_device(gpslam_hip_handle *h, PairScratch &sc, const std::vector<int
 
 int marginals_pairs_keep(gpslam_hip_handle *h) {
   const int m = h->R - 1;
-  h->mg_Ym = 0;
-  if (m == 0) { h->mg_pairs_ok = true; return 0; }     // no landmarks, no closures: nothing to copy
-  if (!h->mg_keep_pairs) return 0;
-  const int my = h->clo.P > 1 ? h->nl : m;             // column passes: W alone, Z is in mg_Z
+  h->mg.Ym = 0;
+  if (m == 0) { h->mg.pairs_ok = true; return 0; }     // no landmarks, no closures: nothing to copy
+  if (!h->mg.keep_pairs) return 0;
+  const int my = h->clo.P > 1 ? h->nl : m;             // column passes: W alone, Z is in mg.Z
   if (my > 0) {
-    HIPCHK(h->mg_Y.reserve((size_t)h->N * my * h->b * sizeof(double)));
+    HIPCHK(h->mg.Y.reserve((size_t)h->N * my * h->b * sizeof(double)));
     const size_t total = (size_t)h->N * my * h->b;
-    k_mg_keep_y<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream>>>(h->lv[0].x.as<double>(), h->mg_Y.as<double>(), h->N, h->R, my, h->b);
+    k_mg_keep_y<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream>>>(h->lv[0].x.as<double>(), h->mg.Y.as<double>(), h->N, h->R, my, h->b);
     HIPCHK(hipGetLastError());
   }
-  h->mg_Ym = my;
-  h->mg_pairs_ok = true;
+  h->mg.Ym = my;
+  h->mg.pairs_ok = true;
   return 0;
 }
 
@@ -361,10 +330,9 @@ extern "C" {
 
 int gpslam_hip_marginals_keep_pair_terms(gpslam_hip_handle *h, int32_t enable) {
   if (!h) return GPSLAM_E_INVALID;
-  h->marg_ok = false;
-  h->mg_pairs_ok = false;
-  h->mg_keep_pairs = enable != 0;
-  if (!h->mg_keep_pairs) h->mg_Y.release();
+  h->mg.invalidate();
+  h->mg.keep_pairs = enable != 0;
+  if (!h->mg.keep_pairs) h->mg.Y.release();   // freed now: N x m x b doubles that nothing reads without the opt-in
   return 0;
 }
 

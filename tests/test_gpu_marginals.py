@@ -6,6 +6,10 @@ O.Chain.normal_equations, which already hold the closures' diagonal blocks; the 
 the oracle's own BetweenFactor Jacobians, orc_between_factor).  The chain-length sweep and the closure test on LINEAR3 take H0 from
 the device's normal_equations -- the same assembly marginals() runs, pinned to the oracle by tests/test_gpu_parity.py -- and add
 J_c^T J_c, whose whitened rows are -I / sigma, I / sigma."""
+import ctypes as C
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -405,3 +409,187 @@ def test_sharded_handle_is_refused():
     p = S.linear_chain(50, D=3)
     with pytest.raises(gp.GpslamHipError, match=r"\(-5\).*sharded"):
         solver(p, force_sharded=True).marginals()
+
+
+# ---------------------------------------------------------------- staleness is total
+
+def _entry_points():
+    """every function include/gpslam_hip.h declares, without the gpslam_hip_ prefix"""
+    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "gpslam_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    return sorted(set(re.findall(r"\bgpslam_hip_([a-z0-9_]+)\s*\(", text)))
+
+
+def _small_graph():
+    """SE(2), 5 states, one landmark seen from the intervals behind states 1, 2, 3, one closure (1, 4): state 0 alone can be a head"""
+    p = _anchored_range_chain(5, L=1)
+    left = np.array([1, 2, 3], dtype=np.int32)
+    z = np.linalg.norm(p["landmark_truth"][0] - p["truth"][left, :2], axis=1)
+    p.update(range_left=left, range_lm=np.zeros(3, dtype=np.int32), range_z=z, range_sigma=np.full(3, 0.5), range_dt=np.full(3, 0.1),
+             range_tau=np.full(3, 0.05))
+    return S.add_loop_closures(p, [[1, 4]])
+
+
+def _small_handle(p):
+    dev = solver(p, landmark_dim=2)
+    dev.marginals_keep_pair_terms()
+    dev.marginals()
+    return dev
+
+
+def _raw(name, *args):
+    """the entry point itself, its status ignored: a local handle is refused by the calls of a caller-owned loop"""
+    return lambda d, p: getattr(d.lib, "gpslam_hip_" + name)(d._h, *args)
+
+
+# Column one: the entry points that change what Sigma depends on (states, landmarks, factors, noise models, Qc, the kept terms) -- after
+# any of them the getters answer "stale".  The value is the call on the small graph, or None where that graph cannot make it: factors
+# of other manifolds, and the phases of the sharded handle, of a split piece and of the segmented path's caller-owned loop
+# (iterate_phase1, fs_set_split, fs_phase1, fs_lm_trial_phase1).
+_EYE = lambda n: np.eye(n)[None]
+_CHANGES_SIGMA = {
+    "set_states": lambda d, p: d.set_states(*d.get_states()),
+    "set_halo_state": lambda d, p: d.set_halo_state(p["pose"][0], p["vel"][0]),
+    "set_landmarks": lambda d, p: d.set_landmarks(d.get_landmarks()),
+    "set_qc": lambda d, p: d.set_qc(p["qc"]),
+    "add_gp_priors": lambda d, p: d.add_gp_priors([0], [0.1]),
+    "add_gp_priors_qc": lambda d, p: d.add_gp_priors_qc([0], [0.1], p["qc"][None]),
+    "add_pose_priors": lambda d, p: d.add_pose_priors([2], p["pose"][2:3], np.ones((1, 3))),
+    "add_vel_priors": lambda d, p: d.add_vel_priors([2], p["vel"][2:3], np.ones((1, 3))),
+    "add_between": lambda d, p: d.add_between([0], p["between_meas"][:1], p["between_sig"][:1]),
+    "add_between_pairs": lambda d, p: d.add_between_pairs([2], [4], p["closure_meas"], p["closure_sig"]),
+    "add_landmark_priors": lambda d, p: d.add_landmark_priors([0], p["lprior"], p["lprior_sig"]),
+    "add_interp_range": lambda d, p: d.add_interp_range([2], [0], p["range_z"][1:2], [0.5], [0.1], [0.02]),
+    "add_range": lambda d, p: d.add_range([2], [0], p["range_z"][1:2], [0.5]),
+    "set_meas_covariance": lambda d, p: d.set_meas_covariance(gp.chain.MEAS_INTERP_RANGE, np.array([0.3])),
+    "set_meas_robust": lambda d, p: d.set_meas_robust(gp.chain.MEAS_INTERP_RANGE, [gp.chain.ROBUST_HUBER], 1.0),
+    "set_between_pairs_robust": lambda d, p: d.set_between_pairs_robust([gp.chain.ROBUST_HUBER], 1.0),
+    "set_closure_passes": lambda d, p: d.set_closure_passes(4, 1),
+    "add_state_gaussians": lambda d, p: d.add_state_gaussians([2], p["pose"][2], p["vel"][2], _EYE(6), np.zeros(6)),
+    "add_border_gaussians": lambda d, p: d.add_border_gaussians([2], p["pose"][2], p["vel"][2], p["landmarks"], _EYE(8), np.zeros(8)),
+    "marginalize_head": lambda d, p: d.marginalize_head(1),
+    "append_states": lambda d, p: d.append_states(p["pose"][-1:], p["vel"][-1:]),
+    "clear_factors": lambda d, p: d.clear_factors(),
+    "compile": lambda d, p: d.compile(),
+    "iterate_gn": lambda d, p: d.iterate_gn(),
+    "run_gn": lambda d, p: d.run_gn(1),
+    "iterate_lm": lambda d, p: d.iterate_lm(1e-3),
+    "optimize": lambda d, p: d.optimize(),
+    "lm_trial_phase1": _raw("lm_trial_phase1", C.c_double(1e-3)),
+    "lm_reject": _raw("lm_reject"),
+    "marginals_keep_closure_columns": lambda d, p: d.marginals_keep_closure_columns(),
+    "marginals_on_segments": lambda d, p: d.marginals_on_segments(),
+    "marginals_keep_pair_terms": lambda d, p: d.marginals_keep_pair_terms(),
+    "add_interp_attitude": None, "add_ahrs": None, "add_interp_gps": None, "add_interp_projection": None, "add_interp_projection_ds2": None,
+    "add_odometry2d": None, "add_bearing_range": None,
+    "iterate_phase1": None, "fs_set_split": None, "fs_phase1": None, "fs_lm_trial_phase1": None,
+}
+# Column two: everything else -- the blocks of the last marginals() stay what they were, to the bit.  (error and lm_begin read the
+# estimate and move nothing.)  None: not a call on this handle, or one the small graph cannot make
+_LEAVES_SIGMA = {
+    "get_states": lambda d, p: d.get_states(),
+    "get_landmarks": lambda d, p: d.get_landmarks(),
+    "closure_info": lambda d, p: d.closure_info(),
+    "get_meas_weights": lambda d, p: d.meas_weights(gp.chain.MEAS_INTERP_RANGE, 3),
+    "get_between_pairs_weights": lambda d, p: d.between_pairs_weights(1),
+    "get_state_gaussians": lambda d, p: d.get_state_gaussians(),
+    "get_border_gaussians": lambda d, p: d.get_border_gaussians(),
+    "marginalize_head_onto_landmarks": lambda d, p: d.marginalize_head_onto_landmarks(),
+    "linearize_gp": lambda d, p: d.linearize_gp(),
+    "linearize_meas": lambda d, p: d.linearize_meas(gp.chain.MEAS_INTERP_RANGE, 3),
+    "error": lambda d, p: d.error(),
+    "normal_equations": lambda d, p: d.normal_equations(),
+    "get_rows": lambda d, p: d.get_rows(),
+    "interpolate_poses": lambda d, p: d.interpolate_poses([1], [0.1], [0.05]),
+    "interpolate_poses_jac": lambda d, p: d.interpolate_poses_jac([1], [0.1], [0.05]),
+    "marginals": lambda d, p: d.marginals(),
+    "get_marginals": lambda d, p: d.get_marginals(cross=True),
+    "get_landmark_marginals": lambda d, p: d.get_landmark_marginals(),
+    "get_state_landmark_marginals": lambda d, p: d.get_state_landmark_marginals([2], [0]),
+    "get_landmark_pair_marginals": lambda d, p: d.get_landmark_pair_marginals([0], [0]),
+    "get_state_pair_marginals": lambda d, p: d.get_state_pair_marginals([0], [3]),
+    "gate_between_pairs": lambda d, p: d.gate_between_pairs([0], [3], p["closure_meas"], p["closure_sig"]),
+    "interpolate_covariances": lambda d, p: d.interpolate_covariances([1], [0.1], [0.05]),
+    "plan_info": lambda d, p: d.plan_info(),
+    "launch_census": lambda d, p: d.launch_census(),
+    "segment_plan": lambda d, p: d.segment_plan(),
+    "last_timing": lambda d, p: d.last_timing(),
+    "last_level0_ms": lambda d, p: d.last_level0_ms(),
+    "set_level0_stamps": lambda d, p: d.set_level0_stamps(False),
+    "last_error": lambda d, p: d.lib.gpslam_hip_last_error(d._h),
+    "stream": lambda d, p: d.stream(),
+    "lm_begin": _raw("lm_begin"),
+    "lm_trial_phase2": _raw("lm_trial_phase2", None),
+    "abi_version": None, "struct_size": None, "create": None, "create_v2": None, "destroy": None, "default_params": None, "lm_decide": None,
+    "robust_eval": None, "set_stream": None, "set_collectives": None, "get_head_prior": None, "get_head_prior_border": None,
+    "block_tridiag_solve": None, "interpolate_velocities": None, "body_centric_velocity": None, "time_kernel": None,
+    "interface_send": None, "interface_recv": None, "iterate_phase2": None, "iterate_phase2a": None, "iterate_phase2b": None,
+    "landmark_reduce_buffer": None, "fs_split_info": None, "fs_set_top": None, "fs_interface": None, "fs_phase2": None, "fs_lm_trial_phase2": None,
+}
+
+
+def test_every_entry_point_is_classified():
+    """The header's entry points, each in exactly one column: a new one fails here until it is classified."""
+    names = _entry_points()
+    assert len(names) > 90 and "marginals" in names and "abi_version" in names
+    assert not set(_CHANGES_SIGMA) & set(_LEAVES_SIGMA)
+    assert sorted(set(_CHANGES_SIGMA) | set(_LEAVES_SIGMA)) == names
+
+
+@pytest.mark.parametrize("name", sorted(k for k, v in _CHANGES_SIGMA.items() if v is not None))
+def test_staleness_is_total(name):
+    p = _small_graph()
+    dev = _small_handle(p)
+    dev.get_marginals(cross=True)
+    _CHANGES_SIGMA[name](dev, p)
+    with pytest.raises(gp.GpslamHipError, match=r"\(-1\).*stale"):
+        dev.get_marginals()
+
+
+def test_other_entry_points_leave_the_marginals_alone():
+    p = _small_graph()
+    dev = _small_handle(p)
+    ref = dev.get_marginals(cross=True)
+    for name in sorted(k for k, v in _LEAVES_SIGMA.items() if v is not None):
+        _LEAVES_SIGMA[name](dev, p)
+        now = dev.get_marginals(cross=True)
+        assert all(np.array_equal(a, b) for a, b in zip(ref, now)), name
+
+
+# ---------------------------------------------------------------- destroy frees
+
+def _free_bytes():
+    free, total = C.c_size_t(0), C.c_size_t(0)
+    assert gp.chain.load_library().hipMemGetInfo(C.byref(free), C.byref(total)) == 0     # (the HIP runtime the library itself is linked to)
+    return free.value
+
+
+def test_destroy_frees_the_device_memory():
+    """A handle's whole life, again and again: the device's free memory after ten cycles is lower than after the first by less than half
+    of what one handle holds (Z alone: mg_zrows(N, b) rows of 16 doubles, 15 MB).  A condition on gross leaks, not a tolerance."""
+    N = 20000
+    p = S.add_loop_closures(_pose2_chain(N), [[100, 5000], [2000, 12000], [7000, 19000], [300, 15000], [9000, 9500]])
+
+    def cycle():
+        dev = gp.ChainSolver(p["kind"])
+        dev.set_closure_passes(8, 2)
+        S.apply(p, dev)
+        assert dev.closure_info()["passes"] == 3
+        dev.marginals_keep_closure_columns()
+        dev.marginals_keep_pair_terms()
+        dev.marginals()
+        dev.get_state_pair_marginals([3], [15000])
+        inside = _free_bytes()
+        dev.close()
+        return inside
+
+    cycle()
+    free_warm = _free_bytes()
+    footprint = free_warm - cycle()
+    for _ in range(9):
+        cycle()
+    lost = free_warm - _free_bytes()
+    print("footprint %d bytes, lost after ten cycles %d bytes" % (footprint, lost))
+    assert footprint >= (N * 6 + 16) * 16 * 8
+    assert lost < footprint / 2

@@ -59,6 +59,13 @@ ABI_SYMBOLS = [
     "gpslam_hip_get_head_prior_border",
     "gpslam_hip_marginals_keep_pair_terms", "gpslam_hip_get_state_pair_marginals", "gpslam_hip_gate_between_pairs",
 ]
+# every symbol include/gpslam_hip_dogleg.h declares (Powell's dogleg; a list of its own: the ABI stays 2.4 and these entry points are
+# detected by presence)
+DOGLEG_SYMBOLS = [
+    "gpslam_hip_dogleg_point", "gpslam_hip_dogleg_decide", "gpslam_hip_iterate_dogleg", "gpslam_hip_optimize_dogleg",
+    "gpslam_hip_dogleg_last",
+]
+DOGLEG_ONE_STEP_PER_ITERATION, DOGLEG_SEARCH_EACH_ITERATION, DOGLEG_SEARCH_REDUCE_ONLY = 0, 1, 2
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
 STRUCT_CONFIG, STRUCT_CONFIG_V2, STRUCT_STATS, STRUCT_PARAMS = 0, 1, 2, 3
@@ -163,6 +170,47 @@ def lm_decide(s6, lam, lambda_factor=10.0, lambda_upper_bound=1e5, lambda_lower_
     if rc:
         raise GpslamHipError("lm_decide: %d" % rc)
     return bool(acc.value), bool(done.value), lam_c.value
+
+
+def _dogleg_lib():
+    """The library with the argument types of include/gpslam_hip_dogleg.h set (doubles travel by value there)."""
+    lib = load_library()
+    if not hasattr(lib, "gpslam_hip_iterate_dogleg"):
+        raise GpslamHipError("this libgpslam_hip.so has no dogleg entry points (include/gpslam_hip_dogleg.h)")
+    if getattr(lib, "_dogleg_bound", False):
+        return lib
+    dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p
+    lib.gpslam_hip_dogleg_point.argtypes = [dp, C.c_double, dp, dp, dp, ip]
+    lib.gpslam_hip_dogleg_decide.argtypes = [dp, C.c_int32, dp, ip, ip, ip]
+    lib.gpslam_hip_iterate_dogleg.argtypes = [vp, dp, C.c_int32, C.POINTER(Stats)]
+    lib.gpslam_hip_optimize_dogleg.argtypes = [vp, C.POINTER(Params), C.c_double, C.c_int32, C.POINTER(Stats)]
+    lib.gpslam_hip_dogleg_last.argtypes = [vp, dp]
+    for name in DOGLEG_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
+    lib._dogleg_bound = True
+    return lib
+
+
+def dogleg_point(s4, delta):
+    """gpslam_hip_dogleg_point (host arithmetic, no GPU): the dogleg point of trust radius delta from s4 = (gg, gHg, gn, nn).
+    Returns (alpha, beta, |delta_d|, predicted decrease, branch): delta_d = alpha g + beta delta_n."""
+    s = (C.c_double * 4)(*[float(v) for v in s4])
+    coef, norm, pred, br = (C.c_double * 2)(), C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+    rc = _dogleg_lib().gpslam_hip_dogleg_point(s, float(delta), coef, C.byref(norm), C.byref(pred), C.byref(br))
+    if rc:
+        raise GpslamHipError("dogleg_point: %d" % rc)
+    return coef[0], coef[1], norm.value, pred.value, br.value
+
+
+def dogleg_decide(s4, mode, delta, last_action=0):
+    """gpslam_hip_dogleg_decide (host arithmetic, no GPU): one trust-region decision from s4 = (f, f_new, predicted, |delta_d|).
+    Returns (keep, stay, new delta, new last_action)."""
+    s = (C.c_double * 4)(*[float(v) for v in s4])
+    d, la, keep, stay = C.c_double(delta), C.c_int32(int(last_action)), C.c_int32(0), C.c_int32(0)
+    rc = _dogleg_lib().gpslam_hip_dogleg_decide(s, int(mode), C.byref(d), C.byref(la), C.byref(keep), C.byref(stay))
+    if rc:
+        raise GpslamHipError("dogleg_decide: %d" % rc)
+    return bool(keep.value), bool(stay.value), d.value, la.value
 
 
 def robust_eval(loss, k, r):
@@ -529,6 +577,25 @@ class ChainSolver:
         rc = self.lib.gpslam_hip_optimize(self._h, C.byref(p), C.byref(st))
         self._chk(rc, "optimize")
         return rc, st
+
+    def iterate_dogleg(self, delta, mode=DOGLEG_ONE_STEP_PER_ITERATION):
+        """One DoglegOptimizer::iterate() (include/gpslam_hip_dogleg.h): returns (stats, the trust radius after)."""
+        st, d = Stats(), C.c_double(delta)
+        self._chk(_dogleg_lib().gpslam_hip_iterate_dogleg(self._h, C.byref(d), int(mode), C.byref(st)), "iterate_dogleg")
+        return st, d.value
+
+    def optimize_dogleg(self, params=None, delta_initial=1.0, mode=DOGLEG_ONE_STEP_PER_ITERATION):
+        st = Stats()
+        p = params or self.default_params()
+        rc = _dogleg_lib().gpslam_hip_optimize_dogleg(self._h, C.byref(p), float(delta_initial), int(mode), C.byref(st))
+        self._chk(rc, "optimize_dogleg")
+        return rc, st
+
+    def dogleg_last(self):
+        """(gg, gHg, gn, nn, alpha, beta, predicted, branch) of the last trial of the last iterate_dogleg"""
+        out = (C.c_double * 8)()
+        self._chk(_dogleg_lib().gpslam_hip_dogleg_last(self._h, out), "dogleg_last")
+        return tuple(out)
 
     def run_gn(self, iters, timed=False):
         st = Stats()

@@ -140,6 +140,13 @@ struct LaunchCensus {
   int32_t &operator[](int i) { return v[i]; }
 };
 
+// gpslam_hip_iterate_dogleg (dogleg.hip): the landmark gradient g_L and the landmarks' part of the Gauss-Newton step (the states' parts
+// are gsave and dvec), the partial sums of g^T H g and g . g, and what the last call computed (gpslam_hip_dogleg_last)
+struct Dogleg {
+  DevBuf gL, nL, part;
+  double last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 struct gpslam_hip_handle {
   gpslam_hip_config_v2 cfg;   // (gpslam_hip_create maps a v1 config onto it)
   int mf = 0, d = 0, pd = 0, b = 0, ld = 0;
@@ -228,6 +235,7 @@ struct gpslam_hip_handle {
   double ph_lambda = 0.0;
   Marginals mg;               // gpslam_hip_marginals (marginals.hpp): what the last call left; every call that can change states, landmarks,
                               // factors or Qc says h->mg.invalidate()
+  Dogleg dl;                  // gpslam_hip_iterate_dogleg (dogleg.hip)
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch

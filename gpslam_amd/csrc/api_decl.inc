@@ -44,3 +44,10 @@ int marginals_fs_forward(gpslam_hip_handle *h, void *Y);
 // gpslam_hip_marginalize_head (fixedlag.hip): the rows and the records [D | O | g] of the current linearisation in the row form (the d = 3
 // GP priors as rows: the head's share of block k is summed from the tables)
 int fixedlag_assemble(gpslam_hip_handle *h);
+// gpslam_hip_iterate_dogleg (dogleg.hip).  dogleg_linearize: the pivot flag cleared, the rows and the error of the current estimate
+// (scal[0]), the estimate remembered (backup_state), the records [D | O | g | B] in the form of gpslam_hip_normal_equations with the
+// gradient copied to gsave.  dogleg_solve: launch_solve at lambda = 0 in the two-launch form.  dogleg_trial: the tail of a
+// Levenberg-Marquardt trial -- retract by column 0 of the level-0 solution and lm_dL (scal[2] = |delta|_inf), error into scal[1]
+int dogleg_linearize(gpslam_hip_handle *h);
+int dogleg_solve(gpslam_hip_handle *h);
+int dogleg_trial(gpslam_hip_handle *h);

@@ -1770,6 +1770,20 @@ int fixedlag_assemble(gpslam_hip_handle *h) {
   if ((rc = launch_factors(h, m, 0, 0))) return rc;
   return launch_assemble(h, m, false);
 }
+// gpslam_hip_iterate_dogleg (dogleg.hip): see api_decl.inc
+int dogleg_linearize(gpslam_hip_handle *h) {
+  int rc;
+  HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
+  if ((rc = launch_factors(h, LaunchMode{}, 0, 0))) return rc;
+  if ((rc = backup_state(h, false))) return rc;
+  return launch_assemble(h, LaunchMode{}, true);
+}
+int dogleg_solve(gpslam_hip_handle *h) { return launch_solve(h, LaunchMode{}, 0.0); }
+int dogleg_trial(gpslam_hip_handle *h) {
+  int rc;
+  if ((rc = launch_retract(h, LaunchMode{}, 2))) return rc;
+  return launch_factors(h, LaunchMode{}, 1, 1);
+}
 // ... and the solver's right-hand sides at lambda = 0: the closure columns Z = A^-1 J_c^T, the landmark columns corrected for the
 // closures, and the landmark Schur complement S of the whole chain -- launch_solve without the landmark solve (the states stay).
 // On a handle in column passes (gpslam_hip_marginals_keep_closure_columns) every slice of Z is kept in h->mg.Z on the way.

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/gpslam_hip.h"
+#include "../../include/gpslam_hip_dogleg.h"
 
 // boost::optional<Matrix&> -- the type of the reference's Jacobian arguments (gpslam/gp/GaussianProcessPriorPose3.h:60-64:
 // `boost::optional<gtsam::Matrix&> H1 = boost::none`).  Where Boost is installed its header is used; where it is not (this image), the
@@ -485,6 +486,17 @@ struct LevenbergMarquardtParams : NonlinearOptimizerParams {
   void setlambdaFactor(double v) { lambdaFactor = v; }
   void setlambdaUpperBound(double v) { lambdaUpperBound = v; }
 };
+/// gtsam::DoglegParams: deltaInitial is the first trust radius.  adaptationMode is DoglegOptimizerImpl::TrustRegionAdaptationMode
+/// (DoglegOptimizer itself always iterates ONE_STEP_PER_ITERATION; the other two are what ISAM2DoglegParams may choose)
+struct DoglegParams : NonlinearOptimizerParams {
+  enum TrustRegionAdaptationMode { ONE_STEP_PER_ITERATION = GPSLAM_DOGLEG_ONE_STEP_PER_ITERATION,
+                                   SEARCH_EACH_ITERATION = GPSLAM_DOGLEG_SEARCH_EACH_ITERATION,
+                                   SEARCH_REDUCE_ONLY = GPSLAM_DOGLEG_SEARCH_REDUCE_ONLY };
+  double deltaInitial = 1.0;
+  TrustRegionAdaptationMode adaptationMode = ONE_STEP_PER_ITERATION;
+  void setDeltaInitial(double v) { deltaInitial = v; }
+  double getDeltaInitial() const { return deltaInitial; }
+};
 
 class NonlinearFactorGraph {
  public:
@@ -898,6 +910,25 @@ class LevenbergMarquardtOptimizer : public NonlinearOptimizer {
  private:
   LevenbergMarquardtParams lm_;
   double lambda_;
+};
+
+/// gtsam::DoglegOptimizer (Powell's dogleg; include/gpslam_hip_dogleg.h): one solve per iteration, every trial of a trust radius a
+/// blend of the Gauss-Newton and the steepest-descent step.  fp64 unsharded handles without loop closures (the library refuses others)
+class DoglegOptimizer : public NonlinearOptimizer {
+ public:
+  DoglegOptimizer(const NonlinearFactorGraph &graph, const Values &initial, const DoglegParams &params = DoglegParams())
+      : NonlinearOptimizer(graph, initial, params), dl_(params), delta_(params.deltaInitial) {}
+  double getDelta() const { return delta_; }
+  /// the library's arguments for these parameters: (trust radius, mode)
+  static std::pair<double, int32_t> abiArguments(const DoglegParams &p) { return {p.deltaInitial, (int32_t)p.adaptationMode}; }
+  void iterate() override {
+    gpslam_hip_stats st;
+    detail::check(gpslam_hip_iterate_dogleg(s_.h, &delta_, abiArguments(dl_).second, &st), s_.h, "iterate_dogleg");
+    error_ = st.error_after; iterations_++; dirty_ = true;
+  }
+ private:
+  DoglegParams dl_;
+  double delta_;
 };
 
 // ---------------------------------------------------------------- fixed-lag smoothing

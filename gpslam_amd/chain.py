@@ -66,6 +66,11 @@ DOGLEG_SYMBOLS = [
     "gpslam_hip_dogleg_last",
 ]
 DOGLEG_ONE_STEP_PER_ITERATION, DOGLEG_SEARCH_EACH_ITERATION, DOGLEG_SEARCH_REDUCE_ONLY = 0, 1, 2
+# every symbol include/gpslam_hip_evidence.h declares (log det H, the Laplace log-evidence; a list of its own, as the dogleg's)
+EVIDENCE_SYMBOLS = [
+    "gpslam_hip_log_determinant", "gpslam_hip_log_noise_normaliser", "gpslam_hip_log_evidence",
+    "gpslam_hip_gp_log_normaliser", "gpslam_hip_evidence_combine",
+]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
 STRUCT_CONFIG, STRUCT_CONFIG_V2, STRUCT_STATS, STRUCT_PARAMS = 0, 1, 2, 3
@@ -211,6 +216,46 @@ def dogleg_decide(s4, mode, delta, last_action=0):
     if rc:
         raise GpslamHipError("dogleg_decide: %d" % rc)
     return bool(keep.value), bool(stay.value), d.value, la.value
+
+
+def _evidence_lib():
+    """The library with the argument types of include/gpslam_hip_evidence.h set (doubles and 64-bit counts travel by value there)."""
+    lib = load_library()
+    if not hasattr(lib, "gpslam_hip_log_determinant"):
+        raise GpslamHipError("this libgpslam_hip.so has no evidence entry points (include/gpslam_hip_evidence.h)")
+    if getattr(lib, "_evidence_bound", False):
+        return lib
+    dp, lp, vp = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p
+    lib.gpslam_hip_log_determinant.argtypes = [vp, dp, dp]
+    lib.gpslam_hip_log_noise_normaliser.argtypes = [vp, dp, lp, lp]
+    lib.gpslam_hip_log_evidence.argtypes = [vp, dp]
+    lib.gpslam_hip_gp_log_normaliser.argtypes = [C.c_int32, dp, C.c_double, dp]
+    lib.gpslam_hip_evidence_combine.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int64, dp]
+    for name in EVIDENCE_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
+    lib._evidence_bound = True
+    return lib
+
+
+def gp_log_normaliser(Qc, dt):
+    """gpslam_hip_gp_log_normaliser (host arithmetic, no GPU): log|det R| = -1/2 log det Q(dt) of one GP prior with the d x d Qc."""
+    q = np.ascontiguousarray(Qc, dtype=np.float64)
+    if q.ndim != 2 or q.shape[0] != q.shape[1]:
+        raise GpslamHipError("gp_log_normaliser: Qc must be square")
+    out = C.c_double(0.0)
+    rc = _evidence_lib().gpslam_hip_gp_log_normaliser(int(q.shape[0]), q.ctypes.data_as(C.POINTER(C.c_double)), float(dt), C.byref(out))
+    if rc:
+        raise GpslamHipError("gp_log_normaliser: %d" % rc)
+    return out.value
+
+
+def evidence_combine(cost, logdet, lognorm, rows, nvars):
+    """gpslam_hip_evidence_combine (host arithmetic, no GPU): log Z = -cost + lognorm - logdet / 2 - ((rows - nvars) / 2) log 2 pi."""
+    out = C.c_double(0.0)
+    rc = _evidence_lib().gpslam_hip_evidence_combine(float(cost), float(logdet), float(lognorm), int(rows), int(nvars), C.byref(out))
+    if rc:
+        raise GpslamHipError("evidence_combine: %d" % rc)
+    return out.value
 
 
 def robust_eval(loss, k, r):
@@ -595,6 +640,25 @@ class ChainSolver:
         """(gg, gHg, gn, nn, alpha, beta, predicted, branch) of the last trial of the last iterate_dogleg"""
         out = (C.c_double * 8)()
         self._chk(_dogleg_lib().gpslam_hip_dogleg_last(self._h, out), "dogleg_last")
+        return tuple(out)
+
+    def log_determinant(self, parts=False):
+        """log det H at the current states (include/gpslam_hip_evidence.h); parts=True: (logdet, (log det A, log det(I + U Z),
+        log det S)).  The marginals are stale afterwards."""
+        out, p3 = C.c_double(0.0), (C.c_double * 3)()
+        self._chk(_evidence_lib().gpslam_hip_log_determinant(self._h, C.byref(out), p3), "log_determinant")
+        return (out.value, tuple(p3)) if parts else out.value
+
+    def log_noise_normaliser(self):
+        """(sum_f log|det R_f|, residual rows m, variables n) of the stored graph: host arithmetic, nothing is launched"""
+        out, m, n = C.c_double(0.0), C.c_int64(0), C.c_int64(0)
+        self._chk(_evidence_lib().gpslam_hip_log_noise_normaliser(self._h, C.byref(out), C.byref(m), C.byref(n)), "log_noise_normaliser")
+        return out.value, m.value, n.value
+
+    def log_evidence(self):
+        """(log Z, cost, log det H, lognorm, m - n) at the current states: the Laplace log-evidence (optimise first)"""
+        out = (C.c_double * 5)()
+        self._chk(_evidence_lib().gpslam_hip_log_evidence(self._h, out), "log_evidence")
         return tuple(out)
 
     def run_gn(self, iters, timed=False):

@@ -281,7 +281,7 @@ int gpslam_hip_add_gp_priors_qc(gpslam_hip_handle *h, int32_t count, const int32
   if (!h || count < 0 || (count > 0 && (!left || !dt || !Qc))) return GPSLAM_E_INVALID;
   const int dq = (h->mf == ROT3_BIAS) ? 3 : h->d;
   std::vector<int32_t> q((size_t)count);
-  std::vector<double> tab = h->gp_Utab;
+  std::vector<double> tab = h->gp_Utab, qtab = h->gp_Qtab;
   for (int k = 0; k < count; k++) {
     if (left[k] < 0 || left[k] > max_left(h)) return fail(h, GPSLAM_E_INVALID, "gp prior index out of range");
     if (!(dt[k] > 0.0)) return fail(h, GPSLAM_E_INVALID, "gp prior delta_t must be positive");
@@ -301,10 +301,16 @@ int gpslam_hip_add_gp_priors_qc(gpslam_hip_handle *h, int32_t count, const int32
     const int nent = (int)(tab.size() / 36);
     for (int e = 0; e < nent && slot < 0; e++)
       if (std::memcmp(&tab[(size_t)e * 36], U, sizeof(U)) == 0) slot = e;
-    if (slot < 0) { slot = nent; tab.insert(tab.end(), U, U + 36); }
+    if (slot < 0) {
+      slot = nent;
+      tab.insert(tab.end(), U, U + 36);
+      qtab.resize(tab.size(), 0.0);      // the Qc itself, for the evidence's normaliser (d x d leading)
+      std::memcpy(&qtab[(size_t)slot * 36], qc, sizeof(double) * h->d * h->d);
+    }
     q[k] = slot + 1;
   }
   h->gp_Utab.swap(tab);
+  h->gp_Qtab.swap(qtab);
   h->gp_left.insert(h->gp_left.end(), left, left + count);
   h->gp_dt.insert(h->gp_dt.end(), dt, dt + count);
   h->gp_q.insert(h->gp_q.end(), q.begin(), q.end());
@@ -527,7 +533,7 @@ int gpslam_hip_add_bearing_range(gpslam_hip_handle *h, int32_t count, const int3
 
 int gpslam_hip_clear_factors(gpslam_hip_handle *h) {
   if (!h) return GPSLAM_E_INVALID;
-  h->gp_left.clear(); h->gp_dt.clear(); h->gp_q.clear(); h->gp_Utab.clear(); h->gp_perm.clear(); h->gp_groups.clear();
+  h->gp_left.clear(); h->gp_dt.clear(); h->gp_q.clear(); h->gp_Utab.clear(); h->gp_Qtab.clear(); h->gp_perm.clear(); h->gp_groups.clear();
   for (SimpleSet *s : {&h->pri, &h->vpri, &h->btw, &h->lpri, &h->clo.fac}) { s->idx.clear(); s->meas.clear(); s->sig.clear(); }
   h->clo.second.clear();
   h->clo.rob.clear();

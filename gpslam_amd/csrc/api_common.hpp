@@ -147,6 +147,18 @@ struct Dogleg {
   double last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// gpslam_hip_log_determinant (evidence.hip): the separators' systems of the levels above 0 (three blocks each: D, O, add), one
+// partial sum of log-pivots per chunk of every level, and what the call reads back ({log det A, log det(I + U Z), log det S, flag})
+struct Evidence {
+  int N = 0;                  // the N the buffers are sized for
+  DevBuf up, part, res;
+  // the buffers serve n states from here on: another N frees what is there (as Marginals::fit)
+  void fit(int n) {
+    if (N != n) { up.release(); part.release(); }
+    N = n;
+  }
+};
+
 struct gpslam_hip_handle {
   gpslam_hip_config_v2 cfg;   // (gpslam_hip_create maps a v1 config onto it)
   int mf = 0, d = 0, pd = 0, b = 0, ld = 0;
@@ -172,6 +184,7 @@ struct gpslam_hip_handle {
   // and the linearisation runs one launch per group (gp_groups: {q, first, count}), each with its U as a kernel argument.
   std::vector<int32_t> gp_q;
   std::vector<double> gp_Utab;
+  std::vector<double> gp_Qtab;  // the Qc behind each entry of gp_Utab as it was given (36 doubles each, d x d leading; evidence.hip)
   std::vector<int32_t> gp_perm;
   std::vector<int32_t> gp_groups;
   int gp_single_q = 0;      // > 0: every GP prior came through add_gp_priors_qc with the SAME Qc (entry gp_single_q - 1 of gp_Utab):
@@ -236,6 +249,7 @@ struct gpslam_hip_handle {
   Marginals mg;               // gpslam_hip_marginals (marginals.hpp): what the last call left; every call that can change states, landmarks,
                               // factors or Qc says h->mg.invalidate()
   Dogleg dl;                  // gpslam_hip_iterate_dogleg (dogleg.hip)
+  Evidence evd;               // gpslam_hip_log_determinant (evidence.hip)
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch

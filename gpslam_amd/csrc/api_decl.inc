@@ -51,3 +51,5 @@ int fixedlag_assemble(gpslam_hip_handle *h);
 int dogleg_linearize(gpslam_hip_handle *h);
 int dogleg_solve(gpslam_hip_handle *h);
 int dogleg_trial(gpslam_hip_handle *h);
+// gpslam_hip_log_determinant (evidence.hip): marginals_border without the kept Z of a handle in column passes
+int evidence_border(gpslam_hip_handle *h);

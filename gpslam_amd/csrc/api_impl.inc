@@ -1788,6 +1788,8 @@ int dogleg_trial(gpslam_hip_handle *h) {
 // closures, and the landmark Schur complement S of the whole chain -- launch_solve without the landmark solve (the states stay).
 // On a handle in column passes (gpslam_hip_marginals_keep_closure_columns) every slice of Z is kept in h->mg.Z on the way.
 int marginals_border(gpslam_hip_handle *h) { return launch_solve(h, LaunchMode{}, 0.0, true, false); }
+// gpslam_hip_log_determinant (evidence.hip): the same without a kept Z -- in column passes W = U [X | Z] in clo.W is all it reads
+int evidence_border(gpslam_hip_handle *h) { return launch_solve(h, LaunchMode{}, 0.0, false, false); }
 // ... and on the segmented landmark path (marginals_fs.hip) the forward half at lambda = 0: segment factors, the half-swept border
 // Y = L^-1 G into the marginals' own buffer (zeroed by the caller; a fused_sweep plan has none), the fat chain's cyclic reduction
 int marginals_fs_forward(gpslam_hip_handle *h, void *Y) { return fs_forward(h, 0.0, static_cast<Real *>(Y)); }

@@ -33,6 +33,7 @@
 
 #include "../../include/gpslam_hip.h"
 #include "../../include/gpslam_hip_dogleg.h"
+#include "../../include/gpslam_hip_evidence.h"
 
 // boost::optional<Matrix&> -- the type of the reference's Jacobian arguments (gpslam/gp/GaussianProcessPriorPose3.h:60-64:
 // `boost::optional<gtsam::Matrix&> H1 = boost::none`).  Where Boost is installed its header is used; where it is not (this image), the
@@ -1339,6 +1340,34 @@ class Marginals {
   }
   detail::Session s_;
 };
+
+/// log det H of the whole graph at `values`, H = J^T J the Gauss-Newton Hessian Marginals inverts (gpslam_hip_log_determinant; include/
+/// gpslam_hip_evidence.h), on a session of its own.  GTSAM's GaussianBayesNet::logDeterminant() of the eliminated linearised graph is
+/// log det R with R^T R = H: HALF of this number.
+inline double logDeterminant(const NonlinearFactorGraph &graph, const Values &values) {
+  detail::Session s;
+  s.build(graph, values);
+  double out = 0.0;
+  detail::check(gpslam_hip_log_determinant(s.h, &out, nullptr), s.h, "log_determinant");
+  return out;
+}
+
+/// The Laplace log-evidence of the graph at `values` (the caller's optimum): log Z = -cost + sum_f log|det R_f| - 1/2 log det H -
+/// ((m - n) / 2) log 2 pi (gpslam_hip_log_evidence), the number a hyperparameter such as Qc is chosen by.  Graphs with robust noise
+/// models or AHRS factors have none: std::invalid_argument.
+struct LogEvidence {
+  double logZ = 0.0, cost = 0.0, logDeterminant = 0.0, logNoiseNormaliser = 0.0;
+  long long rowsMinusVariables = 0;
+};
+inline LogEvidence logEvidence(const NonlinearFactorGraph &graph, const Values &values) {
+  detail::Session s;
+  s.build(graph, values);
+  double out5[5] = {0, 0, 0, 0, 0};
+  detail::check(gpslam_hip_log_evidence(s.h, out5), s.h, "log_evidence");
+  LogEvidence e;
+  e.logZ = out5[0]; e.cost = out5[1]; e.logDeterminant = out5[2]; e.logNoiseNormaliser = out5[3]; e.rowsMinusVariables = (long long)out5[4];
+  return e;
+}
 
 // ---------------------------------------------------------------- AHRS (gtsam/navigation/AHRSFactor.h, GTSAM 4.0; third party)
 /// gtsam::PreintegratedAhrsMeasurements(biasHat, measuredOmegaCovariance): the constructor matlab/GPAHRSexample.m:188 uses.

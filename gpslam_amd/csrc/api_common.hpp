@@ -159,6 +159,20 @@ struct Evidence {
   }
 };
 
+// Work one launch leaves to a later one (chains without landmarks, unsharded: gn_mode; run_gn with Plan::fold_retract).  update: a
+// solve's step sits in the level-0 solution array, not yet applied -- the next k_lin applies it (kernels.hpp: PendUpd), or
+// flush_update.  err: the linearisation's error partial sums in `partial`, summed by an extra workgroup of this iteration's
+// k_retract.  dmax: the retraction's |delta|_inf partial maxima in `partial2`, reduced by an extra workgroup of the NEXT iteration's
+// k_lin -- two launches (+ their gaps) less per iteration, same values, same order
+struct Deferred {
+  bool update = false;
+  struct Sums {
+    int n = 0, slot = 0;      // n > 0: that many partials wait, for scal[slot]
+    Sums take() { const Sums s = *this; n = 0; return s; }   // the launch that reduces them says so
+  } err, dmax;
+  void clear() { update = false; err.n = 0; dmax.n = 0; }
+};
+
 struct gpslam_hip_handle {
   gpslam_hip_config_v2 cfg;   // (gpslam_hip_create maps a v1 config onto it)
   int mf = 0, d = 0, pd = 0, b = 0, ld = 0;
@@ -231,19 +245,13 @@ struct gpslam_hip_handle {
   void *coll_user = nullptr;
   DevBuf coll_s, coll_r;     // 8 doubles of this rank's scalars, nranks x 8 gathered
   DevBuf brec, btwidx;      // Plan::btw_rec
-  // Gauss-Newton runs (gpslam_hip_run_gn, Plan::fold_retract): a solve's update sits in the level-0 solution array, not yet applied
-  bool pend_upd = false;
   // set_qc after compile(): refresh_dU brings the device copy of U (and U_diag) up to date before a launch reads it
   int U_version = 0, dU_version = -1;
   bool U_diag = false;        // the U in dU is diagonal (an isotropic or diagonal Qc): the SE(3) record variants take the shorter assembly form
   bool compiled = false;
   double last_ms[5] = {0, 0, 0, 0, 0};
-  // deferred reductions inside run_gn / iterate_gn (chains without landmarks, unsharded): the error partial sums of the
-  // linearisation are summed by an extra workgroup of k_retract, the |delta|_inf partial maxima of the retraction by an
-  // extra workgroup of the NEXT iteration's k_lin -- two launches (+ their gaps) less per iteration, same values, same order
   DevBuf partial2;            // the retraction's per-block maxima (its own buffer: the linearisation reuses `partial`)
-  int pend_err_n = 0, pend_err_slot = 0;        // pending: error partials in `partial`
-  int pend_dmax_n = 0, pend_dmax_slot = 0;      // pending: maxima in `partial2`
+  Deferred defer;
   double l0_ms = 0.0;         // the level-0 forward launch, accumulated over the last timed run: the dominant kernel INSIDE an iteration
   double ph_lambda = 0.0;
   Marginals mg;               // gpslam_hip_marginals (marginals.hpp): what the last call left; every call that can change states, landmarks,
@@ -271,6 +279,8 @@ struct LaunchMode {
   // what rocprofv3's kernel trace reads) -- events recorded AROUND a launch add their marker packets to it (7 us of 149)
   bool l0_events = false;
   bool weights = false;       // an error-only pass that also stores every robust factor's weight w(r) (MeasArgs::out_w, CloArgs::out_w)
+  bool keep_z = false;        // launch_solve in column passes: every pass's slice of Z = A^-1 U^T into h->mg.Z (the marginals)
+  bool lm_reduce_only = false;   // launch_solve ends with the landmark Schur complement, without the landmark solve (the states stay)
 };
 
 // Loop closures (closures.hip; fp64 only: both precision namespaces call these, and compile() refuses closures on an fp32 handle).

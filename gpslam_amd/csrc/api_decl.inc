@@ -33,23 +33,9 @@ int gpslam_hip_normal_equations(gpslam_hip_handle *h, double *D, double *O, doub
 int gpslam_hip_optimize(gpslam_hip_handle *h, const gpslam_hip_params *p, gpslam_hip_stats *st);
 int gpslam_hip_run_gn(gpslam_hip_handle *h, int32_t iters, gpslam_hip_stats *st, double *out5);
 int gpslam_hip_time_kernel(gpslam_hip_handle *h, int32_t which, int32_t reps, double *avg_ms);
-int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot, bool e32);
-// gpslam_hip_marginals (marginals.hip): the assembly of gpslam_hip_normal_equations; then the solver's right-hand sides at
-// lambda = 0 (forward, backward, closure correction) and the landmark Schur complement, without the landmark solve -- on a handle
-// in column passes launch_solve_passes, every slice of Z kept in h->mg.Z on the way (gpslam_hip_marginals_keep_closure_columns)
-int marginals_assemble(gpslam_hip_handle *h);
-int marginals_border(gpslam_hip_handle *h);
-// the same on the segmented landmark path (marginals_fs.hip): fs_forward at lambda = 0 in the two-launch form, Y into the caller's buffer
-int marginals_fs_forward(gpslam_hip_handle *h, void *Y);
-// gpslam_hip_marginalize_head (fixedlag.hip): the rows and the records [D | O | g] of the current linearisation in the row form (the d = 3
-// GP priors as rows: the head's share of block k is summed from the tables)
-int fixedlag_assemble(gpslam_hip_handle *h);
-// gpslam_hip_iterate_dogleg (dogleg.hip).  dogleg_linearize: the pivot flag cleared, the rows and the error of the current estimate
-// (scal[0]), the estimate remembered (backup_state), the records [D | O | g | B] in the form of gpslam_hip_normal_equations with the
-// gradient copied to gsave.  dogleg_solve: launch_solve at lambda = 0 in the two-launch form.  dogleg_trial: the tail of a
-// Levenberg-Marquardt trial -- retract by column 0 of the level-0 solution and lm_dL (scal[2] = |delta|_inf), error into scal[1]
-int dogleg_linearize(gpslam_hip_handle *h);
-int dogleg_solve(gpslam_hip_handle *h);
-int dogleg_trial(gpslam_hip_handle *h);
-// gpslam_hip_log_determinant (evidence.hip): marginals_border without the kept Z of a handle in column passes
-int evidence_border(gpslam_hip_handle *h);
+// The launchers (api_impl.inc) a feature's translation unit may call; what each does stands at its definition, the default arguments here.
+int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot, bool e32 = false);
+int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g, int pass = 0);
+int launch_solve(gpslam_hip_handle *h, const LaunchMode &m, double lambda);
+int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot);
+int fs_forward(gpslam_hip_handle *h, double lambda, double *y_own = nullptr);

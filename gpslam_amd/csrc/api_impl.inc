@@ -65,132 +65,143 @@ LmArgs<Real, RowT> lm_args(gpslam_hip_handle *h, double lambda) {
   return a;
 }
 
-int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot);
-// pass 0: Jacobian rows + error, 1: error only.  Error partial sums land in h->partial, reduced into scal[slot].
-// e32 (the fp64 instantiation serving an fp32 handle, pass 1): the error pass also deposits its whitened errors as the
-// fp32 right-hand side of the row tables -- the residual of the fp32 mode is always evaluated in fp64.
-// Kernels that do not depend on one another go to the handle's second stream only on graphs of at least this many states: below,
-// everything stays on one stream.  A/B of "never" against "always" (scripts/ab_fork.py, wall clock of run_gn(20), ms per
-// iteration): Plaza2 (4091 states) 0.152 / 0.192; config 5's SO(3) mix 3e4 0.100 / 0.117, 1e5 0.208 / 0.213, 1e6 1.518 / 1.540;
-// config 4's mix 1e5 0.885 / 0.916, 3e5 1.388 / 1.411, 1e6 3.019 / 2.997 -- joining two streams costs more idle time (12 us and up)
-// than the shorter of two concurrent kernels saves, and two kernels side by side slow each other down: only the segmented
-// landmark path (config 4's mix) at 1e6 states gains (0.7 %), and only it forks.
-constexpr int kForkMinStates = 524288;
-int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot, bool e32 = false) {
-  if (!kIsF64 && pass == 1) return impl64::launch_factors(h, m, 1, slot, false);   // an fp32 handle's error is an fp64 error
-  RowT *part = h->partial.as<RowT>();
-  int off = 0;
-  // The factor kernels are independent of one another (disjoint rows, disjoint partial sums).  The GP-prior kernel
-  // runs one register-heavy wave per SIMD and leaves most issue slots empty, the others are light streaming kernels:
-  // they go to a second stream and run underneath it (fork / join with events; joined before the reduction).
-  bool any_meas = false;
-  for (int fk = 0; fk < kNumMeasKinds; fk++) any_meas = any_meas || h->ms[fk].count() > 0;
-  any_meas = any_meas || h->lpri.count() > 0;
-  // GP priors, priors and between factors: ONE launch (k_lin) in the Jacobian pass.  Measurement factors, where a graph
-  // has them, are light streaming kernels: they go to a second stream and run underneath (fork / join with events).
-  const bool merged = (pass == 0) && !h->gp_left.empty() && gp_ngroups(h) <= 1;
-  const LaunchForm form = launch_form(h, m);
-  if (h->pend_upd && !(merged && form.gp != GpForm::Rows)) {   // (defensive: an update is pending and this launch cannot apply it)
-    h->pend_upd = false;
-    h->census[GPSLAM_CENSUS_FLUSH]++;
-    int rcp = launch_retract(h, LaunchMode{}, 2);
-    if (rcp) return rcp;
-  }
+// pose priors (0), velocity priors (1), between factors (2): k_lin's three sets, and the order of their partial sums
+SimpleSet &simple_set(gpslam_hip_handle *h, int kind) { return kind == 0 ? h->pri : (kind == 1 ? h->vpri : h->btw); }
+FacArgs<RowT> fac_args(gpslam_hip_handle *h, const LaunchForm &form, int kind, RowT *partial, bool e32) {
+  SimpleSet &s = simple_set(h, kind);
+  FacArgs<RowT> a;
+  a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride;
+  a.count = s.count(); a.chart = h->cfg.chart;
+  a.idx = s.d_idx.as<int>(); a.meas = s.d_meas.as<double>(); a.sig = s.d_sig.as<double>(); a.row0 = s.d_row0.as<int>();
+  const bool compact = (kind != 1);   // pose priors and between factors: velocity-free rows
+  a.rowLR = compact ? h->rowC.as<RowT>() : h->rowLR.as<RowT>(); a.rowE = compact ? h->rowCE.as<RowT>() : h->rowE.as<RowT>();
+  a.partial = partial; a.rowE32 = e32 ? (compact ? h->rowCE.as<float>() : h->rowE.as<float>()) : nullptr;
+  // BetweenFactor<Pose3> of a launch whose consumer is the structured fused kernel: records instead of compact rows
+  a.rec = (kind == 2 && form.btw_rec) ? h->brec.as<RowT>() : nullptr;
+  return a;
+}
+
+// The factors of one measurement kind, writing nowhere yet: the caller sets the row tables or out_e / out_J, partial, and what its
+// launch adds (rob, gps, pend)
+MeasArgs<RowT> meas_args(gpslam_hip_handle *h, int fk) {
+  MeasSet &s = h->ms[fk];
+  MeasArgs<RowT> a;
+  a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride;
+  a.lmk = h->lmk.as<double>(); a.ld = h->ld; a.count = s.count(); a.chart = h->cfg.chart;
+  a.idx = s.d_idx.as<int>(); a.lm = s.d_lm.as<int>(); a.meas = s.d_meas.as<double>(); a.mw = s.mw;
+  a.sig = s.d_sig.as<double>(); a.coef = s.d_coef.as<double>();
+  a.aux = s.any_aux ? s.d_aux.as<double>() : nullptr; a.aidx = s.any_aux ? s.d_aidx.as<int>() : nullptr;
+  a.sqi = s.sqi.empty() ? nullptr : s.d_sqi.as<double>();
+  a.vw = h->vw; a.row0 = s.d_row0.as<int>();
+  a.rowLR = nullptr; a.rowE = nullptr; a.rowM = nullptr; a.rowLm = nullptr;
+  a.partial = nullptr; a.rowE32 = nullptr; a.out_e = nullptr; a.out_J = nullptr;
+  return a;
+}
+
+// A pending update (Deferred::update) applied by the separate retraction; |delta|_inf into scal[2], as an iteration's own reports it
+int flush_update(gpslam_hip_handle *h) {
+  if (!h->defer.update) return 0;
+  h->defer.update = false;
+  return launch_retract(h, LaunchMode{}, 2);
+}
+
+// One call of launch_factors as its parts below see it.  Every part takes the first free partial-sum slot and returns the next one, or
+// a negative error code.  k_final_reduce adds the slots in index order, so the order of the parts -- GP priors, pose priors, velocity
+// priors, between factors, the measurement kinds in FKind order, closures, state Gaussians, border Gaussians, landmark priors -- is
+// the order of the sum.
+struct FactorPass {
+  gpslam_hip_handle *h;
+  const LaunchMode &m;
+  const LaunchForm form;
+  const int pass;           // 0: Jacobian rows + error, 1: error only
+  const bool e32;           // the error pass also stores its whitened errors as the fp32 right-hand side of the row tables
   // SE(3) chains whose GP priors travel as structured records: the interpolated measurement factors read their interval's record
   // (Jinv, Jinv Ad, the finite-difference block: MeasArgs::gps) instead of forming the same blocks again, so they run BEHIND k_lin
-  const bool meas_rec = (pass == 0) && form.gp == GpForm::Se3Rec && any_meas;
-  // (round 6: only on large graphs, kForkMinStates -- Plaza2's timeline: k_lin 7 us beside k_meas 10 us, then 12 us of nothing before
-  //  the reduction starts)
-  const bool fork = (pass == 0) && !h->gp_left.empty() && h->aux_stream != nullptr && (merged ? any_meas : true) && !meas_rec && h->N >= kForkMinStates && h->fs.active;
-  hipStream_t side = fork ? h->aux_stream : h->stream;
-  if (fork) {
-    HIPCHK(hipEventRecord(h->ev_fork, h->stream));
-    HIPCHK(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
+  bool meas_rec = false;
+  hipStream_t side = nullptr;   // where the light kernels go: the handle's second stream if this launch forks, else its stream
+  RowT *part(int off) const { return h->partial.as<RowT>() + off; }
+};
+// The merged launch applied a pending update: what k_meas beside it (d = 3 chains) needs to see the same states -- the update
+// without a buffer to write (k_meas owns no state) and the buffers that launch READ (by now the handle's other pair)
+struct PendBeside {
+  bool applied = false;
+  PendUpd u;
+  const double *pose = nullptr, *vel = nullptr;
+};
+
+// GP priors, pose priors, velocity priors and between factors of a Jacobian pass over one Qc: ONE launch (k_lin).  Its extra
+// workgroup reduces the previous retraction's maxima if they were deferred.  In its record forms on an fp64 handle it applies a
+// pending update: every state goes into the other buffer, the two change places, and `beside` says so.
+int launch_lin_merged(const FactorPass &c, int off, PendBeside &beside) {
+  gpslam_hip_handle *h = c.h;
+  LinArgs<RowT> la;
+  const Deferred::Sums red = h->defer.dmax.take();
+  la.red_in = red.n > 0 ? h->partial2.as<double>() : nullptr;
+  la.red_n = red.n; la.red_out = h->scal.as<double>() + red.slot;
+  la.gp = gp_args(h, c.m, c.part(off), c.e32, gp_ngroups(h) == 1 ? 0 : -1);
+  la.nb_gp = nblocks(la.gp.count, 128);
+  off += la.nb_gp;
+  for (int kind = 0; kind < 3; kind++) {
+    la.fac[kind] = fac_args(h, c.form, kind, c.part(off), c.e32);
+    la.nb[kind] = nblocks(simple_set(h, kind).count(), 128);
+    off += la.nb[kind];
   }
-  SimpleSet *sets[3] = {&h->pri, &h->vpri, &h->btw};
-  auto fac_args = [&](int kind, RowT *partial) {
-    SimpleSet &s = *sets[kind];
-    FacArgs<RowT> a;
-    a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride;
-    a.count = s.count(); a.chart = h->cfg.chart;
-    a.idx = s.d_idx.as<int>(); a.meas = s.d_meas.as<double>(); a.sig = s.d_sig.as<double>(); a.row0 = s.d_row0.as<int>();
-    const bool compact = (kind != 1);   // pose priors and between factors: velocity-free rows
-    a.rowLR = compact ? h->rowC.as<RowT>() : h->rowLR.as<RowT>(); a.rowE = compact ? h->rowCE.as<RowT>() : h->rowE.as<RowT>();
-    a.partial = partial; a.rowE32 = e32 ? (compact ? h->rowCE.as<float>() : h->rowE.as<float>()) : nullptr;
-    // BetweenFactor<Pose3> of a launch whose consumer is the structured fused kernel: records instead of compact rows
-    a.rec = (kind == 2 && form.btw_rec) ? h->brec.as<RowT>() : nullptr;
-    return a;
-  };
-  // the previous retraction's maxima, if their reduction was deferred: into this launch (k_lin), or a launch of their own
-  bool pend_applied = false;            // this call's k_lin applies a pending update: k_meas beside it (d = 3 chains) does the same
-  PendUpd pend_u;
-  const double *pend_pose = nullptr, *pend_vel = nullptr;
-  const bool red_here = merged && h->pend_dmax_n > 0;
-  if (h->pend_dmax_n > 0 && !merged) {
-    k_final_reduce<double><<<dim3(1), dim3(256), 0, h->stream>>>(h->partial2.as<double>(), h->pend_dmax_n, h->scal.as<double>() + h->pend_dmax_slot, 1);
-    h->pend_dmax_n = 0;
+  const dim3 grid(la.nb_gp + la.nb[0] + la.nb[1] + la.nb[2] + (la.red_in ? 1 : 0)), t(128);
+  const bool pend = kIsF64 && h->defer.update && la.gp.gps != nullptr;     // the previous iteration's update is applied by THIS launch
+  if (pend) {
+    const size_t np = (size_t)h->pd * h->stride * sizeof(double), nv = (size_t)h->d * h->stride * sizeof(double);
+    HIPCHK(h->pose_bak.reserve(np));
+    HIPCHK(h->vel_bak.reserve(nv));
+    PendUpd u;
+    u.dx = h->lv[0].x.as<double>(); u.pose_w = h->pose_bak.as<double>(); u.vel_w = h->vel_bak.as<double>();
+    u.flag = h->flag.as<int>(); u.chart = h->cfg.chart; u.last = h->N - 1;
+    la.gp.pend = u;
+    for (int kind = 0; kind < 3; kind++) la.fac[kind].pend = u;
+    beside.applied = true;
+    beside.u = u;
+    beside.u.pose_w = nullptr; beside.u.vel_w = nullptr;
+    beside.pose = h->pose.as<double>(); beside.vel = h->vel.as<double>();
   }
-  if (merged) {
-    LinArgs<RowT> la;
-    la.red_in = red_here ? h->partial2.as<double>() : nullptr;
-    la.red_n = h->pend_dmax_n; la.red_out = h->scal.as<double>() + h->pend_dmax_slot;
-    h->pend_dmax_n = 0;
-    la.gp = gp_args(h, m, part + off, e32, gp_ngroups(h) == 1 ? 0 : -1);
-    la.nb_gp = nblocks(la.gp.count, 128);
-    off += la.nb_gp;
-    int total = la.nb_gp;
-    for (int kind = 0; kind < 3; kind++) {
-      la.fac[kind] = fac_args(kind, part + off);
-      la.nb[kind] = sets[kind]->count() > 0 ? nblocks(sets[kind]->count(), 128) : 0;
-      off += la.nb[kind];
-      total += la.nb[kind];
-    }
-    const bool pend = kIsF64 && h->pend_upd && la.gp.gps != nullptr;     // the previous iteration's update is applied by THIS launch
-    pend_applied = pend;
-    if (pend) {
-      const size_t np = (size_t)h->pd * h->stride * sizeof(double), nv = (size_t)h->d * h->stride * sizeof(double);
-      HIPCHK(h->pose_bak.reserve(np));
-      HIPCHK(h->vel_bak.reserve(nv));
-      PendUpd u;
-      u.dx = h->lv[0].x.as<double>(); u.pose_w = h->pose_bak.as<double>(); u.vel_w = h->vel_bak.as<double>();
-      u.flag = h->flag.as<int>(); u.chart = h->cfg.chart; u.last = h->N - 1;
-      la.gp.pend = u;
-      for (int kind = 0; kind < 3; kind++) la.fac[kind].pend = u;
-      pend_u = u;
-      pend_u.pose_w = nullptr; pend_u.vel_w = nullptr;     // (k_meas owns nothing)
-      pend_pose = h->pose.as<double>(); pend_vel = h->vel.as<double>();   // the buffer this launch READS (the swap below makes it the other one)
-    }
-    dispatch_mf(h->mf, [&](auto tag) {
-      constexpr int MF = decltype(tag)::value;
-      const bool vp = la.nb[1] > 0;
-      if constexpr ((MF == POSE3 || MF == POSE2 || MF == ROT3 || MF == LINEAR3) && kIsF64) {
-        if (la.gp.gps != nullptr) {      // structured GP records (never on a world-velocity chain: make_plan)
-          if (vp) { h->census[GPSLAM_CENSUS_LIN_REC_VP]++; k_lin<RowT, MF, false, true, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
-          else { h->census[GPSLAM_CENSUS_LIN_REC]++; k_lin<RowT, MF, false, false, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
-          if (pend) {                    // the launch wrote every state into the other buffer: that one is current from here on
-            h->census[GPSLAM_CENSUS_LIN_PEND]++;
-            std::swap(h->pose, h->pose_bak);
-            std::swap(h->vel, h->vel_bak);
-            h->pend_upd = false;
-          }
-          return;
+  dispatch_mf(h->mf, [&](auto tag) {
+    constexpr int MF = decltype(tag)::value;
+    const bool vp = la.nb[1] > 0;
+    if constexpr ((MF == POSE3 || MF == POSE2 || MF == ROT3 || MF == LINEAR3) && kIsF64) {
+      if (la.gp.gps != nullptr) {      // structured GP records (never on a world-velocity chain: make_plan)
+        if (vp) { h->census[GPSLAM_CENSUS_LIN_REC_VP]++; k_lin<RowT, MF, false, true, true><<<grid, t, 0, h->stream>>>(la); }
+        else { h->census[GPSLAM_CENSUS_LIN_REC]++; k_lin<RowT, MF, false, false, true><<<grid, t, 0, h->stream>>>(la); }
+        if (pend) {                    // the launch wrote every state into the other buffer: that one is current from here on
+          h->census[GPSLAM_CENSUS_LIN_PEND]++;
+          std::swap(h->pose, h->pose_bak);
+          std::swap(h->vel, h->vel_bak);
+          h->defer.update = false;
         }
+        return;
       }
-      if (MF == POSE3 && h->vw) {
-        if (vp) { h->census[GPSLAM_CENSUS_LIN_VW_VP]++; k_lin<RowT, MF, true, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
-        else { h->census[GPSLAM_CENSUS_LIN_VW]++; k_lin<RowT, MF, true, false><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
-      } else {
-        if (vp) { h->census[GPSLAM_CENSUS_LIN_ROWS_VP]++; k_lin<RowT, MF, false, true><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
-        else { h->census[GPSLAM_CENSUS_LIN_ROWS]++; k_lin<RowT, MF, false, false><<<dim3(total + (red_here ? 1 : 0)), dim3(128), 0, h->stream>>>(la); }
-      }
-    });
-  } else {
-  for (int grp = 0; grp < std::max(gp_ngroups(h), h->gp_left.empty() ? 0 : 1); grp++) {   // one launch per distinct Qc
-    GpArgs<RowT> a = gp_args(h, m, part + off, e32, gp_ngroups(h) >= 1 ? grp : -1);
+    }
+    if (MF == POSE3 && h->vw) {
+      if (vp) { h->census[GPSLAM_CENSUS_LIN_VW_VP]++; k_lin<RowT, MF, true, true><<<grid, t, 0, h->stream>>>(la); }
+      else { h->census[GPSLAM_CENSUS_LIN_VW]++; k_lin<RowT, MF, true, false><<<grid, t, 0, h->stream>>>(la); }
+    } else {
+      if (vp) { h->census[GPSLAM_CENSUS_LIN_ROWS_VP]++; k_lin<RowT, MF, false, true><<<grid, t, 0, h->stream>>>(la); }
+      else { h->census[GPSLAM_CENSUS_LIN_ROWS]++; k_lin<RowT, MF, false, false><<<grid, t, 0, h->stream>>>(la); }
+    }
+  });
+  return off;
+}
+
+// The same factors where k_lin does not serve (an error pass, several Qc, no GP prior at all): one k_gp per Qc group, each with its
+// U, then one k_simple per set that has factors, those on the side stream.  Deferred maxima of the previous retraction get a launch
+// of their own in front.
+int launch_lin_groups(const FactorPass &c, int off) {
+  gpslam_hip_handle *h = c.h;
+  const Deferred::Sums red = h->defer.dmax.take();
+  if (red.n > 0) k_final_reduce<double><<<dim3(1), dim3(256), 0, h->stream>>>(h->partial2.as<double>(), red.n, h->scal.as<double>() + red.slot, 1);
+  for (int grp = 0; grp < std::max(gp_ngroups(h), h->gp_left.empty() ? 0 : 1); grp++) {
+    GpArgs<RowT> a = gp_args(h, c.m, c.part(off), c.e32, gp_ngroups(h) >= 1 ? grp : -1);
     const int nb = nblocks(a.count, 128);
     dispatch_mf(h->mf, [&](auto tag) {
       constexpr int MF = decltype(tag)::value;
-      if (pass == 0) {
+      if (c.pass == 0) {
         h->census[GPSLAM_CENSUS_LIN_GROUPS]++;
         launch_gp_rows<MF>(h, a, nb);
       } else {
@@ -200,54 +211,51 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
     off += nb;
   }
   for (int kind = 0; kind < 3; kind++) {
-    SimpleSet &s = *sets[kind];
-    if (s.count() == 0) continue;
-    FacArgs<RowT> a = fac_args(kind, part + off);
+    if (simple_set(h, kind).count() == 0) continue;
+    FacArgs<RowT> a = fac_args(h, c.form, kind, c.part(off), c.e32);
     const int nb = nblocks(a.count, 128);
     dispatch_mf(h->mf, [&](auto tag) {
       constexpr int MF = decltype(tag)::value;
       const dim3 g(nb), t(128);
-      if (pass == 0) {
-        if (kind == 0) k_simple<RowT, MF, 0, true><<<g, t, 0, side>>>(a);
-        else if (kind == 1) k_simple<RowT, MF, 1, true><<<g, t, 0, side>>>(a);
-        else k_simple<RowT, MF, 2, true><<<g, t, 0, side>>>(a);
+      if (c.pass == 0) {
+        if (kind == 0) k_simple<RowT, MF, 0, true><<<g, t, 0, c.side>>>(a);
+        else if (kind == 1) k_simple<RowT, MF, 1, true><<<g, t, 0, c.side>>>(a);
+        else k_simple<RowT, MF, 2, true><<<g, t, 0, c.side>>>(a);
       } else {
-        if (kind == 0) k_simple<RowT, MF, 0, false><<<g, t, 0, side>>>(a);
-        else if (kind == 1) k_simple<RowT, MF, 1, false><<<g, t, 0, side>>>(a);
-        else k_simple<RowT, MF, 2, false><<<g, t, 0, side>>>(a);
+        if (kind == 0) k_simple<RowT, MF, 0, false><<<g, t, 0, c.side>>>(a);
+        else if (kind == 1) k_simple<RowT, MF, 1, false><<<g, t, 0, c.side>>>(a);
+        else k_simple<RowT, MF, 2, false><<<g, t, 0, c.side>>>(a);
       }
     });
     off += nb;
   }
-  }
+  return off;
+}
+
+// The measurement kinds in FKind order, one k_meas each on the side stream -- interpolated GPS as 16-double lines (k_gps_lines) where
+// the launch's form says so
+int launch_meas_kinds(const FactorPass &c, int off, const PendBeside &beside) {
+  gpslam_hip_handle *h = c.h;
   for (int fk = 0; fk < kNumMeasKinds; fk++) {
     MeasSet &s = h->ms[fk];
     if (s.count() == 0) continue;
-    MeasArgs<RowT> a;
-    a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride;
-    a.lmk = h->lmk.as<double>(); a.ld = h->ld; a.count = s.count(); a.chart = h->cfg.chart;
-    a.idx = s.d_idx.as<int>(); a.lm = s.d_lm.as<int>(); a.meas = s.d_meas.as<double>(); a.mw = s.mw;
-    a.sig = s.d_sig.as<double>(); a.coef = s.d_coef.as<double>();
-    a.aux = s.any_aux ? s.d_aux.as<double>() : nullptr; a.aidx = s.any_aux ? s.d_aidx.as<int>() : nullptr;
-    a.sqi = s.sqi.empty() ? nullptr : s.d_sqi.as<double>();
+    MeasArgs<RowT> a = meas_args(h, fk);
     a.rob = s.rob.empty() ? nullptr : s.d_rob.as<double>();
-    a.out_w = (m.weights && a.rob) ? s.d_w.as<RowT>() : nullptr;
-    a.vw = h->vw;
-    a.row0 = s.d_row0.as<int>();
+    a.out_w = (c.m.weights && a.rob) ? s.d_w.as<RowT>() : nullptr;
     a.rowLR = h->rowLR.as<RowT>(); a.rowE = h->rowE.as<RowT>(); a.rowM = h->rowM.as<RowT>(); a.rowLm = h->rowLm.as<int>();
-    a.partial = part + off; a.rowE32 = e32 ? h->rowE.as<float>() : nullptr; a.out_e = nullptr; a.out_J = nullptr;
-    if (meas_rec) { a.gps = h->gps.as<RowT>(); a.gpidx = h->gpidx.as<int>(); }
-    if (pend_applied && !meas_rec) {   // beside k_lin, not behind it: the old buffer + the update
+    a.partial = c.part(off); a.rowE32 = c.e32 ? h->rowE.as<float>() : nullptr;
+    if (c.meas_rec) { a.gps = h->gps.as<RowT>(); a.gpidx = h->gpidx.as<int>(); }
+    if (beside.applied && !c.meas_rec) {   // beside k_lin, not behind it: the old buffer + the update
       if (!s.two) return fail(h, GPSLAM_E_INVALID, "internal: a pending update met a measurement kind that cannot apply it");
-      a.pose = pend_pose; a.vel = pend_vel; a.pend = pend_u;
+      a.pose = beside.pose; a.vel = beside.vel; a.pend = beside.u;
     }
     const int nb = nblocks(a.count, 128);
+    off += nb;
     if constexpr (kIsF64) {
-      if (meas_rec && form.lines && fk == FK_INTERP_GPS) {   // 16-double lines for k_fused_level0<4> instead of 24-column rows
+      if (c.meas_rec && c.form.lines && fk == FK_INTERP_GPS) {   // 16-double lines for k_fused_level0<4> instead of 24-column rows
         a.rowI = h->rowI.as<RowT>(); a.row0 = s.d_irow0.as<int>();
         a.rowLR = nullptr; a.rowE = nullptr; a.rowM = nullptr; a.rowLm = nullptr;
-        launch_gps_lines_k(h->census.v, a, nb, side);
-        off += nb;
+        launch_gps_lines_k(h->census.v, a, nb, c.side);
         continue;
       }
     }
@@ -255,60 +263,98 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
       constexpr int MF = decltype(tag)::value;
       dispatch_fk(fk, [&](auto ftag) {
         constexpr int FK = decltype(ftag)::value;
-        if (pass == 0) {
+        if (c.pass == 0) {
           if (FK == FK_INTERP_GPS) h->census[a.gps != nullptr ? GPSLAM_CENSUS_MEAS_REC : GPSLAM_CENSUS_MEAS_SELF]++;
-          k_meas<RowT, MF, FK, true><<<dim3(nb), dim3(128), 0, side>>>(a);
+          k_meas<RowT, MF, FK, true><<<dim3(nb), dim3(128), 0, c.side>>>(a);
         }
-        else k_meas<RowT, MF, FK, false><<<dim3(nb), dim3(128), 0, side>>>(a);
+        else k_meas<RowT, MF, FK, false><<<dim3(nb), dim3(128), 0, c.side>>>(a);
       });
     });
-    off += nb;
   }
-  if (kIsF64 && h->clo.n > 0) {   // loop closures: records [A_i | A_j | r] (Jacobian pass) and their error
-    closures_eval(h, m, pass, reinterpret_cast<double *>(part + off), side);   // (RowT == double here)
+  return off;
+}
+
+// What has no row of the chain's tables to itself, on the side stream (fp64 handles only; RowT == Real == double where they run):
+// loop closures -- records [A_i | A_j | r] in a Jacobian pass, and their error (one slot); joint Gaussians on one state
+// (fixedlag.hip: rows [A | 0] and their error); joint Gaussians on one state and the landmarks (residuals and their error, one
+// slot); landmark priors (no Jacobian rows: on an fp32 handle their error belongs to the fp64 error pass alone)
+int launch_other_factors(const FactorPass &c, int off) {
+  gpslam_hip_handle *h = c.h;
+  if (kIsF64 && h->clo.n > 0) {
+    closures_eval(h, c.m, c.pass, reinterpret_cast<double *>(c.part(off)), c.side);
     off += 1;
   }
-  if (kIsF64 && h->sg.count() > 0) {   // joint Gaussians on one state (fixedlag.hip): rows [A | 0] and their error
-    state_gauss_eval(h, pass, reinterpret_cast<double *>(part + off), side);   // (RowT == double here)
+  if (kIsF64 && h->sg.count() > 0) {
+    state_gauss_eval(h, c.pass, reinterpret_cast<double *>(c.part(off)), c.side);
     off += nblocks(h->sg.count(), 128);
   }
-  if (kIsF64 && h->bg.count() > 0) {   // joint Gaussians on one state and the landmarks (fixedlag.hip): residuals and their error
-    border_gauss_eval(h, pass, reinterpret_cast<double *>(part + off), side);
+  if (kIsF64 && h->bg.count() > 0) {
+    border_gauss_eval(h, c.pass, reinterpret_cast<double *>(c.part(off)), c.side);
     off += 1;
   }
-  // (landmark priors have no Jacobian rows: on an fp32 handle their error belongs to the fp64 error pass alone)
-  if (!kIsF64) {
-  } else if (h->lpri.count() > 0 && h->fs.active) {   // tens of thousands of landmark priors: grid-stride, one partial per block
+  if (kIsF64 && h->lpri.count() > 0 && h->fs.active) {   // tens of thousands of landmark priors: grid-stride, one partial per block
     const int nbl = std::min(nblocks(h->lpri.count(), 256), 256);
-    k_fs_lmprior_err<RowT><<<dim3(nbl), dim3(256), 0, side>>>(h->lmk.as<double>(), h->lpri.d_idx.as<int>(), h->lpri.d_meas.as<double>(),
-                                                               h->lpri.d_sig.as<double>(), h->lpri.count(), h->ld, part + off);
+    k_fs_lmprior_err<RowT><<<dim3(nbl), dim3(256), 0, c.side>>>(h->lmk.as<double>(), h->lpri.d_idx.as<int>(), h->lpri.d_meas.as<double>(),
+                                                                 h->lpri.d_sig.as<double>(), h->lpri.count(), h->ld, c.part(off));
     off += nbl;
-  } else if (h->lpri.count() > 0) {
+  } else if (kIsF64 && h->lpri.count() > 0) {
     LmArgs<Real, RowT> a = lm_args(h, 0.0);
-    a.partial = reinterpret_cast<Real *>(part + off);   // (RowT == Real here)
-    k_lmprior_err<Real, RowT><<<dim3(1), dim3(128), 0, side>>>(a);
+    a.partial = reinterpret_cast<Real *>(c.part(off));
+    k_lmprior_err<Real, RowT><<<dim3(1), dim3(128), 0, c.side>>>(a);
     off += 1;
   }
+  return off;
+}
+
+// The light factor kernels go to the handle's second stream, underneath the chain's, only on the segmented landmark path
+// (fs.active) and only on graphs of at least this many states: everywhere else everything stays on one stream.  A/B of "never"
+// against "always" (scripts/ab_fork.py, wall clock of run_gn(20), ms per iteration): Plaza2 (4091 states) 0.152 / 0.192 -- its
+// timeline: k_lin 7 us beside k_meas 10 us, then 12 us of nothing before the reduction starts; config 5's SO(3) mix 3e4 0.100 /
+// 0.117, 1e5 0.208 / 0.213, 1e6 1.518 / 1.540; config 4's mix 1e5 0.885 / 0.916, 3e5 1.388 / 1.411, 1e6 3.019 / 2.997 -- joining two
+// streams costs more idle time (12 us and up) than the shorter of two concurrent kernels saves, and two kernels side by side slow each
+// other down: only the segmented landmark path (config 4's mix) at 1e6 states gains (0.7 %), and only it forks.
+constexpr int kForkMinStates = 524288;
+// pass 0: Jacobian rows + error, 1: error only.  Error partial sums land in h->partial, reduced into scal[slot] (or left to this
+// iteration's k_retract: LaunchMode::defer_error).  An fp32 handle's residual is always evaluated in fp64: its pass 1 IS impl64's, and
+// its pass 0 ends in impl64's pass 1 with e32 -- whitened errors into the fp32 rowE, the error into scal[slot].
+int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot, bool e32) {
+  if (!kIsF64 && pass == 1) return impl64::launch_factors(h, m, 1, slot, false);
+  FactorPass c{h, m, launch_form(h, m), pass, e32};
+  bool any_meas = h->lpri.count() > 0;
+  for (const MeasSet &s : h->ms) any_meas = any_meas || s.count() > 0;
+  const bool chain = !h->gp_left.empty();
+  const bool merged = pass == 0 && chain && gp_ngroups(h) <= 1;   // k_lin; else one launch per Qc group and per set
+  c.meas_rec = pass == 0 && c.form.gp == GpForm::Se3Rec && any_meas;
+  int rc;
+  if (h->defer.update && !(merged && c.form.gp != GpForm::Rows)) {   // (defensive: an update is pending and this launch cannot apply it)
+    h->census[GPSLAM_CENSUS_FLUSH]++;
+    if ((rc = flush_update(h))) return rc;
+  }
+  // fork: the factor kernels are independent of one another (disjoint rows, disjoint partial sums) -- unless k_meas reads k_lin's records
+  const bool fork = pass == 0 && chain && h->aux_stream != nullptr && (any_meas || !merged) && !c.meas_rec && h->N >= kForkMinStates && h->fs.active;
+  c.side = fork ? h->aux_stream : h->stream;
   if (fork) {
+    HIPCHK(hipEventRecord(h->ev_fork, h->stream));
+    HIPCHK(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
+  }
+  PendBeside beside;
+  int off = merged ? launch_lin_merged(c, 0, beside) : launch_lin_groups(c, 0);
+  if (off >= 0) off = launch_meas_kinds(c, off, beside);
+  if (off >= 0) off = launch_other_factors(c, off);
+  if (off < 0) return off;
+  if (fork) {   // joined before the reduction
     HIPCHK(hipEventRecord(h->ev_join, h->aux_stream));
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_join, 0));
   }
-  if (!kIsF64) {   // fp32 rows are in place; now the fp64 residual: whitened errors -> rowE (fp32), error -> scal[slot]
-    HIPCHK(hipGetLastError());
-    return impl64::launch_factors(h, m, 1, slot, true);
-  }
-  if (m.defer_error && kIsF64) {   // (RowT == double here: an fp32 handle's error comes out of the nested fp64 pass)
-    h->pend_err_n = off; h->pend_err_slot = slot;     // summed by the extra workgroup of this iteration's k_retract
-  } else {
-    k_final_reduce<RowT><<<dim3(1), dim3(256), 0, h->stream>>>(part, off, h->scal.as<double>() + slot, 0);
-  }
+  if (kIsF64 && m.defer_error) h->defer.err = {off, slot};     // summed by the extra workgroup of this iteration's k_retract
+  else if (kIsF64) k_final_reduce<RowT><<<dim3(1), dim3(256), 0, h->stream>>>(c.part(0), off, h->scal.as<double>() + slot, 0);
   HIPCHK(hipGetLastError());
-  return 0;
+  return kIsF64 ? 0 : impl64::launch_factors(h, m, 1, slot, true);   // fp32 rows are in place; now the fp64 residual
 }
 
 // pass (closures in column passes, clo.P > 1): which slice of the closures' columns the records take; pass == clo.P: the final
 // pass, whose right-hand sides are U^T Y alone
-int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g, int pass = 0) {
+int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g, int pass) {
   AsmArgs<Real, RowT> a;
   a.N = h->N; a.R = h->R;
   a.rowptr = h->rowptr.as<int>();
@@ -629,8 +675,9 @@ void launch_fat_back(const FsArgs<Real, RowT> &a, const FatLevel &fl, hipStream_
 
 // forward half: segment interiors -> fat blocks -> cyclic-reduction levels (down to one block, or to the two end blocks of a
 // piece of a split chain)
-// y_own: the sweep and the Schur complements in two launches through THIS Y buffer, whatever the plan's choice (marginals_fs_forward)
-int fs_forward(gpslam_hip_handle *h, double lambda, Real *y_own = nullptr) {
+// y_own: the sweep and the Schur complements in two launches through THIS Y buffer, whatever the plan's choice (marginals_fs.hip: the
+// half-swept border Y = L^-1 G into the marginals' own buffer, zeroed by the caller -- a fused_sweep plan has none)
+int fs_forward(gpslam_hip_handle *h, double lambda, Real *y_own) {
   FatSepPlan &p = h->fs;
   FsArgs<Real, RowT> a = fs_args(h, lambda);
   const bool fused_sweep = p.fused_sweep && !y_own;
@@ -987,10 +1034,9 @@ int fs_build(gpslam_hip_handle *h, const std::vector<int> &touch_lo, const std::
 
 // Closures in column passes (clo.P > 1): the caller's assembly carried slice 0.  Every pass is the same factorisation at the same
 // lambda; the records are reassembled in front of each one because the elimination works in place.  The marginals run the same
-// passes at lambda = 0 with keep_z (every pass's slice of Z = A^-1 U^T copied into h->mg.Z behind its backward sweep) and without
-// the landmark solve (the landmark reduction alone ends them: the states stay).  Leaves W = U [X | Z] in clo.W and the corrected
-// landmark columns in the leading columns of the level-0 solution.
-int launch_solve_passes(gpslam_hip_handle *h, const LaunchMode &m, double lambda, bool keep_z, bool solve_landmarks) {
+// passes at lambda = 0 with m.keep_z (every pass's slice of Z = A^-1 U^T copied into h->mg.Z behind its backward sweep) and
+// m.lm_reduce_only.  Leaves W = U [X | Z] in clo.W and the corrected landmark columns in the leading columns of the level-0 solution.
+int launch_solve_passes(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
   int rc;
   const int P = h->clo.P;
   LaunchMode later = m;       // (a timed iteration stamps the level-0 launch of pass 0 alone)
@@ -999,24 +1045,26 @@ int launch_solve_passes(gpslam_hip_handle *h, const LaunchMode &m, double lambda
     if (p > 0 && (rc = launch_assemble(h, m, false, p))) return rc;
     if ((rc = launch_forward(h, p == 0 ? m : later, lambda))) return rc;
     if ((rc = launch_backward(h, nullptr))) return rc;
-    closures_collect(h, p, keep_z);   // (behind the last pass: the wide solve for Y)
+    closures_collect(h, p, m.keep_z);   // (behind the last pass: the wide solve for Y)
   }
   if ((rc = launch_assemble(h, m, false, P))) return rc;
   if ((rc = launch_forward(h, later, lambda))) return rc;
   if ((rc = launch_backward(h, nullptr))) return rc;
   if ((rc = closures_add(h))) return rc;
-  return solve_landmarks ? launch_landmarks(h, lambda) : launch_landmarks_reduce(h, lambda);
+  return m.lm_reduce_only ? launch_landmarks_reduce(h, lambda) : launch_landmarks(h, lambda);
 }
 
-// keep_z, solve_landmarks: as launch_solve_passes (the marginals: marginals_border)
-int launch_solve(gpslam_hip_handle *h, const LaunchMode &m, double lambda, bool keep_z = false, bool solve_landmarks = true) {
+// The solve behind an assembly: forward, backward, the closures' correction, the landmarks.  With m.lm_reduce_only (the marginals, the
+// evidence: at lambda = 0) it leaves the solver's right-hand sides -- the closure columns Z = A^-1 J_c^T, the landmark columns
+// corrected for the closures, the landmark Schur complement S of the whole chain -- and the states stay.
+int launch_solve(gpslam_hip_handle *h, const LaunchMode &m, double lambda) {
   int rc;
   if (h->fs.active) return fs_solve(h, lambda);
-  if (h->clo.P > 1) return launch_solve_passes(h, m, lambda, keep_z, solve_landmarks);
+  if (h->clo.P > 1) return launch_solve_passes(h, m, lambda);
   if ((rc = launch_forward(h, m, lambda))) return rc;
   if ((rc = launch_backward(h, nullptr))) return rc;
   if ((rc = closures_correct(h))) return rc;
-  return solve_landmarks ? launch_landmarks(h, lambda) : launch_landmarks_reduce(h, lambda);
+  return m.lm_reduce_only ? launch_landmarks_reduce(h, lambda) : launch_landmarks(h, lambda);
 }
 
 // k_retract over the local states: its arguments and its grid (one workgroup more when this iteration's error partial sums are
@@ -1025,15 +1073,14 @@ RetractArgs<Real> retract_args(gpslam_hip_handle *h, int &grid) {
   RetractArgs<Real> a;
   a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride; a.N = h->N; a.R = h->R;
   a.chart = h->cfg.chart; a.first = 0; a.x = h->lv[0].x.as<Real>(); a.partial = h->partial2.as<Real>(); a.flag = h->flag.as<int>();
-  const bool red = h->pend_err_n > 0;
-  a.red_in = red ? h->partial.as<double>() : nullptr; a.red_n = h->pend_err_n; a.red_out = h->scal.as<double>() + h->pend_err_slot;
-  grid = nblocks(h->N, 128) + (red ? 1 : 0);
+  const Deferred::Sums red = h->defer.err.take();
+  a.red_in = red.n > 0 ? h->partial.as<double>() : nullptr; a.red_n = red.n; a.red_out = h->scal.as<double>() + red.slot;
+  grid = nblocks(h->N, 128) + (red.n > 0 ? 1 : 0);
   return a;
 }
 void launch_retract_k(gpslam_hip_handle *h) {
   int grid;
   const RetractArgs<Real> a = retract_args(h, grid);
-  h->pend_err_n = 0;
   h->census[GPSLAM_CENSUS_RETRACT]++;
   dispatch_mf(h->mf, [&](auto tag) {
     constexpr int MF = decltype(tag)::value;
@@ -1044,7 +1091,7 @@ void launch_retract_k(gpslam_hip_handle *h) {
 int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot) {
   const int nb = nblocks(h->N, 128);
   launch_retract_k(h);
-  if (m.defer_maxima && h->nl == 0) { h->pend_dmax_n = nb; h->pend_dmax_slot = slot; }   // reduced by the next linearisation's launch
+  if (m.defer_maxima && h->nl == 0) h->defer.dmax = {nb, slot};   // reduced by the next linearisation's launch
   else k_final_reduce<Real><<<dim3(1), dim3(256), 0, h->stream>>>(h->partial2.as<Real>(), nb, h->scal.as<double>() + slot, 1);
   if (h->nl > 0 && h->fs.active) {
     const int nbl = std::min(nblocks(h->nl, 256), 1024);
@@ -1075,14 +1122,14 @@ LaunchMode gn_mode(const gpslam_hip_handle *h, bool timed, bool eval_after) {
 int enqueue_gn(gpslam_hip_handle *h, const LaunchMode &m, double lambda, bool timed, bool eval_after, bool defer_retract) {
   int rc;
   if (timed) HIPCHK(hipEventRecord(h->ev[0], h->stream));
-  if ((rc = launch_factors(h, m, 0, 0))) { h->pend_err_n = 0; return rc; }
+  if ((rc = launch_factors(h, m, 0, 0))) { h->defer.err.n = 0; return rc; }
   if (timed) HIPCHK(hipEventRecord(h->ev[1], h->stream));
   if (!m.fused && (rc = launch_assemble(h, m, false))) return rc;   // (fused: the assembly happens inside the level-0 elimination)
   if (timed) HIPCHK(hipEventRecord(h->ev[2], h->stream));
   if ((rc = launch_solve(h, m, lambda))) return rc;
   if (timed) HIPCHK(hipEventRecord(h->ev[3], h->stream));
   if (defer_retract) {                                  // run_gn, not the last iteration: the NEXT k_lin applies this update
-    h->pend_upd = true;
+    h->defer.update = true;
     if (timed) HIPCHK(hipEventRecord(h->ev[4], h->stream));
     return 0;
   }
@@ -1398,7 +1445,7 @@ int size_workspace(gpslam_hip_handle *h, int npart) {
   npart = std::max(npart, std::max(nblocks(N, 128), 3 * nblocks(N * b, 256))) + 4200;   // (3 x: launch_dot3's three partial arrays)
   HIPCHK(h->partial.reserve((size_t)npart * sizeof(double)));   // the fp64 error pass of an fp32 handle uses it as well
   HIPCHK(h->partial2.reserve((size_t)(nblocks(N, 128) + 8) * sizeof(double)));
-  h->pend_err_n = 0; h->pend_dmax_n = 0;
+  h->defer.clear();
   HIPCHK(h->gsave.reserve((size_t)N * b * sizeof(Real)));
   HIPCHK(h->gsave2.reserve((size_t)(N + 1) * b * sizeof(Real)));   // (LM through the fused kernel: separator parts)
   HIPCHK(hipMemsetAsync(h->gsave2.p, 0, (size_t)(N + 1) * b * sizeof(Real), h->stream));
@@ -1540,8 +1587,9 @@ int make_plan(gpslam_hip_handle *h, const RowLayout &lay) {
     bool ok = p.gp_rec != GpForm::Rows && h->lv.size() >= 2 && !sharded(h) && h->nl == 0 && h->clo.n == 0 && gp_ngroups(h) <= 1 &&
               ngp == N - 1 && N >= 2;      // (lv.size() >= 2: the fused level 0, whose K1 writes the records, runs)
     // measurement factors: on SE(3) record chains k_meas runs BEHIND k_lin on the same stream (it reads the interval's record) and
-    // so behind the buffer swap -- it sees the updated states; the d = 3 chains run it beside k_lin on a second stream
-    // -- those kinds that read two states (the interpolated ones) apply the pending update themselves from the old buffer
+    // so behind the buffer swap -- it sees the updated states; on the d = 3 chains it reads nothing k_lin writes (a launch that
+    // forks puts it on the second stream) -- the kinds that read two states (the interpolated ones) apply the pending update themselves
+    // from the old buffer
     for (int fk = 0; fk < kNumMeasKinds && ok; fk++) ok = h->ms[fk].count() == 0 || se3 || h->ms[fk].two;
     for (int f = 0; f < ngp && ok; f++) ok = h->gp_left[f] < N - 1;     // (one per left state: rec_ok)
     ok = ok && h->sg.count() == 0;      // (the state Gaussians' kernel reads the stored states: it applies no pending update)
@@ -1588,7 +1636,7 @@ int alloc_records(gpslam_hip_handle *h, const RowLayout &lay) {
     HIPCHK(hipMemsetAsync(static_cast<char *>(h->brec.p) + (size_t)h->btw.count() * kBtwLen * sizeof(Real), 0, kBtwLen * sizeof(Real), h->stream));
   }
   if (p.gp_rec == GpForm::Se3Rec && (rc = alloc_gp_records(h, kGpsLen))) return rc;
-  h->pend_upd = false;
+  h->defer.clear();
   if (p.fold_retract) {   // the second state buffer: here, not inside the first run's second iteration (a hipMalloc in a timed region)
     HIPCHK(h->pose_bak.reserve((size_t)h->pd * h->stride * sizeof(double)));
     HIPCHK(h->vel_bak.reserve((size_t)h->d * h->stride * sizeof(double)));
@@ -1674,18 +1722,10 @@ int gpslam_hip_linearize_meas(gpslam_hip_handle *h, int32_t kind, double *errors
   if (F == 0) return 0;
   HIPCHK(h->api_e.reserve((size_t)F * s.rows * sizeof(RowT)));
   HIPCHK(h->api_H.reserve((size_t)F * s.rows * W * sizeof(RowT)));
-  MeasArgs<RowT> a;
-  a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride;
-  a.lmk = h->lmk.as<double>(); a.ld = h->ld; a.count = F; a.chart = h->cfg.chart;
-  a.idx = s.d_idx.as<int>(); a.lm = s.d_lm.as<int>(); a.meas = s.d_meas.as<double>(); a.mw = s.mw;
-  a.sig = s.d_sig.as<double>(); a.coef = s.d_coef.as<double>();
-  a.aux = s.any_aux ? s.d_aux.as<double>() : nullptr; a.aidx = s.any_aux ? s.d_aidx.as<int>() : nullptr;
-  a.sqi = s.sqi.empty() ? nullptr : s.d_sqi.as<double>();
-  a.vw = h->vw; a.row0 = s.d_row0.as<int>();     // (a.rob stays null: evaluateError knows no noise model)
   // no row tables: on an fp32 handle (this is impl64 answering for it) they hold floats, and a later solve must not find
-  // this call's rows in them either way (ADVICE r3)
-  a.rowLR = nullptr; a.rowE = nullptr; a.rowM = nullptr; a.rowLm = nullptr;
-  a.partial = h->partial.as<RowT>(); a.rowE32 = nullptr;
+  // this call's rows in them either way (ADVICE r3).  (a.rob stays null: evaluateError knows no noise model)
+  MeasArgs<RowT> a = meas_args(h, kind);
+  a.partial = h->partial.as<RowT>();
   a.out_e = h->api_e.as<RowT>(); a.out_J = h->api_H.as<RowT>();
   dispatch_mf(h->mf, [&](auto tag) {
     constexpr int MF = decltype(tag)::value;
@@ -1755,44 +1795,6 @@ int gpslam_hip_normal_equations(gpslam_hip_handle *h, double *D, double *O, doub
   }
   return 0;
 }
-
-// gpslam_hip_marginals (marginals.hip): the records of the current linearisation, as gpslam_hip_normal_equations assembles them
-int marginals_assemble(gpslam_hip_handle *h) {
-  int rc;
-  if ((rc = launch_factors(h, LaunchMode{}, 0, 0))) return rc;
-  return launch_assemble(h, LaunchMode{}, false);
-}
-// gpslam_hip_marginalize_head (fixedlag.hip): the same in the row form -- the d = 3 GP priors as rows, so that the tables hold every row
-int fixedlag_assemble(gpslam_hip_handle *h) {
-  LaunchMode m;
-  m.d3_rows = true;
-  int rc;
-  if ((rc = launch_factors(h, m, 0, 0))) return rc;
-  return launch_assemble(h, m, false);
-}
-// gpslam_hip_iterate_dogleg (dogleg.hip): see api_decl.inc
-int dogleg_linearize(gpslam_hip_handle *h) {
-  int rc;
-  HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  if ((rc = launch_factors(h, LaunchMode{}, 0, 0))) return rc;
-  if ((rc = backup_state(h, false))) return rc;
-  return launch_assemble(h, LaunchMode{}, true);
-}
-int dogleg_solve(gpslam_hip_handle *h) { return launch_solve(h, LaunchMode{}, 0.0); }
-int dogleg_trial(gpslam_hip_handle *h) {
-  int rc;
-  if ((rc = launch_retract(h, LaunchMode{}, 2))) return rc;
-  return launch_factors(h, LaunchMode{}, 1, 1);
-}
-// ... and the solver's right-hand sides at lambda = 0: the closure columns Z = A^-1 J_c^T, the landmark columns corrected for the
-// closures, and the landmark Schur complement S of the whole chain -- launch_solve without the landmark solve (the states stay).
-// On a handle in column passes (gpslam_hip_marginals_keep_closure_columns) every slice of Z is kept in h->mg.Z on the way.
-int marginals_border(gpslam_hip_handle *h) { return launch_solve(h, LaunchMode{}, 0.0, true, false); }
-// gpslam_hip_log_determinant (evidence.hip): the same without a kept Z -- in column passes W = U [X | Z] in clo.W is all it reads
-int evidence_border(gpslam_hip_handle *h) { return launch_solve(h, LaunchMode{}, 0.0, false, false); }
-// ... and on the segmented landmark path (marginals_fs.hip) the forward half at lambda = 0: segment factors, the half-swept border
-// Y = L^-1 G into the marginals' own buffer (zeroed by the caller; a fused_sweep plan has none), the fat chain's cyclic reduction
-int marginals_fs_forward(gpslam_hip_handle *h, void *Y) { return fs_forward(h, 0.0, static_cast<Real *>(Y)); }
 
 // whitened Jacobian rows of the current linearisation, in row-table order (rows grouped by left state; inside a
 // state: GP priors, pose priors, velocity priors, between, then the measurement kinds in FKind order)

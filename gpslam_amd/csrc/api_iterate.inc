@@ -359,7 +359,7 @@ int gpslam_hip_run_gn(gpslam_hip_handle *h, int32_t iters, gpslam_hip_stats *st,
   // never leave an update unapplied behind an error (ADVICE r5: EVERY exit, not only enqueue_gn's): the accessors of the states
   // (get_states, set_halo, the next linearisation) read h->pose / h->vel as they are
   auto bail = [&](int code) {
-    if (h->pend_upd) { h->pend_upd = false; (void)launch_retract(h, LaunchMode{}, 2); (void)hipStreamSynchronize(h->stream); }
+    if (h->defer.update) { (void)flush_update(h); (void)hipStreamSynchronize(h->stream); }
     return code;
   };
   for (int it = 0; it < iters; it++) {

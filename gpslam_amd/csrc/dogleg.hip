@@ -2,11 +2,11 @@
 // iteration, every trial of a trust radius a blend of two vectors that are already on the device, a retraction and an error pass.
 // fp64, unsharded handles with the dense landmark border (or none); DESIGN.md section 4i has the algebra and the launch sequence.
 //
-// Per iteration: dogleg_linearize (rows, error, records [D | O | g | B] with the gradient copied to gsave) -> k_dl_lm (landmarks: g_L
+// Per iteration: the linearisation (rows, error, records [D | O | g | B] with the gradient copied to gsave) -> k_dl_lm (landmarks: g_L
 // and its share of g^T H g, g . g) -> k_dl_quad (the records' share, before the elimination overwrites them) -> one fixed-order sum
-// -> dogleg_solve (lambda = 0) -> the Gauss-Newton step kept (dvec, dl.nL) -> g . dn, dn . dn -> ONE read of the scalars.  Per
-// trial: gpslam_hip_dogleg_point on the host -> k_dl_blend writes alpha g + beta dn where the retraction reads it -> dogleg_trial
-// -> gpslam_hip_dogleg_decide on the host.
+// -> launch_solve (lambda = 0) -> the Gauss-Newton step kept (dvec, dl.nL) -> g . dn, dn . dn -> ONE read of the scalars.  Per
+// trial: gpslam_hip_dogleg_point on the host -> k_dl_blend writes alpha g + beta dn where the retraction reads it -> launch_retract
+// and an error pass -> gpslam_hip_dogleg_decide on the host.
 #include "api_common.hpp"
 #include "../../include/gpslam_hip_dogleg.h"
 
@@ -249,7 +249,10 @@ int dl_prepare(gpslam_hip_handle *h, double *s4, double *f) {
   HIPCHK(h->dl.nL.reserve((size_t)std::max(nl, 1) * sizeof(double)));
   double *part = h->dl.part.as<double>(), *pdx = part + 2 * (size_t)nbt, *pdl = pdx + 3 * (size_t)nbd;
   double *scal = h->scal.as<double>();
-  if ((rc = impl64::dogleg_linearize(h))) return rc;
+  // the pivot flag cleared; rows and the error of the current estimate (scal[0]); the estimate remembered; the records [D | O | g | B]
+  // in the form of gpslam_hip_normal_equations, the gradient copied to gsave
+  HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
+  if ((rc = impl64::launch_factors(h, LaunchMode{}, 0, 0)) || (rc = backup_state(h, false)) || (rc = impl64::launch_assemble(h, LaunchMode{}, true))) return rc;
   if (nl > 0) {
     DlLmArgs la;
     la.rowE = h->rowE.as<double>(); la.rowM = h->rowM.as<double>();
@@ -269,7 +272,7 @@ int dl_prepare(gpslam_hip_handle *h, double *s4, double *f) {
   });
   k_final_reduce3<double><<<dim3(2), dim3(256), 0, h->stream>>>(part, nbt, scal, DL_GHG, DL_GG, -1);
   HIPCHK(hipGetLastError());
-  if ((rc = impl64::dogleg_solve(h))) return rc;
+  if ((rc = impl64::launch_solve(h, LaunchMode{}, 0.0))) return rc;   // (lambda = 0, level 0 unfused: the two-launch form)
   // the Gauss-Newton step is kept: the trials overwrite column 0 of the level-0 solution and lm_dL
   double *dv = h->dvec.as<double>();
   k_gather_delta<double><<<dim3(nblocks(nx, 256)), dim3(256), 0, h->stream>>>(h->lv[0].x.as<double>(), N, R, b, dv);
@@ -317,7 +320,8 @@ int dl_iterate(gpslam_hip_handle *h, double *delta, int32_t mode, gpslam_hip_sta
     if ((rc = ::gpslam_hip_dogleg_point(s4, *delta, coef, &norm, &pred, &branch))) return rc;
     if (moved && (rc = backup_state(h, true))) return rc;
     if ((rc = dl_blend(h, coef[0], coef[1]))) return rc;
-    if ((rc = impl64::dogleg_trial(h))) return rc;
+    // the tail of a Levenberg-Marquardt trial: retract by column 0 of the level-0 solution and lm_dL (scal[2] = |delta|_inf), error into scal[1]
+    if ((rc = impl64::launch_retract(h, LaunchMode{}, 2)) || (rc = impl64::launch_factors(h, LaunchMode{}, 1, 1))) return rc;
     moved = true;
     double s[3];
     int flag = 0;

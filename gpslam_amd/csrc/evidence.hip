@@ -1,14 +1,14 @@
 // evidence.hip -- log det H and the Laplace log-evidence of a handle (include/gpslam_hip_evidence.h):
 //   log Z = -cost(x^) + sum_f log|det R_f| - 1/2 log det H - ((m - n) / 2) log 2 pi,   H = J^T J as gpslam_hip_marginals defines it.
 // log det H = log det A + log det(I + U Z) + log det S:
-//   (a) the level-0 records [D | O | G] of the current linearisation (marginals_assemble);
+//   (a) the level-0 records [D | O | G] of the current linearisation (launch_factors, launch_assemble);
 //   (b) log det A of the block-tridiagonal chain part: the chunked elimination of marginals.hip (b), its forward half only
 //       (k_ev_forward / k_ev_top).  Chunks of kMgChunk states, the first of a chunk its separator; the interiors are eliminated in
 //       order, fill the separator and leave ONE number, the sum of the logarithms of their pivots; the separators form a system of
 //       the same kind, recursively, until one block is left.  Nothing is stored per interior state: a pivot block is factorised by
 //       Cholesky with [E | F] riding along (one forward substitution gives L^-1 E and L^-1 F, and every Schur update is a product
 //       of those two), so there is no inverse, no [P^-1 | U | V], and no backward sweep;
-//   (c) the solver's own right-hand sides at lambda = 0 (evidence_border) give Z = A^-1 U^T at the closures' states -- in column
+//   (c) the solver's own right-hand sides at lambda = 0 (launch_solve, lm_reduce_only) give Z = A^-1 U^T at the closures' states -- in column
 //       passes W = U [X | Z] in clo.W -- and the landmarks' Schur complement S in lm_S; k_ev_core takes the two log-determinants by
 //       Cholesky in LDS, I + U Z symmetrised as k_mg_core / k_clo_solve_wide do (clo_sym_entry);
 //   (d) k_ev_reduce adds the per-chunk partial sums of every level in a fixed order and writes the three parts and the pivot flag
@@ -357,7 +357,7 @@ int ev_logdet(gpslam_hip_handle *h, double *logdet, double *parts3) {
   }
   HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
   HIPCHK(hipMemsetAsync(h->evd.res.p, 0, 6 * sizeof(double), h->stream));
-  if ((rc = impl64::marginals_assemble(h))) return rc;
+  if ((rc = impl64::launch_factors(h, LaunchMode{}, 0, 0)) || (rc = impl64::launch_assemble(h, LaunchMode{}, false))) return rc;
   const double *blk = h->lv[0].blk.as<double>();
   double *up = h->evd.up.as<double>(), *part = h->evd.part.as<double>(), *res = h->evd.res.as<double>();
   auto level = [&](int l) {
@@ -383,7 +383,9 @@ int ev_logdet(gpslam_hip_handle *h, double *logdet, double *parts3) {
   HIPCHK(hipGetLastError());
   // (c) landmarks and closures
   if (m > 0) {
-    if ((rc = impl64::evidence_border(h))) return rc;
+    LaunchMode border;
+    border.lm_reduce_only = true;   // (no kept Z: in column passes W = U [X | Z] in clo.W is all k_ev_core reads)
+    if ((rc = impl64::launch_solve(h, border, 0.0))) return rc;
     EvCore c;
     c.S = h->lm_S.as<double>(); c.cloA = h->clo.A.as<double>(); c.first = h->clo.fac.d_idx.as<int>(); c.second = h->clo.d_second.as<int>();
     c.x = h->lv[0].x.as<double>(); c.W = passes ? h->clo.W.as<double>() : nullptr; c.ldw = clo_ldw(h); c.nr = 1 + nl;

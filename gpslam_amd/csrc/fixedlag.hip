@@ -806,7 +806,9 @@ int gpslam_hip_marginalize_head(gpslam_hip_handle *h, int32_t k) {
   if (const char *bad = widths_ok(h))
     return fail(h, GPSLAM_E_INVALID, (std::string("marginalize_head: internal error: the per-factor array ") + bad + " does not hold its width per factor").c_str());
   // ---- the head's linearisation: the handle's own rows and records (lambda = 0, robust weights), then the recursion
-  if ((rc = impl64::fixedlag_assemble(h))) return rc;
+  LaunchMode rows;
+  rows.d3_rows = true;   // the d = 3 GP priors as rows: the head's share of block k is summed from the tables, so they hold every row
+  if ((rc = impl64::launch_factors(h, rows, 0, 0)) || (rc = impl64::launch_assemble(h, rows, false))) return rc;
   const int BB = b * b, nl = joint ? h->nl : 0, R1 = 1 + nl, n = b + nl;
   // [D_k^left | g_k^left | B_k^left] (k_head_left, k_head_left_lm), [Lambda (n x n) | g' (n)], [pose_k | vel_k], the landmarks
   const int nleft = BB + b * R1, nout = nleft + n * n + n + pd + d + nl, nhead = nl * nl + nl;
@@ -898,7 +900,7 @@ int gpslam_hip_marginalize_head(gpslam_hip_handle *h, int32_t k) {
     h->hpb.insert(h->hpb.end(), Lam, Lam + (size_t)n * n);
     for (int q = 0; q < n; q++) h->hpb.push_back(-gk[q]);
   }
-  h->pend_upd = false; h->pend_err_n = 0; h->pend_dmax_n = 0;
+  h->defer.clear();
   h->compiled = false;
   h->mg.invalidate();
   return 0;

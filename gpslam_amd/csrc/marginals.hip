@@ -411,7 +411,7 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
     HIPCHK(hipMemsetAsync(h->mg.Z.p, 0, zbytes, h->stream));   // the padding rows and columns: k_mg_clo_finish reads them
   }
   HIPCHK(hipMemsetAsync(h->flag.p, 0, sizeof(int), h->stream));
-  if ((rc = impl64::marginals_assemble(h))) return rc;
+  if ((rc = impl64::launch_factors(h, LaunchMode{}, 0, 0)) || (rc = impl64::launch_assemble(h, LaunchMode{}, false))) return rc;
   const double *blk = h->lv[0].blk.as<double>();
   const int BS = 2 * BB + B * R;
   auto level = [&](int l) {
@@ -448,7 +448,9 @@ int gpslam_hip_marginals(gpslam_hip_handle *h) {
   if (m > 0) {
     // closures in column passes: Z slice by slice into mg.Z, then - Z M^-1 Z^T on its own; what is left for k_mg_core and
     // k_mg_finish is the landmark term (W in the leading columns of the level-0 solution, K = S^-1: no closure reaches k_mg_core)
-    if ((rc = impl64::marginals_border(h))) return rc;
+    LaunchMode border;
+    border.keep_z = true; border.lm_reduce_only = true;
+    if ((rc = impl64::launch_solve(h, border, 0.0))) return rc;
     if (passes && (rc = marginals_closure_term(h))) return rc;
     if (!passes || h->nl > 0) {
       MgCore c;

@@ -147,7 +147,7 @@ template <int B> __global__ void __launch_bounds__(64 * kMgCloWaves) k_mg_clo_fi
 
 }  // namespace
 
-// behind the column passes of marginals_border (W = U [X | Z] in clo.W, Z in mg.Z) and in front of k_mg_finish: M^-1 into mg.Minv, then the term
+// behind the column passes of the marginals' launch_solve (W = U [X | Z] in clo.W, Z in mg.Z) and in front of k_mg_finish: M^-1 into mg.Minv, then the term
 int marginals_closure_term(gpslam_hip_handle *h) {
   const int N = h->N, B = h->b, ldz = mg_ldz(h->clo.nc);
   MgCloInv ci;

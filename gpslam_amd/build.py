@@ -21,9 +21,10 @@ LIB = os.path.join(LIBDIR, "libgpslam_hip.so")
 # (marginals_fs.hip: fp64 only), the loop closures' launches (closures.hip: fp64 only), and fixed-lag smoothing (fixedlag.hip: state
 # Gaussians, the head's marginalisation; fp64 only), the marginals of any two states with the closure gate (marginals_pairs.hip),
 # Powell's dogleg optimiser (dogleg.hip: fp64 only; its C declarations are include/gpslam_hip_dogleg.h), and log det H with the
-# Laplace log-evidence (evidence.hip: fp64 only; include/gpslam_hip_evidence.h)
+# Laplace log-evidence (evidence.hip: fp64 only; include/gpslam_hip_evidence.h), and learning Qc from the marginals (qc_learn.hip: fp64
+# only; include/gpslam_hip_qc.h)
 SOURCES = ["api.hip", "api_impl64.hip", "api_impl32.hip", "upper.hip", "marginals.hip", "marginals_clo.hip", "marginals_fs.hip", "closures.hip", "fixedlag.hip", "marginals_pairs.hip", "dogleg.hip",
-           "evidence.hip"]
+           "evidence.hip", "qc_learn.hip"]
 HEADERS = ["kernels.hpp", "closures.hpp", "factors.hpp", "lie.hpp", "devbuf.hpp", "fatsep.hpp", "dpp.hpp", "cr_step.hpp", "cr_quad.hpp", "upper.hpp", "api_common.hpp", "robust.hpp",
            "marginals.hpp", "api_decl.inc", os.path.join("..", "..", "include", "gpslam_hip.h")]
 # what each translation unit includes (an edit to upper.hip does not recompile the others)
@@ -32,7 +33,8 @@ MGDEV = HEADERS + ["marginals_dev.hpp"]   # the marginals' units, and closures.h
 DEPS = {"api.hip": HEADERS, "api_impl64.hip": IMPL, "api_impl32.hip": IMPL,
         "upper.hip": ["dpp.hpp", "cr_step.hpp", "cr_quad.hpp", "upper.hpp"], "marginals.hip": MGDEV, "marginals_clo.hip": MGDEV, "marginals_fs.hip": MGDEV, "closures.hip": MGDEV, "fixedlag.hip": HEADERS, "marginals_pairs.hip": MGDEV,
         "dogleg.hip": HEADERS + [os.path.join("..", "..", "include", "gpslam_hip_dogleg.h")],
-        "evidence.hip": HEADERS + [os.path.join("..", "..", "include", "gpslam_hip_evidence.h")]}
+        "evidence.hip": HEADERS + [os.path.join("..", "..", "include", "gpslam_hip_evidence.h")],
+        "qc_learn.hip": HEADERS + [os.path.join("..", "..", "include", "gpslam_hip_qc.h")]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"]
 
 

@@ -71,6 +71,10 @@ EVIDENCE_SYMBOLS = [
     "gpslam_hip_log_determinant", "gpslam_hip_log_noise_normaliser", "gpslam_hip_log_evidence",
     "gpslam_hip_gp_log_normaliser", "gpslam_hip_evidence_combine",
 ]
+# every symbol include/gpslam_hip_qc.h declares (learning Qc: the statistic A, its gradient, the EM update; a list of its own again)
+QC_SYMBOLS = [
+    "gpslam_hip_qc_statistic", "gpslam_hip_qc_gradient", "gpslam_hip_qc_em_update", "gpslam_hip_qc_em_scale",
+]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
 STRUCT_CONFIG, STRUCT_CONFIG_V2, STRUCT_STATS, STRUCT_PARAMS = 0, 1, 2, 3
@@ -255,6 +259,69 @@ def evidence_combine(cost, logdet, lognorm, rows, nvars):
     rc = _evidence_lib().gpslam_hip_evidence_combine(float(cost), float(logdet), float(lognorm), int(rows), int(nvars), C.byref(out))
     if rc:
         raise GpslamHipError("evidence_combine: %d" % rc)
+    return out.value
+
+
+def _qc_lib():
+    """The library with the argument types of include/gpslam_hip_qc.h set (64-bit counts travel by value there)."""
+    lib = load_library()
+    if not hasattr(lib, "gpslam_hip_qc_statistic"):
+        raise GpslamHipError("this libgpslam_hip.so has no Qc-learning entry points (include/gpslam_hip_qc.h)")
+    if getattr(lib, "_qc_bound", False):
+        return lib
+    dp, lp, vp = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p
+    lib.gpslam_hip_qc_statistic.argtypes = [vp, dp, lp]
+    lib.gpslam_hip_qc_gradient.argtypes = [C.c_int32, dp, dp, C.c_int64, dp]
+    lib.gpslam_hip_qc_em_update.argtypes = [C.c_int32, dp, C.c_int64, dp]
+    lib.gpslam_hip_qc_em_scale.argtypes = [C.c_int32, dp, dp, C.c_int64, dp]
+    for name in QC_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
+    lib._qc_bound = True
+    return lib
+
+
+def _square(M, what):
+    m = np.ascontiguousarray(M, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise GpslamHipError("%s: the matrices must be square" % what)
+    return m
+
+
+def qc_gradient(Qc, A, n_f):
+    """gpslam_hip_qc_gradient (host arithmetic, no GPU): G = n_f Qc - A / 2, the derivative of the log-evidence in W = Qc^-1 at
+    fixed states (dF = tr(G dW)), from the statistic (A, n_f) of ChainSolver.qc_statistic."""
+    q, a = _square(Qc, "qc_gradient"), _square(A, "qc_gradient")
+    if q.shape != a.shape:
+        raise GpslamHipError("qc_gradient: Qc and A differ in size")
+    dp = C.POINTER(C.c_double)
+    G = np.zeros_like(q)
+    rc = _qc_lib().gpslam_hip_qc_gradient(int(q.shape[0]), q.ctypes.data_as(dp), a.ctypes.data_as(dp), int(n_f), G.ctypes.data_as(dp))
+    if rc:
+        raise GpslamHipError("qc_gradient: %d" % rc)
+    return G
+
+
+def qc_em_update(A, n_f):
+    """gpslam_hip_qc_em_update (host arithmetic, no GPU): the EM M-step Qc+ = A / (2 n_f)."""
+    a = _square(A, "qc_em_update")
+    dp = C.POINTER(C.c_double)
+    out = np.zeros_like(a)
+    rc = _qc_lib().gpslam_hip_qc_em_update(int(a.shape[0]), a.ctypes.data_as(dp), int(n_f), out.ctypes.data_as(dp))
+    if rc:
+        raise GpslamHipError("qc_em_update: %d" % rc)
+    return out
+
+
+def qc_em_scale(Qc0, A, n_f):
+    """gpslam_hip_qc_em_scale (host arithmetic, no GPU): theta+ = tr(Qc0^-1 A) / (2 n_f d), the stationary scale of Qc = theta Qc0."""
+    q, a = _square(Qc0, "qc_em_scale"), _square(A, "qc_em_scale")
+    if q.shape != a.shape:
+        raise GpslamHipError("qc_em_scale: Qc0 and A differ in size")
+    dp = C.POINTER(C.c_double)
+    out = C.c_double(0.0)
+    rc = _qc_lib().gpslam_hip_qc_em_scale(int(q.shape[0]), q.ctypes.data_as(dp), a.ctypes.data_as(dp), int(n_f), C.byref(out))
+    if rc:
+        raise GpslamHipError("qc_em_scale: %d" % rc)
     return out.value
 
 
@@ -660,6 +727,13 @@ class ChainSolver:
         out = (C.c_double * 5)()
         self._chk(_evidence_lib().gpslam_hip_log_evidence(self._h, out), "log_evidence")
         return tuple(out)
+
+    def qc_statistic(self):
+        """(A, n_f) over the GP priors that carry the handle's shared Qc, from the current marginals (include/gpslam_hip_qc.h):
+        A = sum_i sum_k (e~_k e~_k^T + J~_k Sigma_J J~_k^T), d x d.  Call marginals() first; they stay valid."""
+        A, n = np.zeros((self.d, self.d)), C.c_int64(0)
+        self._chk(_qc_lib().gpslam_hip_qc_statistic(self._h, A.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)), "qc_statistic")
+        return A, n.value
 
     def run_gn(self, iters, timed=False):
         st = Stats()

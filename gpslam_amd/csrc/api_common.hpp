@@ -159,6 +159,17 @@ struct Evidence {
   }
 };
 
+// gpslam_hip_qc_statistic (qc_learn.hip): one d x d partial sum per workgroup of k_qc_stat, and the d x d result behind them
+struct QcLearn {
+  int N = 0;                  // the N the buffer is sized for
+  DevBuf part;
+  // the buffer serves n states from here on: another N frees what is there (as Marginals::fit)
+  void fit(int n) {
+    if (N != n) part.release();
+    N = n;
+  }
+};
+
 // Work one launch leaves to a later one (chains without landmarks, unsharded: gn_mode; run_gn with Plan::fold_retract).  update: a
 // solve's step sits in the level-0 solution array, not yet applied -- the next k_lin applies it (kernels.hpp: PendUpd), or
 // flush_update.  err: the linearisation's error partial sums in `partial`, summed by an extra workgroup of this iteration's
@@ -258,6 +269,7 @@ struct gpslam_hip_handle {
                               // factors or Qc says h->mg.invalidate()
   Dogleg dl;                  // gpslam_hip_iterate_dogleg (dogleg.hip)
   Evidence evd;               // gpslam_hip_log_determinant (evidence.hip)
+  QcLearn qcl;                // gpslam_hip_qc_statistic (qc_learn.hip)
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch

@@ -34,6 +34,7 @@
 #include "../../include/gpslam_hip.h"
 #include "../../include/gpslam_hip_dogleg.h"
 #include "../../include/gpslam_hip_evidence.h"
+#include "../../include/gpslam_hip_qc.h"
 
 // boost::optional<Matrix&> -- the type of the reference's Jacobian arguments (gpslam/gp/GaussianProcessPriorPose3.h:60-64:
 // `boost::optional<gtsam::Matrix&> H1 = boost::none`).  Where Boost is installed its header is used; where it is not (this image), the
@@ -650,7 +651,11 @@ struct Session {
   }
 
   bool qc_set = false;
-  int closures = 0;                  // BetweenFactors between non-adjacent states
+  // qcStatistic: GP priors whose Qc_model is the handle's shared Qc (the first one seen) go in as sharing it, not with a copy of
+  // their own -- the statistic sums the priors that share it (include/gpslam_hip_qc.h); everything else builds as it always did
+  bool share_qc = false;
+  std::vector<double> qc_shared;
+  int closures = 0;                 // BetweenFactors between non-adjacent states
   // the factors of `graph` onto the handle: build(), and BatchFixedLagSmoother::update for the factors that arrive later
   void add_factors(const NonlinearFactorGraph &graph) {
     std::vector<double> qc_used;
@@ -662,7 +667,7 @@ struct Session {
         if (Qc.rows != (bias ? 3 : d)) throw std::invalid_argument("Qc_model dimension does not match the manifold");
         // (the handle's shared Qc serves the interpolation queries; GP priors carry their own Qc_model -- below --, and
         //  the interpolated measurement factors do not depend on theirs: Qc cancels in Lambda and Psi)
-        if (!qc_set) { check(gpslam_hip_set_qc(h, Qc.a.data()), h, "set_qc"); qc_set = true; qc_used = Qc.a; }
+        if (!qc_set) { check(gpslam_hip_set_qc(h, Qc.a.data()), h, "set_qc"); qc_set = true; qc_used = Qc.a; qc_shared = Qc.a; }
       };
       auto gaussian = [&](int kind) {   // noiseModel::Gaussian::Covariance / noiseModel::Robust on the factor just added
         if (!f.cov.empty()) check(gpslam_hip_set_meas_covariance(h, kind, 1, f.cov.data()), h, "set_meas_covariance");
@@ -681,7 +686,8 @@ struct Session {
               (f.vw && (symbolIndex(f.kw[0]) != symbolIndex(f.k[0]) || symbolIndex(f.kw[1]) != symbolIndex(f.k[2]))))
             throw std::invalid_argument("GP prior: pose and velocity keys of a state must share their index");
           int32_t l = adjacent(f.k[0], f.k[2]);
-          check(gpslam_hip_add_gp_priors_qc(h, 1, &l, &f.dt, f.Qc.a.data()), h, "add_gp_priors_qc");   // one Qc_model per factor
+          if (share_qc && f.Qc.a == qc_shared) check(gpslam_hip_add_gp_priors(h, 1, &l, &f.dt), h, "add_gp_priors");
+          else check(gpslam_hip_add_gp_priors_qc(h, 1, &l, &f.dt, f.Qc.a.data()), h, "add_gp_priors_qc");   // one Qc_model per factor
         } break;
         case F_POSE_PRIOR: {
           int32_t s = state_of(f.k[0]);
@@ -1367,6 +1373,47 @@ inline LogEvidence logEvidence(const NonlinearFactorGraph &graph, const Values &
   LogEvidence e;
   e.logZ = out5[0]; e.cost = out5[1]; e.logDeterminant = out5[2]; e.logNoiseNormaliser = out5[3]; e.rowsMinusVariables = (long long)out5[4];
   return e;
+}
+
+/// The statistic Qc is learned from (gpslam_hip_qc_statistic; include/gpslam_hip_qc.h), at `values` (the caller's optimum), on a session
+/// of its own: A = sum over the GP priors whose Qc_model is the first one the graph names of e~ e~^T + J~ Sigma_J J~^T, and their
+/// number.  GP priors with another Qc_model are constants: neither summed nor counted.  gradient(Qc) is the derivative of the
+/// log-evidence in Qc^-1 at fixed states, emUpdate() the Qc that makes it zero, emScale(Qc0) the stationary theta of theta Qc0.
+struct QcStatistic {
+  Matrix A;
+  long long priors = 0;
+  Matrix gradient(const Matrix &Qc) const {
+    Matrix G(A.rows, A.cols);
+    if (Qc.rows != A.rows || Qc.cols != A.cols || gpslam_hip_qc_gradient(A.rows, Qc.a.data(), A.a.data(), priors, G.a.data()))
+      throw std::invalid_argument("QcStatistic::gradient: Qc must be symmetric positive definite, of the statistic's size, and the statistic must count a prior");
+    return G;
+  }
+  Matrix emUpdate() const {
+    Matrix Q(A.rows, A.cols);
+    if (gpslam_hip_qc_em_update(A.rows, A.a.data(), priors, Q.a.data())) throw std::invalid_argument("QcStatistic::emUpdate: the statistic counts no prior, or A is not positive definite");
+    return Q;
+  }
+  double emScale(const Matrix &Qc0) const {
+    double theta = 0.0;
+    if (Qc0.rows != A.rows || Qc0.cols != A.cols || gpslam_hip_qc_em_scale(A.rows, Qc0.a.data(), A.a.data(), priors, &theta))
+      throw std::invalid_argument("QcStatistic::emScale: Qc0 must be symmetric positive definite, of the statistic's size, and the statistic must count a prior");
+    return theta;
+  }
+};
+inline QcStatistic qcStatistic(const NonlinearFactorGraph &graph, const Values &values) {
+  detail::Session s;
+  s.share_qc = true;
+  s.build(graph, values);
+  // (as Marginals: the closures' columns kept in column passes, G kept on the segmented landmark path)
+  detail::check(gpslam_hip_marginals_keep_closure_columns(s.h, 1), s.h, "marginals_keep_closure_columns");
+  detail::check(gpslam_hip_marginals_on_segments(s.h, 1), s.h, "marginals_on_segments");
+  detail::check(gpslam_hip_marginals(s.h), s.h, "marginals");
+  QcStatistic q;
+  q.A = Matrix(s.d, s.d);
+  int64_t n = 0;
+  detail::check(gpslam_hip_qc_statistic(s.h, q.A.a.data(), &n), s.h, "qc_statistic");
+  q.priors = (long long)n;
+  return q;
 }
 
 // ---------------------------------------------------------------- AHRS (gtsam/navigation/AHRSFactor.h, GTSAM 4.0; third party)

@@ -1,6 +1,8 @@
 // api_common.hpp -- what the translation units of the library's host side share (api.hip: the C ABI; api_impl64.hip / api_impl32.hip:
-// api_impl.inc + api_iterate.inc once per row precision; closures.hip, fixedlag.hip, the four marginals*.hip): the handle, the host helpers and the
-// kernel launchers.  The marginals' state is marginals.hpp's (h->mg); device buffers free themselves (devbuf.hpp: no list names them)
+// api_impl.inc + api_iterate.inc once per row precision; closures.hip, fixedlag.hip, the four marginals*.hip, dogleg.hip, evidence.hip,
+// qc_learn.hip): the handle and the host helpers.  This file launches no kernel, so including it compiles none: a unit holds the
+// kernels its own launch statements name (level0.hip: the level-0 row and fused forms, behind kernels.hpp's declarations).
+// The marginals' state is marginals.hpp's (h->mg); device buffers free themselves (devbuf.hpp: no list names them)
 // (round 3: api.hip was one 3.5-minute translation unit; the fp64 and fp32 halves compile side by side now)
 #pragma once
 // api.hip -- host side of libgpslam_hip.so: the opaque handle, the graph-compile pass and the C ABI
@@ -640,113 +642,3 @@ int refresh_dU(gpslam_hip_handle *h) {
 }
 
 }  // namespace
-
-// kernels that exist for fp64 only (hand-written 64-bit DPP row layout, v_mfma_f64): the fp32 instantiation of the
-// host code never selects them (make_plan), these overloads only keep it compiling
-namespace {
-// ea / eb != null: the launch carries its own start / stop events (a timed iteration: the dispatch's own time stamps)
-// (expands inside launch_fused_k only: grid, st, ea, eb, u and the census array `cen` are that function's parameters)
-// (the census takes the instantiation from the text of the launch statement itself, at compile time: it cannot drift from it)
-struct FusedId { int sv = 0, b = 12; bool fp32 = false, dg = false; };
-constexpr FusedId fused_id(const char *s) {   // "k_fused_level0<SV[, TR[, B[, DG]]]>", the template's defaults where the text stops early
-  FusedId id;
-  while (*s != '<') ++s;
-  id.sv = s[1] - '0';
-  for (int field = 0; *s != '>'; ++s) {
-    if (*s != ',') continue;
-    while (s[1] == ' ') ++s;
-    field++;
-    if (field == 1) id.fp32 = s[1] == 'f';
-    if (field == 2) { id.b = 0; for (const char *t = s + 1; *t >= '0' && *t <= '9'; ++t) id.b = id.b * 10 + (*t - '0'); }
-    if (field == 3) id.dg = s[1] == 't';
-  }
-  return id;
-}
-static_assert(fused_id("k_fused_level0<4>").sv == 4 && fused_id("k_fused_level0<4>").b == 12 && !fused_id("k_fused_level0<4>").dg, "fused_id");
-static_assert(fused_id("k_fused_level0<1,double,6>").sv == 1 && fused_id("k_fused_level0<1,double,6>").b == 6 && !fused_id("k_fused_level0<1,double,6>").fp32 &&
-              fused_id("k_fused_level0<2,float,12,true>").dg && fused_id("k_fused_level0<2,float,12,true>").fp32 && fused_id("k_fused_level0<2,float,12,true>").b == 12, "fused_id");
-static_assert(fused_id("k_fused_level0<3, double, 12, true>").dg && fused_id("k_fused_level0<0, float, 6>").fp32 && fused_id("k_fused_level0<0, float, 6>").b == 6, "fused_id");
-#define GPS_FUSED_LAUNCH(...)                                                                                      \
-  do {                                                                                                             \
-    constexpr FusedId id_ = fused_id(#__VA_ARGS__);                                                                \
-    cen[GPSLAM_CENSUS_L0_FUSED]++;                                                                                 \
-    cen[GPSLAM_CENSUS_FUSED_SV] = id_.sv; cen[GPSLAM_CENSUS_FUSED_DG] = id_.dg; cen[GPSLAM_CENSUS_FUSED_B] = id_.b; \
-    cen[GPSLAM_CENSUS_FUSED_FP32] = id_.fp32;                                                                      \
-    if (ea) hipExtLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(128), 0, st, ea, eb, 0, u);                      \
-    else __VA_ARGS__<<<dim3(grid), dim3(128), 0, st>>>(u);                                                         \
-  } while (0)
-// the inputs of a k_fused_level0 launch as its arguments carry them (census)
-template <typename TR> inline void census_fused_inputs(int32_t *cen, int b, const FusedArgs<double, TR> &u) {
-  cen[GPSLAM_CENSUS_FUSED_GP] = u.gps == nullptr ? 0 : (b == 6 ? 1 : 2);
-  cen[GPSLAM_CENSUS_FUSED_BTW_REC] = u.brec != nullptr;
-  cen[GPSLAM_CENSUS_FUSED_LINES] = u.rowI != nullptr;
-  cen[GPSLAM_CENSUS_FUSED_ODD_ROWS] = u.odd_rows;
-  cen[GPSLAM_CENSUS_FUSED_GSAVE] = u.gsave != nullptr;
-  cen[GPSLAM_CENSUS_FUSED_TAIL] = u.f.tail != 0;
-  cen[GPSLAM_CENSUS_FUSED_GSAVE_LAUNCHES] += u.gsave != nullptr;
-  cen[GPSLAM_CENSUS_FUSED_TAIL_LAUNCHES] += u.f.tail != 0;
-}
-inline void launch_fused_k(int32_t *cen, int b, const LaunchForm &f, const FusedArgs<double, double> &u, int grid, hipStream_t st, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr) {
-  census_fused_inputs(cen, b, u);
-  if (b == 6) {
-    if (f.sv == 1) GPS_FUSED_LAUNCH(k_fused_level0<1, double, 6>);      // d = 3 records (kGp3*)
-    else GPS_FUSED_LAUNCH(k_fused_level0<0, double, 6>);
-    return;
-  }
-  switch (f.sv) {
-    case 4:                                  // records + interpolated measurement rows as 16-double lines (round 5)
-      if (f.dg) GPS_FUSED_LAUNCH(k_fused_level0<4, double, 12, true>);
-      else GPS_FUSED_LAUNCH(k_fused_level0<4>);
-      break;
-    case 3:                                  // records + a ring of full-width rows (measurement factors)
-      if (f.dg) GPS_FUSED_LAUNCH(k_fused_level0<3, double, 12, true>);
-      else GPS_FUSED_LAUNCH(k_fused_level0<3>);
-      break;
-    case 2: GPS_FUSED_LAUNCH(k_fused_level0<2>); break;
-    case 1:
-      if (f.dg) GPS_FUSED_LAUNCH(k_fused_level0<1, double, 12, true>);   // diagonal chol(Qc^-1)
-      else GPS_FUSED_LAUNCH(k_fused_level0<1>);
-      break;
-    default: GPS_FUSED_LAUNCH(k_fused_level0<0>);
-  }
-}
-// fp32 handles: fp32 row tables straight into the fused kernel's fp64 accumulation (round 3: the unfused assembly had cost the
-// fp32 mode more than its halved row traffic saved)
-inline void launch_fused_k(int32_t *cen, int b, const LaunchForm &, const FusedArgs<double, float> &u, int grid, hipStream_t st, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr) {
-  census_fused_inputs(cen, b, u);
-  if (b == 6) GPS_FUSED_LAUNCH(k_fused_level0<0, float, 6>);
-  else GPS_FUSED_LAUNCH(k_fused_level0<0, float>);
-}
-// GPInterpolatedGPSFactorPose3 as 16-double lines: fp64 only (Plan::lines)
-inline void launch_gps_lines_k(int32_t *cen, const MeasArgs<double> &a, int nb, hipStream_t st) {
-  cen[GPSLAM_CENSUS_GPS_LINES]++;
-  if (a.aidx != nullptr) k_gps_lines<kGpsLinesWaves, true><<<dim3(nb), dim3(128), 0, st>>>(a);   // (round 6: a kernel written for its register count)
-  else k_gps_lines<kGpsLinesWaves, false><<<dim3(nb), dim3(128), 0, st>>>(a);
-}
-inline void launch_gps_lines_k(int32_t *, const MeasArgs<float> &, int, hipStream_t) {}
-inline void launch_rows_k(int32_t *cen, int b, const FwdArgs<double> &a, int grid, hipStream_t st) {
-  cen[GPSLAM_CENSUS_L0_ROWS]++;
-  if (b == 12) k_chunk_forward_rows<12><<<dim3(grid), dim3(64), 0, st>>>(a);
-  else if (b == 6) k_chunk_forward_rows<6><<<dim3(grid), dim3(64), 0, st>>>(a);
-  else k_chunk_forward_rows<4><<<dim3(grid), dim3(64), 0, st>>>(a);
-}
-inline void launch_rows_k(int32_t *, int, const FwdArgs<float> &, int, hipStream_t) {}
-inline void launch_bwd_rows_k(int32_t *cen, int b, const BwdArgs<double> &a, int grid, hipStream_t st) {
-  cen[GPSLAM_CENSUS_BWD_ROWS]++;
-  cen[GPSLAM_CENSUS_BWD_ROWS_FOLD] += a.l1_blk != nullptr;
-  if (b == 12) k_chunk_backward_rows<12><<<dim3(grid), dim3(64), 0, st>>>(a);
-  else if (b == 6) k_chunk_backward_rows<6><<<dim3(grid), dim3(64), 0, st>>>(a);
-  else k_chunk_backward_rows<4><<<dim3(grid), dim3(64), 0, st>>>(a);
-}
-inline void launch_bwd_rows_k(int32_t *, int, const BwdArgs<float> &, int, hipStream_t) {}
-// segment interiors of the segmented landmark elimination: planar fp64 chains take the cooperative row-layout kernel (four
-// segments per wave), everything else the wave-per-segment kernel
-template <int BB, typename T, typename TR> inline void fs_launch_factor(const FsArgs<T, TR> &a, int nseg, hipStream_t st) {
-  if constexpr (BB == 6 && std::is_same<T, double>::value && std::is_same<TR, double>::value) {
-    k_fs_factor_rows6<0><<<dim3((nseg + 3) / 4), dim3(64), 0, st>>>(a);
-    return;
-  }
-  k_fs_factor<T, BB, TR><<<dim3(nseg), dim3(64), 0, st>>>(a);
-}
-}  // namespace
-

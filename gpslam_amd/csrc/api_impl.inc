@@ -232,6 +232,16 @@ int launch_lin_groups(const FactorPass &c, int off) {
   return off;
 }
 
+// GPInterpolatedGPSFactorPose3 as 16-double lines: fp64 only (Plan::lines; make_plan never selects them on an fp32 handle, whose
+// half therefore holds no form of k_gps_lines)
+template <typename R> void launch_gps_lines_k(int32_t *cen, const MeasArgs<R> &a, int nb, hipStream_t st) {
+  if constexpr (std::is_same<R, double>::value) {
+    cen[GPSLAM_CENSUS_GPS_LINES]++;
+    if (a.aidx != nullptr) k_gps_lines<kGpsLinesWaves, true><<<dim3(nb), dim3(128), 0, st>>>(a);   // (round 6: a kernel written for its register count)
+    else k_gps_lines<kGpsLinesWaves, false><<<dim3(nb), dim3(128), 0, st>>>(a);
+  }
+}
+
 // The measurement kinds in FKind order, one k_meas each on the side stream -- interpolated GPS as 16-double lines (k_gps_lines) where
 // the launch's form says so
 int launch_meas_kinds(const FactorPass &c, int off, const PendBeside &beside) {
@@ -415,7 +425,7 @@ int launch_fwd(gpslam_hip_handle *h, const LaunchMode &m, const FwdArgs<Real> &a
     (void)hipMemsetAsync(h->dbg_trace.p, 0, (size_t)h->dbg_trace_waves * 64 * 8, h->stream);
     u.trace = h->dbg_trace.as<unsigned long long>();
 #endif
-    launch_fused_k(h->census.v, h->b, form, u, nblocks(grid, 4), h->stream, m.l0_events ? h->ev_l0a : nullptr, m.l0_events ? h->ev_l0b : nullptr);
+    launch_fused_k(h->census.v, h->b, form.sv, form.dg, u, nblocks(grid, 4), h->stream, m.l0_events ? h->ev_l0a : nullptr, m.l0_events ? h->ev_l0b : nullptr);
     return 0;
   }
   if (h->plan.rows() && !a.no_sep && !a.add) {
@@ -671,6 +681,16 @@ void launch_fat_back(const FsArgs<Real, RowT> &a, const FatLevel &fl, hipStream_
     return;
   }
   k_fat_back_w4<RowT><<<dim3(fl.nelim), dim3(256), ((size_t)a.NB * (a.NB + 1) + 3 * (size_t)a.NB) * sizeof(Real), st>>>(a, fl);
+}
+
+// segment interiors of the segmented landmark elimination: planar fp64 chains take the cooperative row-layout kernel (four
+// segments per wave), everything else the wave-per-segment kernel
+template <int BB, typename T, typename TR> void fs_launch_factor(const FsArgs<T, TR> &a, int nseg, hipStream_t st) {
+  if constexpr (BB == 6 && std::is_same<T, double>::value && std::is_same<TR, double>::value) {
+    k_fs_factor_rows6<0><<<dim3((nseg + 3) / 4), dim3(64), 0, st>>>(a);
+    return;
+  }
+  k_fs_factor<T, BB, TR><<<dim3(nseg), dim3(64), 0, st>>>(a);
 }
 
 // forward half: segment interiors -> fat blocks -> cyclic-reduction levels (down to one block, or to the two end blocks of a

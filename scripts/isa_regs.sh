@@ -4,7 +4,8 @@
 # The ISA is left in /tmp/isa_regs.s.
 cd "$(dirname "$0")/../gpslam_amd/csrc" || exit 1
 T=_isa_regs_$$.hip
-echo '#include "api_common.hpp"' > $T
+# (api_common.hpp brings every kernel header but level0.hpp, which holds k_fused_level0 and the two k_chunk_*_rows kernels)
+printf '#include "api_common.hpp"\n#include "level0.hpp"\n' > $T
 for sig in "$@"; do echo "template __global__ void $sig;" >> $T; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast --cuda-device-only -S -o /tmp/isa_regs.s $T 2>&1 | grep -v "warning\|^ *[0-9]* *|\|^ *|\|generated\.$" | head -30
 rm -f $T

@@ -1,4 +1,4 @@
-"""CPU guard on the table of k_fused_level0 instantiations: the launch statements of launch_fused_k (api_common.hpp), the list
+"""CPU guard on the table of k_fused_level0 instantiations: the launch statements of launch_fused_k (level0.hip), the list
 tests/test_gpu_forms.py keeps (FUSED_FORMS) and the forms its rows expect must be the same set.  A thirteenth instantiation without a
 row, a dropped one, or a row that goes missing fails here, without a GPU."""
 import os
@@ -10,9 +10,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def launch_statements():
-    """(SV, TR, B, DG) of every GPS_FUSED_LAUNCH(k_fused_level0<...>) statement, the template's defaults (kernels.hpp:
+    """(SV, TR, B, DG) of every GPS_FUSED_LAUNCH(k_fused_level0<...>) statement, the template's defaults (level0.hpp:
     template <int SV, typename TR = double, int B = 12, bool DG = false>) filled in where a statement leaves them out"""
-    with open(os.path.join(ROOT, "gpslam_amd", "csrc", "api_common.hpp")) as f:
+    with open(os.path.join(ROOT, "gpslam_amd", "csrc", "level0.hip")) as f:
         src = f.read()
     found = []
     for args in re.findall(r"GPS_FUSED_LAUNCH\(\s*k_fused_level0<([^>]*)>\s*\)", src):
@@ -25,7 +25,7 @@ def launch_statements():
 
 
 def test_the_template_defaults_are_the_ones_this_file_fills_in():
-    with open(os.path.join(ROOT, "gpslam_amd", "csrc", "kernels.hpp")) as f:
+    with open(os.path.join(ROOT, "gpslam_amd", "csrc", "level0.hpp")) as f:
         src = f.read()
     assert re.search(r"template <int SV, typename TR = double, int B = 12, bool DG = false>\s*\n__global__ void __launch_bounds__\([^)]*\) k_fused_level0\(", src)
 

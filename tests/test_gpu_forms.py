@@ -9,7 +9,7 @@ convergence; the record forms also run one damped trial (iterate_lm at lambda = 
 instantiation with the gradient store on.
 
 FUSED_FORMS is every k_fused_level0<SV, TR, B, DG> instantiation launch_fused_k can launch; tests/test_forms_table.py (CPU) holds it
-against the launch statements of api_common.hpp and against the forms the rows here expect, so a thirteenth instantiation -- or a
+against the launch statements of level0.hip and against the forms the rows here expect, so a thirteenth instantiation -- or a
 row that goes missing -- fails without a GPU.
 
 Shapes: chunks of 4 on 70 states (18 chunks: five workgroups of four chunks, the last one ragged, a last chunk of two states), or

@@ -75,6 +75,10 @@ EVIDENCE_SYMBOLS = [
 QC_SYMBOLS = [
     "gpslam_hip_qc_statistic", "gpslam_hip_qc_gradient", "gpslam_hip_qc_em_update", "gpslam_hip_qc_em_scale",
 ]
+# every symbol include/gpslam_hip_sampling.h declares (draws from N(x^, H^-1) by perturbed solves; a list of its own again)
+SAMPLING_SYMBOLS = [
+    "gpslam_hip_posterior_noise_dim", "gpslam_hip_posterior_noise", "gpslam_hip_sample_posterior",
+]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
 STRUCT_CONFIG, STRUCT_CONFIG_V2, STRUCT_STATS, STRUCT_PARAMS = 0, 1, 2, 3
@@ -277,6 +281,23 @@ def _qc_lib():
     for name in QC_SYMBOLS:
         getattr(lib, name).restype = C.c_int
     lib._qc_bound = True
+    return lib
+
+
+def _sampling_lib():
+    """The library with the argument types of include/gpslam_hip_sampling.h set (64-bit seeds and counters travel by value there)."""
+    lib = load_library()
+    if not hasattr(lib, "gpslam_hip_sample_posterior"):
+        raise GpslamHipError("this libgpslam_hip.so has no sampling entry points (include/gpslam_hip_sampling.h)")
+    if getattr(lib, "_sampling_bound", False):
+        return lib
+    dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p
+    lib.gpslam_hip_posterior_noise_dim.argtypes = [vp, ip]
+    lib.gpslam_hip_posterior_noise.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int32, dp]
+    lib.gpslam_hip_sample_posterior.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, dp, dp, dp, dp, dp]
+    for name in SAMPLING_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
+    lib._sampling_bound = True
     return lib
 
 
@@ -734,6 +755,47 @@ class ChainSolver:
         A, n = np.zeros((self.d, self.d)), C.c_int64(0)
         self._chk(_qc_lib().gpslam_hip_qc_statistic(self._h, A.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)), "qc_statistic")
         return A, n.value
+
+    def posterior_noise_dim(self):
+        """length of one noise vector of sample_posterior: the rows of get_rows(), then the landmark priors' coordinates"""
+        n = C.c_int32(0)
+        self._chk(_sampling_lib().gpslam_hip_posterior_noise_dim(self._h, C.byref(n)), "posterior_noise_dim")
+        return n.value
+
+    def posterior_noise(self, seed, first, count):
+        """(count, n_noise): the generator's standard normals for samples first .. first + count - 1 (include/gpslam_hip_sampling.h:
+        Philox4x32-10, one normal per (seed, sample, noise index)); nothing is solved"""
+        out = np.zeros((max(int(count), 0), self.posterior_noise_dim()))
+        rc = _sampling_lib().gpslam_hip_posterior_noise(self._h, int(seed), int(first), int(count), out.ctypes.data_as(C.POINTER(C.c_double)))
+        self._chk(rc, "posterior_noise")
+        return out
+
+    def sample_posterior(self, count, seed=0, first=0, noise=None, want=("delta", "poses", "vels", "landmarks")):
+        """count draws from N(x^, H^-1) at the current states: (delta, poses, vels, landmarks), each with a leading axis of count --
+        delta the tangent draws (states, then landmarks), the rest x^ (+) delta in the layouts of get_states() and get_landmarks()
+        (landmarks None on a handle without any).  noise: (count, n_noise) whitened residuals to solve for instead of the generator's
+        -- the graph's own give the Gauss-Newton step.  want: the outputs asked for; the others return None and are neither written
+        nor copied to the host (on long chains the copies cost more than the solve).  The estimate stays; the marginals are stale
+        afterwards."""
+        count = int(count)
+        if not set(want) <= {"delta", "poses", "vels", "landmarks"}:
+            raise GpslamHipError("sample_posterior: want names delta, poses, vels, landmarks")
+        dp = C.POINTER(C.c_double)
+        if noise is not None:
+            noise = _f64(noise)
+            if noise.shape != (count, self.posterior_noise_dim()):
+                raise GpslamHipError("sample_posterior: noise must be count x posterior_noise_dim()")
+        nl = self.L * self.ld
+        n = max(count, 0)
+        delta = np.zeros((n, self.N * self.b + nl)) if "delta" in want else None
+        poses = np.zeros((n, self.N, self.pd)) if "poses" in want else None
+        vels = np.zeros((n, self.N, self.d)) if "vels" in want else None
+        lms = np.zeros((n, self.L, self.ld)) if (nl and "landmarks" in want) else None
+        out = (delta, poses, vels, lms)
+        rc = _sampling_lib().gpslam_hip_sample_posterior(self._h, count, int(seed), int(first), None if noise is None else noise.ctypes.data_as(dp),
+                                                         *[None if a is None else a.ctypes.data_as(dp) for a in out])
+        self._chk(rc, "sample_posterior")
+        return out
 
     def run_gn(self, iters, timed=False):
         st = Stats()

@@ -1,6 +1,6 @@
 // api_common.hpp -- what the translation units of the library's host side share (api.hip: the C ABI; api_impl64.hip / api_impl32.hip:
 // api_impl.inc + api_iterate.inc once per row precision; closures.hip, fixedlag.hip, the four marginals*.hip, dogleg.hip, evidence.hip,
-// qc_learn.hip): the handle and the host helpers.  This file launches no kernel, so including it compiles none: a unit holds the
+// qc_learn.hip, sampling.hip): the handle and the host helpers.  This file launches no kernel, so including it compiles none: a unit holds the
 // kernels its own launch statements name (level0.hip: the level-0 row and fused forms, behind kernels.hpp's declarations).
 // The marginals' state is marginals.hpp's (h->mg); device buffers free themselves (devbuf.hpp: no list names them)
 // (round 3: api.hip was one 3.5-minute translation unit; the fp64 and fp32 halves compile side by side now)
@@ -172,6 +172,13 @@ struct QcLearn {
   }
 };
 
+// gpslam_hip_sample_posterior (sampling.hip): a chunk of noise rows, the scratch copy of the landmark priors' measurements that stands
+// in for lpri.d_meas during a call, the tables' whitened errors as the call's linearisation left them, and the output slabs of a chunk
+struct Sampling {
+  DevBuf stage, pri, saveE;
+  DevBuf delta, poses, vels, lms;
+};
+
 // Work one launch leaves to a later one (chains without landmarks, unsharded: gn_mode; run_gn with Plan::fold_retract).  update: a
 // solve's step sits in the level-0 solution array, not yet applied -- the next k_lin applies it (kernels.hpp: PendUpd), or
 // flush_update.  err: the linearisation's error partial sums in `partial`, summed by an extra workgroup of this iteration's
@@ -272,6 +279,7 @@ struct gpslam_hip_handle {
   Dogleg dl;                  // gpslam_hip_iterate_dogleg (dogleg.hip)
   Evidence evd;               // gpslam_hip_log_determinant (evidence.hip)
   QcLearn qcl;                // gpslam_hip_qc_statistic (qc_learn.hip)
+  Sampling ps;                // gpslam_hip_sample_posterior (sampling.hip)
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch

@@ -35,6 +35,7 @@
 #include "../../include/gpslam_hip_dogleg.h"
 #include "../../include/gpslam_hip_evidence.h"
 #include "../../include/gpslam_hip_qc.h"
+#include "../../include/gpslam_hip_sampling.h"
 
 // boost::optional<Matrix&> -- the type of the reference's Jacobian arguments (gpslam/gp/GaussianProcessPriorPose3.h:60-64:
 // `boost::optional<gtsam::Matrix&> H1 = boost::none`).  Where Boost is installed its header is used; where it is not (this image), the
@@ -806,23 +807,28 @@ struct Session {
     std::vector<double> P((size_t)N * pd), V((size_t)N * d), LM((size_t)L * (ld ? ld : 1));
     check(gpslam_hip_get_states(h, P.data(), V.data()), h, "get_states");
     if (L > 0) check(gpslam_hip_get_landmarks(h, LM.data()), h, "get_landmarks");
-    for (auto &kv : values.raw()) {
+    scatter(values, P.data(), V.data(), LM.data());
+  }
+  // states (N x pd, N x d) and landmarks (L x ld) in the layouts of gpslam_hip_get_states / gpslam_hip_get_landmarks into the
+  // variables of `out` (the keys of this session's Values)
+  void scatter(Values &out, const double *P, const double *V, const double *LM) const {
+    for (auto &kv : out.raw()) {
       const unsigned char c = symbolChr(kv.first);
       if (kv.second.type == T_POINT2 || kv.second.type == T_POINT3) {
         const int j = lm_of(kv.first);
-        kv.second.d.assign(LM.begin() + (size_t)j * ld, LM.begin() + (size_t)(j + 1) * ld);
+        kv.second.d.assign(LM + (size_t)j * ld, LM + (size_t)(j + 1) * ld);
       } else if (c == 'v') {
         const int s = state_of(kv.first);
-        kv.second.d.assign(V.begin() + (size_t)s * d, V.begin() + (size_t)s * d + ((vw || bias) ? 3 : d));
+        kv.second.d.assign(V + (size_t)s * d, V + (size_t)s * d + ((vw || bias) ? 3 : d));
       } else if (bias && c == 'b' && kv.second.type == T_VEC3) {
         const int s = state_of(kv.first);
-        kv.second.d.assign(P.begin() + (size_t)s * pd + 9, P.begin() + (size_t)(s + 1) * pd);
+        kv.second.d.assign(P + (size_t)s * pd + 9, P + (size_t)(s + 1) * pd);
       } else if (vw && c == 'w') {
         const int s = state_of(kv.first);
-        kv.second.d.assign(V.begin() + (size_t)s * d + 3, V.begin() + (size_t)(s + 1) * d);
+        kv.second.d.assign(V + (size_t)s * d + 3, V + (size_t)(s + 1) * d);
       } else {
         const int s = state_of(kv.first);
-        kv.second.d.assign(P.begin() + (size_t)s * pd, P.begin() + (size_t)s * pd + (bias ? 9 : pd));
+        kv.second.d.assign(P + (size_t)s * pd, P + (size_t)s * pd + (bias ? 9 : pd));
       }
     }
   }
@@ -1414,6 +1420,24 @@ inline QcStatistic qcStatistic(const NonlinearFactorGraph &graph, const Values &
   detail::check(gpslam_hip_qc_statistic(s.h, q.A.a.data(), &n), s.h, "qc_statistic");
   q.priors = (long long)n;
   return q;
+}
+
+/// `count` draws from the Laplace posterior N(values, H^-1) of the graph at `values` (the caller's optimum), H = J^T J the matrix
+/// Marginals inverts (gpslam_hip_sample_posterior; include/gpslam_hip_sampling.h), on a session of its own: each draw a Values with
+/// the keys of `values` -- whole trajectories, landmarks included, from the JOINT over all variables.  Draw k depends on (seed,
+/// first + k) alone, so a run can be extended or cut into batches.  A velocity that is no variable of the graph is pinned by a
+/// unit prior (as every optimiser here does) and returns as it was given.  Graphs with loop closures or LinearContainerFactors:
+/// std::invalid_argument.
+inline std::vector<Values> samplePosterior(const NonlinearFactorGraph &graph, const Values &values, int count, uint64_t seed = 0, uint64_t first = 0) {
+  if (count <= 0) throw std::invalid_argument("samplePosterior: count must be positive");
+  detail::Session s;
+  s.build(graph, values);
+  const size_t wp = (size_t)s.N * s.pd, wv = (size_t)s.N * s.d, wl = (size_t)s.L * s.ld;
+  std::vector<double> P(count * wp), V(count * wv), LM(std::max<size_t>(count * wl, 1));
+  detail::check(gpslam_hip_sample_posterior(s.h, count, seed, first, nullptr, nullptr, P.data(), V.data(), wl ? LM.data() : nullptr), s.h, "sample_posterior");
+  std::vector<Values> out((size_t)count, s.values);
+  for (int k = 0; k < count; k++) s.scatter(out[k], P.data() + k * wp, V.data() + k * wv, LM.data() + k * wl);
+  return out;
 }
 
 // ---------------------------------------------------------------- AHRS (gtsam/navigation/AHRSFactor.h, GTSAM 4.0; third party)

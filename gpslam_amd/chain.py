@@ -79,6 +79,12 @@ QC_SYMBOLS = [
 SAMPLING_SYMBOLS = [
     "gpslam_hip_posterior_noise_dim", "gpslam_hip_posterior_noise", "gpslam_hip_sample_posterior",
 ]
+# every symbol include/gpslam_hip_noise.h declares (learning measurement noise: the per-kind statistic, the predicted covariances, the
+# gradient, the EM updates; a list of its own again)
+NOISE_SYMBOLS = [
+    "gpslam_hip_meas_noise_statistic", "gpslam_hip_meas_predicted_covariances", "gpslam_hip_noise_gradient",
+    "gpslam_hip_noise_em_update", "gpslam_hip_noise_em_scale",
+]
 # the version of include/gpslam_hip.h this binding's structs mirror (GPSLAM_HIP_ABI_MAJOR / _MINOR); load_library() checks the library's
 ABI_MAJOR, ABI_MINOR = 2, 4
 STRUCT_CONFIG, STRUCT_CONFIG_V2, STRUCT_STATS, STRUCT_PARAMS = 0, 1, 2, 3
@@ -284,6 +290,25 @@ def _qc_lib():
     return lib
 
 
+def _noise_lib():
+    """The library with the argument types of include/gpslam_hip_noise.h set (64-bit counts travel by value there)."""
+    lib = load_library()
+    if not hasattr(lib, "gpslam_hip_meas_noise_statistic"):
+        raise GpslamHipError("this libgpslam_hip.so has no noise-learning entry points (include/gpslam_hip_noise.h)")
+    if getattr(lib, "_noise_bound", False):
+        return lib
+    dp, lp, vp = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p
+    lib.gpslam_hip_meas_noise_statistic.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint8), dp, dp, lp]
+    lib.gpslam_hip_meas_predicted_covariances.argtypes = [vp, C.c_int32, dp]
+    lib.gpslam_hip_noise_gradient.argtypes = [C.c_int32, dp, dp, C.c_int64, dp]
+    lib.gpslam_hip_noise_em_update.argtypes = [C.c_int32, dp, C.c_int64, dp]
+    lib.gpslam_hip_noise_em_scale.argtypes = [C.c_int32, dp, C.c_int64, dp, dp]
+    for name in NOISE_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
+    lib._noise_bound = True
+    return lib
+
+
 def _sampling_lib():
     """The library with the argument types of include/gpslam_hip_sampling.h set (64-bit seeds and counters travel by value there)."""
     lib = load_library()
@@ -344,6 +369,43 @@ def qc_em_scale(Qc0, A, n_f):
     if rc:
         raise GpslamHipError("qc_em_scale: %d" % rc)
     return out.value
+
+
+def noise_gradient(Cov, B, n):
+    """gpslam_hip_noise_gradient (host arithmetic, no GPU): G = (n C - B) / 2, the derivative of the log-evidence in W = C^-1 at
+    fixed states (dF = tr(G dW)) when the used factors share the covariance C, from ChainSolver.meas_noise_statistic's (B, n)."""
+    c, b = _square(Cov, "noise_gradient"), _square(B, "noise_gradient")
+    if c.shape != b.shape:
+        raise GpslamHipError("noise_gradient: C and B differ in size")
+    dp = C.POINTER(C.c_double)
+    G = np.zeros_like(c)
+    rc = _noise_lib().gpslam_hip_noise_gradient(int(c.shape[0]), c.ctypes.data_as(dp), b.ctypes.data_as(dp), int(n), G.ctypes.data_as(dp))
+    if rc:
+        raise GpslamHipError("noise_gradient: %d" % rc)
+    return G
+
+
+def noise_em_update(B, n):
+    """gpslam_hip_noise_em_update (host arithmetic, no GPU): the EM M-step C+ = B / n of a covariance the used factors share."""
+    b = _square(B, "noise_em_update")
+    dp = C.POINTER(C.c_double)
+    out = np.zeros_like(b)
+    rc = _noise_lib().gpslam_hip_noise_em_update(int(b.shape[0]), b.ctypes.data_as(dp), int(n), out.ctypes.data_as(dp))
+    if rc:
+        raise GpslamHipError("noise_em_update: %d" % rc)
+    return out
+
+
+def noise_em_scale(Bw, n):
+    """gpslam_hip_noise_em_scale (host arithmetic, no GPU): (theta+ / theta, per-row ratios) = (tr(Bw) / (n r), diag(Bw) / n), the
+    stationary scales of C_m = theta C_m^0 relative to the ones Bw was whitened with."""
+    b = _square(Bw, "noise_em_scale")
+    dp = C.POINTER(C.c_double)
+    ratio, rows = C.c_double(0.0), np.zeros(b.shape[0])
+    rc = _noise_lib().gpslam_hip_noise_em_scale(int(b.shape[0]), b.ctypes.data_as(dp), int(n), C.byref(ratio), rows.ctypes.data_as(dp))
+    if rc:
+        raise GpslamHipError("noise_em_scale: %d" % rc)
+    return ratio.value, rows
 
 
 def robust_eval(loss, k, r):
@@ -755,6 +817,37 @@ class ChainSolver:
         A, n = np.zeros((self.d, self.d)), C.c_int64(0)
         self._chk(_qc_lib().gpslam_hip_qc_statistic(self._h, A.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)), "qc_statistic")
         return A, n.value
+
+    def meas_noise_statistic(self, kind, use=None):
+        """(B, Bw, n) over the factors of one MEAS_* kind whose entry of `use` is true (None: all; one entry per factor in the order
+        added), from the current marginals (include/gpslam_hip_noise.h): B = sum_m (e e^T + J Sigma_m J^T), Bw the same between the
+        factors' base whitening R_m and R_m^T, r x r.  Call marginals() first; they stay valid."""
+        r = self.MEAS_ROWS[int(kind)]
+        B, Bw, n = np.zeros((r, r)), np.zeros((r, r)), C.c_int64(0)
+        dp = C.POINTER(C.c_double)
+        m = None if use is None else np.ascontiguousarray(np.asarray(use).reshape(-1) != 0, dtype=np.uint8)
+        if m is not None:
+            count = self.meas_count(kind)
+            if count != len(m):
+                raise GpslamHipError("meas_noise_statistic: `use` has %d entries, the kind has %d factors" % (len(m), count))
+        self._chk(_noise_lib().gpslam_hip_meas_noise_statistic(self._h, int(kind), None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                               B.ctypes.data_as(dp), Bw.ctypes.data_as(dp), C.byref(n)), "meas_noise_statistic")
+        return B, Bw, n.value
+
+    def meas_count(self, kind):
+        """the number of factors of one MEAS_* kind the handle stores (gpslam_hip_meas_predicted_covariances without an output)"""
+        return self._chk(_noise_lib().gpslam_hip_meas_predicted_covariances(self._h, int(kind), None), "meas_count")
+
+    def meas_predicted_covariances(self, kind):
+        """(count, r, r): P_m = J_m Sigma_m J_m^T of every factor of one MEAS_* kind in the order added, from the current marginals
+        (include/gpslam_hip_noise.h); robust graphs are accepted.  Call marginals() first; they stay valid."""
+        r = self.MEAS_ROWS[int(kind)]
+        lib = _noise_lib()
+        count = self.meas_count(kind)
+        P = np.zeros((count, r, r))
+        if count:
+            self._chk(lib.gpslam_hip_meas_predicted_covariances(self._h, int(kind), P.ctypes.data_as(C.POINTER(C.c_double))), "meas_predicted_covariances")
+        return P
 
     def posterior_noise_dim(self):
         """length of one noise vector of sample_posterior: the rows of get_rows(), then the landmark priors' coordinates"""

@@ -733,6 +733,7 @@ int gpslam_hip_body_centric_velocity(gpslam_hip_handle *h, int32_t which, int32_
 int gpslam_hip_compile(gpslam_hip_handle *h) {
   if (!h) return GPSLAM_E_INVALID;
   h->mg.fit(h->N);   // freed now if N changed: the marginals' buffers are sized by N, and the next call may be far off
+  h->mn.invalidate();   // (the factors' order by left state, meas_noise.hip: built again at the next call)
   return GPS_BY_PRECISION_STALE(gpslam_hip_compile, h);
 }
 int gpslam_hip_linearize_gp(gpslam_hip_handle *h, double *errors, double *jacobians) {

@@ -1,6 +1,6 @@
 // api_common.hpp -- what the translation units of the library's host side share (api.hip: the C ABI; api_impl64.hip / api_impl32.hip:
 // api_impl.inc + api_iterate.inc once per row precision; closures.hip, fixedlag.hip, the four marginals*.hip, dogleg.hip, evidence.hip,
-// qc_learn.hip, sampling.hip): the handle and the host helpers.  This file launches no kernel, so including it compiles none: a unit holds the
+// qc_learn.hip, sampling.hip, meas_noise.hip): the handle and the host helpers.  This file launches no kernel, so including it compiles none: a unit holds the
 // kernels its own launch statements name (level0.hip: the level-0 row and fused forms, behind kernels.hpp's declarations).
 // The marginals' state is marginals.hpp's (h->mg); device buffers free themselves (devbuf.hpp: no list names them)
 // (round 3: api.hip was one 3.5-minute translation unit; the fp64 and fp32 halves compile side by side now)
@@ -179,6 +179,26 @@ struct Sampling {
   DevBuf delta, poses, vels, lms;
 };
 
+// gpslam_hip_meas_noise_statistic / gpslam_hip_meas_predicted_covariances (meas_noise.hip): per kind the factors' order by left state
+// (a stable sort inside every chunk of the pass, built on the host at the first call after a compile() and kept), the call's `use`
+// bytes, one 2 r x r partial per workgroup of k_mn_stat, the first reduction stage's sums with the result behind them, and a chunk's P_m
+struct MeasNoise {
+  int N = 0;                  // the N the buffers are sized for
+  DevBuf perm[kNumMeasKinds];
+  bool have[kNumMeasKinds] = {false, false, false, false, false, false, false, false};
+  DevBuf use, part, cpart, P;
+  void invalidate() { for (bool &v : have) v = false; }   // compile(): the factors may be others
+  // the buffers serve n states from here on: another N frees what is there (as Marginals::fit)
+  void fit(int n) {
+    if (N != n) {
+      for (DevBuf &p : perm) p.release();
+      for (DevBuf *p : {&use, &part, &cpart, &P}) p->release();
+      invalidate();
+    }
+    N = n;
+  }
+};
+
 // Work one launch leaves to a later one (chains without landmarks, unsharded: gn_mode; run_gn with Plan::fold_retract).  update: a
 // solve's step sits in the level-0 solution array, not yet applied -- the next k_lin applies it (kernels.hpp: PendUpd), or
 // flush_update.  err: the linearisation's error partial sums in `partial`, summed by an extra workgroup of this iteration's
@@ -280,6 +300,7 @@ struct gpslam_hip_handle {
   Evidence evd;               // gpslam_hip_log_determinant (evidence.hip)
   QcLearn qcl;                // gpslam_hip_qc_statistic (qc_learn.hip)
   Sampling ps;                // gpslam_hip_sample_posterior (sampling.hip)
+  MeasNoise mn;               // gpslam_hip_meas_noise_statistic (meas_noise.hip)
   std::string err;
 #ifdef GPS_TRACE_FUSED
   DevBuf dbg_trace;           // debug builds only: 64 stamps per wave of the last k_fused_level0 launch

@@ -38,4 +38,5 @@ int launch_factors(gpslam_hip_handle *h, const LaunchMode &m, int pass, int slot
 int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g, int pass = 0);
 int launch_solve(gpslam_hip_handle *h, const LaunchMode &m, double lambda);
 int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot);
+int launch_meas_inspect(gpslam_hip_handle *h, int kind, int first, int count, void *out_e, void *out_J);
 int fs_forward(gpslam_hip_handle *h, double lambda, double *y_own = nullptr);

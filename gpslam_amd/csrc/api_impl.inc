@@ -1731,6 +1731,36 @@ int gpslam_hip_linearize_gp(gpslam_hip_handle *h, double *errors, double *jacobi
   return F;
 }
 
+// k_meas's inspection mode on factors first .. first + count - 1 of one kind, in the order they were added: the unwhitened
+// evaluateError() values into out_e (count x rows) and [H1 H2 | H3 H4 | H5 (3, zero padded)] per row into out_J, both on the device
+// and of this namespace's row precision.  Writes them and `partial`, nothing else; no synchronisation
+int launch_meas_inspect(gpslam_hip_handle *h, int kind, int first, int count, void *out_e, void *out_J) {
+  MeasSet &s = h->ms[kind];
+  if (first < 0 || count <= 0 || first + count > s.count() || !out_e || !out_J) return GPSLAM_E_INVALID;
+  // no row tables: on an fp32 handle (this is impl64 answering for it) they hold floats, and a later solve must not find
+  // this call's rows in them either way (ADVICE r3).  (a.rob stays null: evaluateError knows no noise model)
+  MeasArgs<RowT> a = meas_args(h, kind);
+  const size_t o = (size_t)first;
+  a.count = count;
+  a.idx += o; a.row0 += o;
+  if (a.lm) a.lm += o;
+  a.meas += o * s.mw; a.sig += o * s.rows;
+  if (a.coef) a.coef += o * 4;
+  if (a.aidx) a.aidx += o;
+  if (a.sqi) a.sqi += o * s.rows * s.rows;
+  a.partial = h->partial.as<RowT>();
+  a.out_e = static_cast<RowT *>(out_e); a.out_J = static_cast<RowT *>(out_J);
+  dispatch_mf(h->mf, [&](auto tag) {
+    constexpr int MF = decltype(tag)::value;
+    dispatch_fk(kind, [&](auto ftag) {
+      constexpr int FK = decltype(ftag)::value;
+      k_meas<RowT, MF, FK, true><<<dim3(nblocks(count, 128)), dim3(128), 0, h->stream>>>(a);
+    });
+  });
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // unwhitened evaluateError + H1..H5 of every measurement factor of one kind, in the order they were added
 int gpslam_hip_linearize_meas(gpslam_hip_handle *h, int32_t kind, double *errors, double *jacobians) {
   if (!kIsF64) return impl64::gpslam_hip_linearize_meas(h, kind, errors, jacobians);   // the inspection API answers in fp64
@@ -1742,19 +1772,7 @@ int gpslam_hip_linearize_meas(gpslam_hip_handle *h, int32_t kind, double *errors
   if (F == 0) return 0;
   HIPCHK(h->api_e.reserve((size_t)F * s.rows * sizeof(RowT)));
   HIPCHK(h->api_H.reserve((size_t)F * s.rows * W * sizeof(RowT)));
-  // no row tables: on an fp32 handle (this is impl64 answering for it) they hold floats, and a later solve must not find
-  // this call's rows in them either way (ADVICE r3).  (a.rob stays null: evaluateError knows no noise model)
-  MeasArgs<RowT> a = meas_args(h, kind);
-  a.partial = h->partial.as<RowT>();
-  a.out_e = h->api_e.as<RowT>(); a.out_J = h->api_H.as<RowT>();
-  dispatch_mf(h->mf, [&](auto tag) {
-    constexpr int MF = decltype(tag)::value;
-    dispatch_fk(kind, [&](auto ftag) {
-      constexpr int FK = decltype(ftag)::value;
-      k_meas<RowT, MF, FK, true><<<dim3(nblocks(F, 128)), dim3(128), 0, h->stream>>>(a);
-    });
-  });
-  HIPCHK(hipGetLastError());
+  if ((rc = launch_meas_inspect(h, kind, 0, F, h->api_e.p, h->api_H.p))) return rc;
   HIPCHK(hipMemcpyAsync(errors, h->api_e.p, (size_t)F * s.rows * sizeof(RowT), hipMemcpyDeviceToHost, h->stream));
   if (jacobians) HIPCHK(hipMemcpyAsync(jacobians, h->api_H.p, (size_t)F * s.rows * W * sizeof(RowT), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));

@@ -35,6 +35,7 @@
 #include "../../include/gpslam_hip_dogleg.h"
 #include "../../include/gpslam_hip_evidence.h"
 #include "../../include/gpslam_hip_qc.h"
+#include "../../include/gpslam_hip_noise.h"
 #include "../../include/gpslam_hip_sampling.h"
 
 // boost::optional<Matrix&> -- the type of the reference's Jacobian arguments (gpslam/gp/GaussianProcessPriorPose3.h:60-64:
@@ -1419,6 +1420,51 @@ inline QcStatistic qcStatistic(const NonlinearFactorGraph &graph, const Values &
   int64_t n = 0;
   detail::check(gpslam_hip_qc_statistic(s.h, q.A.a.data(), &n), s.h, "qc_statistic");
   q.priors = (long long)n;
+  return q;
+}
+
+/// The statistic the measurement noise of one kind of factor is learned from (gpslam_hip_meas_noise_statistic;
+/// include/gpslam_hip_noise.h), at `values` (the caller's optimum), on a session of its own: over the graph's factors of `kind`
+/// (GPSLAM_MEAS_*), B = sum (e e^T + J Sigma J^T), Bw the same between each factor's base whitening R and R^T, and their number.
+/// gradient(C) is the derivative of the log-evidence in C^-1 at fixed states when the factors share the covariance C, emUpdate() the
+/// C that makes it zero, emScale() the stationary theta+ / theta of C_m = theta C_m^0 (rows: one ratio per row of diagonal models).
+struct MeasNoiseStatistic {
+  Matrix B, Bw;
+  long long factors = 0;
+  Matrix gradient(const Matrix &C) const {
+    Matrix G(B.rows, B.cols);
+    if (C.rows != B.rows || C.cols != B.cols || gpslam_hip_noise_gradient(B.rows, C.a.data(), B.a.data(), factors, G.a.data()))
+      throw std::invalid_argument("MeasNoiseStatistic::gradient: C must be symmetric positive definite, of the statistic's size, and the statistic must count a factor");
+    return G;
+  }
+  Matrix emUpdate() const {
+    Matrix C(B.rows, B.cols);
+    if (gpslam_hip_noise_em_update(B.rows, B.a.data(), factors, C.a.data())) throw std::invalid_argument("MeasNoiseStatistic::emUpdate: the statistic counts no factor, or B is not positive definite");
+    return C;
+  }
+  double emScale(std::vector<double> *rows = nullptr) const {
+    double ratio = 0.0;
+    if (rows) rows->assign((size_t)Bw.rows, 0.0);
+    if (gpslam_hip_noise_em_scale(Bw.rows, Bw.a.data(), factors, &ratio, rows ? rows->data() : nullptr))
+      throw std::invalid_argument("MeasNoiseStatistic::emScale: the statistic counts no factor, or Bw is not positive definite");
+    return ratio;
+  }
+};
+inline MeasNoiseStatistic measNoiseStatistic(const NonlinearFactorGraph &graph, const Values &values, int kind) {
+  static const int rows_of[8] = {1, 1, 2, 3, 3, 2, 2, 3};
+  if (kind < 0 || kind >= 8) throw std::invalid_argument("measNoiseStatistic: kind must be one of GPSLAM_MEAS_*");
+  detail::Session s;
+  s.build(graph, values);
+  // (as qcStatistic: the closures' columns kept in column passes, G kept on the segmented landmark path)
+  detail::check(gpslam_hip_marginals_keep_closure_columns(s.h, 1), s.h, "marginals_keep_closure_columns");
+  detail::check(gpslam_hip_marginals_on_segments(s.h, 1), s.h, "marginals_on_segments");
+  detail::check(gpslam_hip_marginals(s.h), s.h, "marginals");
+  MeasNoiseStatistic q;
+  q.B = Matrix(rows_of[kind], rows_of[kind]);
+  q.Bw = Matrix(rows_of[kind], rows_of[kind]);
+  int64_t n = 0;
+  detail::check(gpslam_hip_meas_noise_statistic(s.h, kind, nullptr, q.B.a.data(), q.Bw.a.data(), &n), s.h, "meas_noise_statistic");
+  q.factors = (long long)n;
   return q;
 }
 

@@ -79,6 +79,11 @@ QC_SYMBOLS = [
 SAMPLING_SYMBOLS = [
     "gpslam_hip_posterior_noise_dim", "gpslam_hip_posterior_noise", "gpslam_hip_sample_posterior",
 ]
+# every symbol include/gpslam_hip_sampling_at.h declares (the same draws at query times between the support states, with the GP's
+# conditional noise; a list of its own again)
+SAMPLING_AT_SYMBOLS = [
+    "gpslam_hip_posterior_noise_dim_at", "gpslam_hip_posterior_noise_at", "gpslam_hip_sample_posterior_at",
+]
 # every symbol include/gpslam_hip_noise.h declares (learning measurement noise: the per-kind statistic, the predicted covariances, the
 # gradient, the EM updates; a list of its own again)
 NOISE_SYMBOLS = [
@@ -323,6 +328,23 @@ def _sampling_lib():
     for name in SAMPLING_SYMBOLS:
         getattr(lib, name).restype = C.c_int
     lib._sampling_bound = True
+    return lib
+
+
+def _sampling_at_lib():
+    """The library with the argument types of include/gpslam_hip_sampling_at.h set."""
+    lib = _sampling_lib()
+    if not hasattr(lib, "gpslam_hip_sample_posterior_at"):
+        raise GpslamHipError("this libgpslam_hip.so has no dense sampling entry points (include/gpslam_hip_sampling_at.h)")
+    if getattr(lib, "_sampling_at_bound", False):
+        return lib
+    dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p
+    lib.gpslam_hip_posterior_noise_dim_at.argtypes = [vp, C.c_int32, ip]
+    lib.gpslam_hip_posterior_noise_at.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, dp]
+    lib.gpslam_hip_sample_posterior_at.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, dp, C.c_int32, ip, dp, dp, dp, dp, dp, dp, dp, dp]
+    for name in SAMPLING_AT_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
+    lib._sampling_at_bound = True
     return lib
 
 
@@ -888,6 +910,50 @@ class ChainSolver:
         rc = _sampling_lib().gpslam_hip_sample_posterior(self._h, count, int(seed), int(first), None if noise is None else noise.ctypes.data_as(dp),
                                                          *[None if a is None else a.ctypes.data_as(dp) for a in out])
         self._chk(rc, "sample_posterior")
+        return out
+
+    def posterior_noise_dim_at(self, n_queries):
+        """length of one noise vector of sample_posterior_at: posterior_noise_dim() + 2 d n_queries (per query eps_p, then eps_v)"""
+        n = C.c_int32(0)
+        self._chk(_sampling_at_lib().gpslam_hip_posterior_noise_dim_at(self._h, int(n_queries), C.byref(n)), "posterior_noise_dim_at")
+        return n.value
+
+    def posterior_noise_at(self, seed, first, count, n_queries):
+        """(count, n_noise_at): the generator's standard normals of a dense draw; the first posterior_noise_dim() columns are
+        posterior_noise()'s"""
+        out = np.zeros((max(int(count), 0), self.posterior_noise_dim_at(n_queries)))
+        rc = _sampling_at_lib().gpslam_hip_posterior_noise_at(self._h, int(seed), int(first), int(count), int(n_queries), out.ctypes.data_as(C.POINTER(C.c_double)))
+        self._chk(rc, "posterior_noise_at")
+        return out
+
+    def sample_posterior_at(self, left, dt, tau, count, seed=0, first=0, noise=None, want=("query_poses",)):
+        """count draws of the support states AND of the trajectory at the query times (left, dt, tau as interpolate_poses takes them;
+        include/gpslam_hip_sampling_at.h): each draw's queries are conditioned on that draw's own support states, with the GP's
+        conditional noise, and the queries of one interval are correlated as the prior says.  Returns (query_poses (count, n, pose_dim),
+        query_vels (count, n, d; LINEAR2 / LINEAR3 only), delta, poses, vels, landmarks) -- the last four as sample_posterior returns
+        them, for the same draws; whatever `want` does not name is None and is not copied to the host.  left is non-decreasing; within
+        an interval dt is one number and 0 < tau < dt increases strictly.  noise: (count, posterior_noise_dim_at(n))."""
+        count = int(count)
+        names = ("query_poses", "query_vels", "delta", "poses", "vels", "landmarks")
+        if not set(want) <= set(names):
+            raise GpslamHipError("sample_posterior_at: want names " + ", ".join(names))
+        left, dt, tau = _i32(left), _f64(dt), _f64(tau)
+        nq = len(left)
+        if len(dt) != nq or len(tau) != nq:
+            raise GpslamHipError("sample_posterior_at: left, dt and tau differ in length")
+        dp = C.POINTER(C.c_double)
+        if noise is not None:
+            noise = _f64(noise)
+            if noise.shape != (count, self.posterior_noise_dim_at(nq)):
+                raise GpslamHipError("sample_posterior_at: noise must be count x posterior_noise_dim_at(n_queries)")
+        nl = self.L * self.ld
+        n = max(count, 0)
+        shapes = dict(query_poses=(n, nq, self.pd), query_vels=(n, nq, self.d), delta=(n, self.N * self.b + nl), poses=(n, self.N, self.pd),
+                      vels=(n, self.N, self.d), landmarks=(n, self.L, self.ld))
+        out = tuple(np.zeros(shapes[k]) if (k in want and (k != "landmarks" or nl)) else None for k in names)
+        rc = _sampling_at_lib().gpslam_hip_sample_posterior_at(self._h, count, int(seed), int(first), None if noise is None else noise.ctypes.data_as(dp),
+                                                              nq, left.ctypes.data_as(C.POINTER(C.c_int32)), dt.ctypes.data_as(dp), tau.ctypes.data_as(dp), *[None if a is None else a.ctypes.data_as(dp) for a in out])
+        self._chk(rc, "sample_posterior_at")
         return out
 
     def run_gn(self, iters, timed=False):

@@ -177,6 +177,10 @@ struct QcLearn {
 struct Sampling {
   DevBuf stage, pri, saveE;
   DevBuf delta, poses, vels, lms;
+  // gpslam_hip_sample_posterior_at: a call's query runs (CSR over runs: first query of each, its interval), the eleven bridge
+  // coefficients of every query, and the query slabs of a chunk
+  DevBuf at_ptr, at_left, at_coef;
+  DevBuf at_poses, at_vels;
 };
 
 // gpslam_hip_meas_noise_statistic / gpslam_hip_meas_predicted_covariances (meas_noise.hip): per kind the factors' order by left state

@@ -10,8 +10,13 @@
 // gathers delta from column 0 of the level-0 solution and lm_dL and writes x^ (+) delta into the output slabs; the estimate is only read.
 // Per chunk of draws: k_ps_noise (or one copy of the caller's noise) in front, one read of the pivot flag and of the slabs behind.
 // At the end the tables' errors and the priors are put back.
+//
+// Draws at query times (include/gpslam_hip_sampling_at.h): the same loop with an optional part (PsAt).  The
+// staged noise rows are n_noise_at wide -- k_ps_noise writes the bridge's normals behind the rows', one kernel and one arithmetic for
+// both -- the pose and velocity slabs are kept whether or not the caller asks for them, and ONE k_ps_bridge launch per chunk, behind
+// the chunk's last k_ps_emit, walks every run of queries of every draw of the chunk from that draw's own support states in the slabs.
 #include "api_common.hpp"
-#include "../../include/gpslam_hip_sampling.h"
+#include "../../include/gpslam_hip_sampling_at.h"
 
 #include <cmath>
 
@@ -22,6 +27,7 @@ namespace impl64 {
 namespace {
 
 // doubles per staging / output slab at most (32 MiB): a chunk of draws is as many as fit, at least one
+// (tests/test_gpu_sampling_at.py restates this number and ps_chunk's rule as KSLAB to pick a call that spans two chunks: keep them in step)
 constexpr size_t kPsSlab = size_t(1) << 22;
 
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: Parallel random numbers: as easy as 1, 2, 3; SC'11), the key bumped before every
@@ -119,6 +125,131 @@ template <int MF> __global__ void __launch_bounds__(128) k_ps_emit(PsEmit a) {
   }
 }
 
+// doubles per query of the bridge's coefficient table: the first block rows of Lambda_k, Psi_k (l11, l12, p11, p12), the second
+// (l21, l22, p21, p22), and the Cholesky factor of K (l00, l10, l11)
+constexpr int kPsCoef = 11;
+
+struct PsBridge {
+  const double *poses, *vels;       // the chunk's support slabs: draws x N x pd, draws x N x d (what k_ps_emit wrote)
+  const double *eps;                // the chunk's staged noise rows, ldn wide; a draw's bridge normals start at column n_noise
+  const int *run_ptr, *run_left;    // CSR over runs: queries run_ptr[r] .. run_ptr[r + 1] - 1 lie in interval run_left[r]
+  const double *coef;               // nq x kPsCoef
+  int N, draws, nruns, nq, n_noise, ldn;
+  double Lq[21];                    // the lower Cholesky factor of Qc, rows packed: entry (r, c) at r (r + 1) / 2 + c
+  double *qposes, *qvels;           // the chunk's query slabs: draws x nq x pd, draws x nq x d (null: not asked for)
+};
+
+// the local variable of an interval and the way back: xb = xi(t_i+1), xdb = J v_i+1 (J = Jr^-1(xb) on SE(3), I elsewhere: the
+// interpolators' own arithmetic, factors.hpp interp_pose2 / interp_rot3 / interp_pose3), and put = T_i (+) Exp(xi)
+template <int MF> struct PsLocal;
+template <int D> struct PsLocalLinear {
+  static __device__ __forceinline__ void ends(const double *p1, const double *p2, const double *v2, double *xb, double *xdb) {
+#pragma unroll
+    for (int c = 0; c < D; c++) { xb[c] = p2[c] - p1[c]; xdb[c] = v2[c]; }
+  }
+  static __device__ __forceinline__ void put(const double *p1, const double *xi, double *o) {
+#pragma unroll
+    for (int c = 0; c < D; c++) o[c] = p1[c] + xi[c];
+  }
+};
+template <> struct PsLocal<LINEAR2> : PsLocalLinear<2> {};
+template <> struct PsLocal<LINEAR3> : PsLocalLinear<3> {};
+template <> struct PsLocal<POSE2> {
+  static __device__ __forceinline__ void ends(const double *p1, const double *p2, const double *v2, double *xb, double *xdb) {
+    const SE2<double> a = {p1[0], p1[1], p1[2]}, b = {p2[0], p2[1], p2[2]};
+    const V3<double> r = se2_log(se2_between(a, b));
+    xb[0] = r.x; xb[1] = r.y; xb[2] = r.z;
+#pragma unroll
+    for (int c = 0; c < 3; c++) xdb[c] = v2[c];
+  }
+  static __device__ __forceinline__ void put(const double *p1, const double *xi, double *o) {
+    const SE2<double> a = {p1[0], p1[1], p1[2]};
+    const SE2<double> r = se2_compose(a, se2_exp(V3<double>{xi[0], xi[1], xi[2]}));
+    o[0] = r.x; o[1] = r.y; o[2] = r.th;
+  }
+};
+template <> struct PsLocal<ROT3> {
+  static __device__ __forceinline__ void ends(const double *p1, const double *p2, const double *v2, double *xb, double *xdb) {
+    const V3<double> r = so3_log(transpose(as_m3(p1)) * as_m3(p2));
+    xb[0] = r.x; xb[1] = r.y; xb[2] = r.z;
+#pragma unroll
+    for (int c = 0; c < 3; c++) xdb[c] = v2[c];
+  }
+  static __device__ __forceinline__ void put(const double *p1, const double *xi, double *o) {
+    const M3<double> r = as_m3(p1) * so3_exp(V3<double>{xi[0], xi[1], xi[2]});
+#pragma unroll
+    for (int c = 0; c < 9; c++) o[c] = r.m[c];
+  }
+};
+template <> struct PsLocal<POSE3> {
+  static __device__ __forceinline__ void ends(const double *p1, const double *p2, const double *v2, double *xb, double *xdb) {
+    const V6<double> r = se3_log(se3_between(as_se3(p1), as_se3(p2)));
+    const V6<double> jv = se3_jrinv_k(jr_coefs(r.w), r) * as_v6(v2);
+    xb[0] = r.w.x; xb[1] = r.w.y; xb[2] = r.w.z; xb[3] = r.v.x; xb[4] = r.v.y; xb[5] = r.v.z;
+    xdb[0] = jv.w.x; xdb[1] = jv.w.y; xdb[2] = jv.w.z; xdb[3] = jv.v.x; xdb[4] = jv.v.y; xdb[5] = jv.v.z;
+  }
+  static __device__ __forceinline__ void put(const double *p1, const double *xi, double *o) {
+    const SE3<double> r = se3_compose(as_se3(p1), se3_exp(as_v6(xi)));
+#pragma unroll
+    for (int c = 0; c < 9; c++) o[c] = r.R.m[c];
+    o[9] = r.t.x; o[10] = r.t.y; o[11] = r.t.z;
+  }
+};
+
+// One work item per (draw of the chunk, run of queries): the draw's two support states of the run's interval from the slabs, the
+// interval's local variable once, then the walk over the run's queries in order
+//   gamma_k = Lambda_k gamma_k-1 + Psi_k gamma(t_i+1) + [l00 Lq eps_p; l10 Lq eps_p + l11 Lq eps_v]
+// and T_i (+) Exp(xi_k) per query into the query slab.  Neighbouring work items are neighbouring runs of one draw.  No atomics.
+// A work item's records (eleven coefficients and 2 d normals read, pose_dim doubles written per query) lie a whole run from its
+// neighbour's.  Measured: that costs bandwidth from four queries per run on, and staging the workgroup's
+// queries through LDS in tiles of 128 -- copies in and out with consecutive lanes on consecutive doubles -- was 1.5 to 2.6 times
+// SLOWER at 1e6 SE(3) states: a tile of 128 queries holds 128 / m runs of m queries, so 1 / m of the lanes walk while the rest wait at
+// the tile's barriers.  The direct form stays.
+template <int MF> __global__ void __launch_bounds__(128) k_ps_bridge(PsBridge a) {
+  constexpr int d = MTraits<MF>::d, pd = MTraits<MF>::pd;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)a.draws * a.nruns) return;
+  const int k = (int)(t / (size_t)a.nruns), run = (int)(t - (size_t)k * a.nruns);
+  const int i = a.run_left[run], q1 = a.run_ptr[run + 1];
+  const double *P = a.poses + ((size_t)k * a.N + i) * pd, *V = a.vels + ((size_t)k * a.N + i) * d;
+  double p1[pd], xb[d], xdb[d], xi[d], xd[d];
+  {
+    double p2[pd], v2[d];
+#pragma unroll
+    for (int c = 0; c < pd; c++) { p1[c] = P[c]; p2[c] = P[pd + c]; }
+#pragma unroll
+    for (int c = 0; c < d; c++) { xi[c] = 0.0; xd[c] = V[c]; v2[c] = V[d + c]; }     // gamma_0 = [0; v_i]
+    PsLocal<MF>::ends(p1, p2, v2, xb, xdb);
+  }
+  const double *eps = a.eps + (size_t)k * a.ldn + a.n_noise;
+  for (int q = a.run_ptr[run]; q < q1; q++) {
+    const double *cf = a.coef + (size_t)q * kPsCoef, *e = eps + (size_t)q * (2 * d);
+    const double l11 = cf[0], l12 = cf[1], p11 = cf[2], p12 = cf[3], l21 = cf[4], l22 = cf[5], p21 = cf[6], p22 = cf[7];
+    const double c00 = cf[8], c10 = cf[9], c11 = cf[10];
+    double ep[d], ev[d];
+#pragma unroll
+    for (int c = 0; c < d; c++) { ep[c] = e[c]; ev[c] = e[d + c]; }
+#pragma unroll
+    for (int r = 0; r < d; r++) {
+      double wp = 0.0, wv = 0.0;
+#pragma unroll
+      for (int c = 0; c <= r; c++) { wp += a.Lq[r * (r + 1) / 2 + c] * ep[c]; wv += a.Lq[r * (r + 1) / 2 + c] * ev[c]; }
+      const double x0 = xi[r], x1 = xd[r];
+      xi[r] = l11 * x0 + l12 * x1 + p11 * xb[r] + p12 * xdb[r] + c00 * wp;
+      xd[r] = l21 * x0 + l22 * x1 + p21 * xb[r] + p22 * xdb[r] + c10 * wp + c11 * wv;
+    }
+    const size_t at = (size_t)k * a.nq + q;
+    double o[pd];
+    PsLocal<MF>::put(p1, xi, o);
+#pragma unroll
+    for (int c = 0; c < pd; c++) a.qposes[at * pd + c] = o[c];
+    if (a.qvels) {
+#pragma unroll
+      for (int c = 0; c < d; c++) a.qvels[at * d + c] = xd[c];
+    }
+  }
+}
+
 // every refusal, before anything is launched
 int ps_guard(gpslam_hip_handle *h, const char *what) {
   int rc = need_compiled(h);
@@ -138,9 +269,19 @@ int ps_guard(gpslam_hip_handle *h, const char *what) {
 
 int ps_noise_dim(const gpslam_hip_handle *h) { return h->M + h->Mc + h->lpri.count() * h->ld; }
 
-// draws per chunk: the widest slab row decides
-int ps_chunk(const gpslam_hip_handle *h, int count) {
-  const size_t widest = std::max<size_t>({(size_t)ps_noise_dim(h), (size_t)h->N * h->b + (size_t)h->nl, (size_t)h->N * h->pd, 1});
+// the optional part of a call: draws at query times (gpslam_hip_sample_posterior_at).  The runs and the coefficient table are on
+// the device (h->ps.at_ptr, at_left, at_coef) before ps_sample is called
+struct PsAt {
+  int nq, nruns;
+  double Lq[21];
+  double *qposes, *qvels;   // the caller's outputs; either may be null
+};
+
+// draws per chunk: the widest slab row decides (with queries: the noise row with the bridge's normals, the query poses)
+int ps_chunk(const gpslam_hip_handle *h, int count, const PsAt *at = nullptr) {
+  const size_t nq = at ? (size_t)at->nq : 0;
+  const size_t widest = std::max<size_t>({(size_t)ps_noise_dim(h) + 2 * (size_t)h->d * nq, (size_t)h->N * h->b + (size_t)h->nl, (size_t)h->N * h->pd,
+                                          nq * h->pd, 1});
   return (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kPsSlab / widest));
 }
 
@@ -164,16 +305,23 @@ struct PsOut {
   double *delta, *poses, *vels, *lms;
 };
 
-// the draws, chunk by chunk, over the linearisation in place
-int ps_draws(gpslam_hip_handle *h, const LaunchMode &m, int count, uint64_t seed, uint64_t first, const double *noise, const PsOut &o) {
+// the draws, chunk by chunk, over the linearisation in place; at: the queries' part (null: gpslam_hip_sample_posterior, which
+// launches what it always launched)
+int ps_draws(gpslam_hip_handle *h, const LaunchMode &m, int count, uint64_t seed, uint64_t first, const double *noise, const PsOut &o,
+             const PsAt *at = nullptr) {
   int rc;
-  const int N = h->N, b = h->b, nl = h->nl, n_noise = ps_noise_dim(h), chunk = ps_chunk(h, count);
+  const int N = h->N, b = h->b, nl = h->nl, n_noise = ps_noise_dim(h), chunk = ps_chunk(h, count, at);
+  const int ldn = n_noise + (at ? 2 * h->d * at->nq : 0);          // a staged noise row
+  const bool sp = o.poses || at, sv = o.vels || at;                // the bridge reads a draw's support states from the slabs
   const size_t wd = (size_t)N * b + nl, wp = (size_t)N * h->pd, wv = (size_t)N * h->d;
-  HIPCHK(h->ps.stage.reserve(std::max<size_t>((size_t)chunk * n_noise, 1) * sizeof(double)));
+  const size_t wqp = at ? (size_t)at->nq * h->pd : 0, wqv = at ? (size_t)at->nq * h->d : 0;
+  HIPCHK(h->ps.stage.reserve(std::max<size_t>((size_t)chunk * ldn, 1) * sizeof(double)));
   if (o.delta) HIPCHK(h->ps.delta.reserve((size_t)chunk * wd * sizeof(double)));
-  if (o.poses) HIPCHK(h->ps.poses.reserve((size_t)chunk * wp * sizeof(double)));
-  if (o.vels) HIPCHK(h->ps.vels.reserve((size_t)chunk * wv * sizeof(double)));
+  if (sp) HIPCHK(h->ps.poses.reserve((size_t)chunk * wp * sizeof(double)));
+  if (sv) HIPCHK(h->ps.vels.reserve((size_t)chunk * wv * sizeof(double)));
   if (o.lms && nl > 0) HIPCHK(h->ps.lms.reserve((size_t)chunk * nl * sizeof(double)));
+  if (at) HIPCHK(h->ps.at_poses.reserve((size_t)chunk * wqp * sizeof(double)));
+  if (at && at->qvels) HIPCHK(h->ps.at_vels.reserve((size_t)chunk * wqv * sizeof(double)));
   PsPlace pa;
   pa.M = h->M; pa.Mc = h->Mc; pa.npri = h->lpri.count(); pa.ld = h->ld;
   pa.rowE = h->rowE.as<double>(); pa.rowCE = h->rowCE.as<double>();
@@ -184,21 +332,43 @@ int ps_draws(gpslam_hip_handle *h, const LaunchMode &m, int count, uint64_t seed
   ea.pose = h->pose.as<double>(); ea.vel = h->vel.as<double>(); ea.lmk = h->lmk.as<double>();
   ea.N = N; ea.R = h->R; ea.stride = h->stride; ea.chart = h->cfg.chart; ea.nl = nl;
   ea.pad0 = h->mf == ROT3_BIAS ? 9 : b;
+  PsBridge ba;
+  if (at) {
+    ba.poses = h->ps.poses.as<double>(); ba.vels = h->ps.vels.as<double>(); ba.eps = h->ps.stage.as<double>();
+    ba.run_ptr = h->ps.at_ptr.as<int>(); ba.run_left = h->ps.at_left.as<int>(); ba.coef = h->ps.at_coef.as<double>();
+    ba.N = N; ba.nruns = at->nruns; ba.nq = at->nq; ba.n_noise = n_noise; ba.ldn = ldn;
+    std::memcpy(ba.Lq, at->Lq, sizeof(ba.Lq));
+    ba.qposes = h->ps.at_poses.as<double>(); ba.qvels = at->qvels ? h->ps.at_vels.as<double>() : nullptr;
+  }
   for (int k0 = 0; k0 < count; k0 += chunk) {
     const int nk = std::min(chunk, count - k0);
     double *stage = h->ps.stage.as<double>();
     if (noise) {
-      if (n_noise > 0) HIPCHK(hipMemcpyAsync(stage, noise + (size_t)k0 * n_noise, (size_t)nk * n_noise * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    } else if (n_noise > 0 && (rc = ps_generate(h, seed, first + (uint64_t)k0, nk, n_noise, stage))) return rc;
+      if (ldn > 0) HIPCHK(hipMemcpyAsync(stage, noise + (size_t)k0 * ldn, (size_t)nk * ldn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    } else if (ldn > 0 && (rc = ps_generate(h, seed, first + (uint64_t)k0, nk, ldn, stage))) return rc;
     for (int k = 0; k < nk; k++) {
-      pa.eps = stage + (size_t)k * n_noise;
+      pa.eps = stage + (size_t)k * ldn;
       if (n_noise > 0) k_ps_place<<<dim3(nblocks(n_noise, 256)), dim3(256), 0, h->stream>>>(pa);
       if ((rc = impl64::launch_assemble(h, m, false)) || (rc = impl64::launch_solve(h, m, 0.0))) return rc;
       ea.delta = o.delta ? h->ps.delta.as<double>() + (size_t)k * wd : nullptr;
-      ea.poses = o.poses ? h->ps.poses.as<double>() + (size_t)k * wp : nullptr;
-      ea.vels = o.vels ? h->ps.vels.as<double>() + (size_t)k * wv : nullptr;
+      ea.poses = sp ? h->ps.poses.as<double>() + (size_t)k * wp : nullptr;
+      ea.vels = sv ? h->ps.vels.as<double>() + (size_t)k * wv : nullptr;
       ea.lms = (o.lms && nl > 0) ? h->ps.lms.as<double>() + (size_t)k * nl : nullptr;
       dispatch_mf(h->mf, [&](auto tag) { k_ps_emit<decltype(tag)::value><<<dim3(nblocks(N + nl, 128)), dim3(128), 0, h->stream>>>(ea); });
+      HIPCHK(hipGetLastError());
+    }
+    if (at) {
+      // the chunk's queries in one launch: draws x runs work items
+      ba.draws = nk;
+      const unsigned nb = (unsigned)(((size_t)nk * at->nruns + 127) / 128);
+      switch (h->mf) {      // (ps_at_guard has refused GPSLAM_ROT3_BIAS)
+        case LINEAR2: k_ps_bridge<LINEAR2><<<dim3(nb), dim3(128), 0, h->stream>>>(ba); break;
+        case LINEAR3: k_ps_bridge<LINEAR3><<<dim3(nb), dim3(128), 0, h->stream>>>(ba); break;
+        case POSE2: k_ps_bridge<POSE2><<<dim3(nb), dim3(128), 0, h->stream>>>(ba); break;
+        case ROT3: k_ps_bridge<ROT3><<<dim3(nb), dim3(128), 0, h->stream>>>(ba); break;
+        case POSE3: k_ps_bridge<POSE3><<<dim3(nb), dim3(128), 0, h->stream>>>(ba); break;
+        default: return fail(h, GPSLAM_E_UNSUPPORTED, "sample_posterior_at: no bridge kernel for this manifold");
+      }
       HIPCHK(hipGetLastError());
     }
     // the one read of a chunk: the pivot flag (sticky over the chunk's solves), then the slabs
@@ -210,12 +380,14 @@ int ps_draws(gpslam_hip_handle *h, const LaunchMode &m, int count, uint64_t seed
     if (o.poses) HIPCHK(hipMemcpyAsync(o.poses + (size_t)k0 * wp, h->ps.poses.p, (size_t)nk * wp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (o.vels) HIPCHK(hipMemcpyAsync(o.vels + (size_t)k0 * wv, h->ps.vels.p, (size_t)nk * wv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (o.lms && nl > 0) HIPCHK(hipMemcpyAsync(o.lms + (size_t)k0 * nl, h->ps.lms.p, (size_t)nk * nl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (at && at->qposes) HIPCHK(hipMemcpyAsync(at->qposes + (size_t)k0 * wqp, h->ps.at_poses.p, (size_t)nk * wqp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (at && at->qvels) HIPCHK(hipMemcpyAsync(at->qvels + (size_t)k0 * wqv, h->ps.at_vels.p, (size_t)nk * wqv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   return 0;
 }
 
-int ps_sample(gpslam_hip_handle *h, int count, uint64_t seed, uint64_t first, const double *noise, const PsOut &o) {
+int ps_sample(gpslam_hip_handle *h, int count, uint64_t seed, uint64_t first, const double *noise, const PsOut &o, const PsAt *at = nullptr) {
   int rc;
   h->mg.invalidate();             // the solver's buffers, which the marginals' getters read, are rewritten below
   const size_t nE = (size_t)h->M * sizeof(double), nCE = (size_t)h->Mc * sizeof(double);
@@ -234,13 +406,87 @@ int ps_sample(gpslam_hip_handle *h, int count, uint64_t seed, uint64_t first, co
   {
     PsPriors guard(h);            // (back in place on every way out of this block)
     if (npri) guard.swap();
-    rc = ps_draws(h, m, count, seed, first, noise, o);
+    rc = ps_draws(h, m, count, seed, first, noise, o, at);
   }
   // the linearisation's own errors back into the tables: the handle is as a call of gpslam_hip_get_rows leaves it
   if (nE) HIPCHK(hipMemcpyAsync(h->rowE.p, save, nE, hipMemcpyDeviceToDevice, h->stream));
   if (nCE) HIPCHK(hipMemcpyAsync(h->rowCE.p, save + nE, nCE, hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return rc;
+}
+
+// the generator's numbers for count samples, `width` per sample, to the host
+int ps_noise_out(gpslam_hip_handle *h, uint64_t seed, uint64_t first, int count, int width, double *noise) {
+  int rc;
+  if (width == 0) return 0;
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kPsSlab / (size_t)width));
+  HIPCHK(h->ps.stage.reserve((size_t)chunk * width * sizeof(double)));
+  for (int k0 = 0; k0 < count; k0 += chunk) {
+    const int nk = std::min(chunk, count - k0);
+    if ((rc = ps_generate(h, seed, first + (uint64_t)k0, nk, width, h->ps.stage.as<double>()))) return rc;
+    HIPCHK(hipMemcpyAsync(noise + (size_t)k0 * width, h->ps.stage.p, (size_t)nk * width * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return 0;
+}
+
+// n_noise_at = n_noise + 2 d n_queries, or (negative) the refusal of a width that an int32 does not hold
+int ps_at_width(gpslam_hip_handle *h, int n_queries, const char *what) {
+  const int64_t w = (int64_t)ps_noise_dim(h) + 2 * (int64_t)h->d * n_queries;
+  if (w > INT32_MAX) return fail(h, GPSLAM_E_INVALID, (std::string(what) + ": the noise vector of that many queries is longer than 2^31 - 1").c_str());
+  return (int)w;
+}
+
+// what the bridge refuses on top of ps_guard, before anything is launched
+int ps_at_guard(gpslam_hip_handle *h, bool query_vels) {
+  const char *why = nullptr;
+  bool own_qc = false;
+  for (int32_t q : h->gp_q) own_qc = own_qc || q != 0;
+  if (h->mf == ROT3_BIAS) why = "GPSLAM_ROT3_BIAS handles (the bias is held over an interval, not interpolated)";
+  else if (h->vw) why = "world-frame velocities (velocity_world: the interval's local variable differs)";
+  else if (own_qc) why = "GP priors with a Qc of their own (gpslam_hip_add_gp_priors_qc): the bridge's noise is the handle's Qc";
+  else if (query_vels && h->mf != LINEAR2 && h->mf != LINEAR3) why = "query_vels on a Lie group (GPSLAM_LINEAR2 / LINEAR3 only, as interpolate_velocities)";
+  if (why) return fail(h, GPSLAM_E_UNSUPPORTED, (std::string("sample_posterior_at: not supported on ") + why).c_str());
+  return 0;
+}
+
+// the queries checked and cut into runs, the bridge's coefficients of every query and the Cholesky factor of Qc; the tables uploaded
+int ps_at_upload(gpslam_hip_handle *h, int nq, const int32_t *left, const double *dt, const double *tau, PsAt &at) {
+  if (h->N < 2) return fail(h, GPSLAM_E_INVALID, "sample_posterior_at: interpolation needs at least two states");
+  auto bad = [&](int q, const char *msg) { return fail(h, GPSLAM_E_INVALID, ("sample_posterior_at: query " + std::to_string(q) + ": " + msg).c_str()); };
+  std::vector<int> ptr, rl;
+  std::vector<double> coef((size_t)nq * kPsCoef);
+  for (int q = 0; q < nq; q++) {
+    if (left[q] < 0 || left[q] > h->N - 2) return bad(q, "interval out of range (0 .. N - 2)");
+    if (q > 0 && left[q] < left[q - 1]) return bad(q, "left must be non-decreasing");
+    const bool head = q == 0 || left[q] != left[q - 1];
+    if (!(dt[q] > 0.0)) return bad(q, "delta_t must be positive");
+    if (!head && dt[q] != dt[q - 1]) return bad(q, "delta_t differs within one interval");
+    if (!(tau[q] > 0.0) || !(tau[q] < dt[q])) return bad(q, "tau must lie inside (0, delta_t): the ends and extrapolation are not sampled");
+    if (!head && !(tau[q] > tau[q - 1])) return bad(q, "tau must increase strictly within one interval");
+    if (head) { ptr.push_back(q); rl.push_back(left[q]); }
+    // (a, tau, b) = (the query before or 0, tau, dt): Psi = Q(u) Phi(s)^T Q(T)^-1, Lambda = Phi(u) - Psi Phi(T), K = l l^T in closed
+    // forms without cancellation (the header has them)
+    const double a = head ? 0.0 : tau[q - 1], u = tau[q] - a, s = dt[q] - tau[q], T = dt[q] - a, T2 = T * T, T3 = T2 * T, us = u * s;
+    double *c = &coef[(size_t)q * kPsCoef];
+    c[0] = s * s * (3.0 * u + s) / T3; c[1] = u * s * s / T2; c[2] = u * u * (u + 3.0 * s) / T3; c[3] = -u * u * s / T2;
+    c[4] = -6.0 * us / T3; c[5] = s * (s - 2.0 * u) / T2; c[6] = 6.0 * us / T3; c[7] = u * (u - 2.0 * s) / T2;
+    c[8] = us * std::sqrt(us) / std::sqrt(3.0 * T3); c[9] = std::sqrt(3.0) * (s - u) * std::sqrt(us) / (2.0 * T * std::sqrt(T));
+    c[10] = 0.5 * std::sqrt(us / T);
+  }
+  ptr.push_back(nq);
+  at.nq = nq; at.nruns = (int)rl.size();
+  // Qc = U^T U: L_q = U^T, rows packed
+  const int d = h->d;
+  double U[36];
+  std::memcpy(U, h->Qc, sizeof(double) * d * d);
+  if (!spd_chol_upper(d, U)) return fail(h, GPSLAM_E_INVALID, "sample_posterior_at: Qc is not positive definite");
+  std::memset(at.Lq, 0, sizeof(at.Lq));
+  for (int r = 0; r < d; r++)
+    for (int c = 0; c <= r; c++) at.Lq[r * (r + 1) / 2 + c] = U[c * d + r];
+  int rc;
+  if ((rc = upload(h, h->ps.at_ptr, ptr)) || (rc = upload(h, h->ps.at_left, rl)) || (rc = upload(h, h->ps.at_coef, coef))) return rc;
+  return 0;
 }
 
 }  // namespace
@@ -259,17 +505,39 @@ int gpslam_hip_posterior_noise(gpslam_hip_handle *h, uint64_t seed, uint64_t fir
   if (!h || count <= 0 || !noise) return GPSLAM_E_INVALID;
   int rc = need_local(h);
   if (rc) return rc;
-  const int n_noise = ps_noise_dim(h);
-  if (n_noise == 0) return 0;
-  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kPsSlab / (size_t)n_noise));
-  HIPCHK(h->ps.stage.reserve((size_t)chunk * n_noise * sizeof(double)));
-  for (int k0 = 0; k0 < count; k0 += chunk) {
-    const int nk = std::min(chunk, count - k0);
-    if ((rc = ps_generate(h, seed, first + (uint64_t)k0, nk, n_noise, h->ps.stage.as<double>()))) return rc;
-    HIPCHK(hipMemcpyAsync(noise + (size_t)k0 * n_noise, h->ps.stage.p, (size_t)nk * n_noise * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
+  return ps_noise_out(h, seed, first, count, ps_noise_dim(h), noise);
+}
+
+int gpslam_hip_posterior_noise_dim_at(gpslam_hip_handle *h, int32_t n_queries, int32_t *n_noise_at) {
+  int rc = need_compiled(h);
+  if (rc) return rc;
+  if (!n_noise_at || n_queries <= 0) return GPSLAM_E_INVALID;
+  if ((rc = ps_at_width(h, n_queries, "posterior_noise_dim_at")) < 0) return rc;
+  *n_noise_at = (int32_t)rc;
   return 0;
+}
+
+int gpslam_hip_posterior_noise_at(gpslam_hip_handle *h, uint64_t seed, uint64_t first, int32_t count, int32_t n_queries, double *noise) {
+  if (!h || count <= 0 || n_queries <= 0 || !noise) return GPSLAM_E_INVALID;
+  int rc = need_local(h);
+  if (rc) return rc;
+  if ((rc = ps_at_width(h, n_queries, "posterior_noise_at")) < 0) return rc;
+  return ps_noise_out(h, seed, first, count, rc, noise);
+}
+
+int gpslam_hip_sample_posterior_at(gpslam_hip_handle *h, int32_t count, uint64_t seed, uint64_t first, const double *noise,
+                                   int32_t n_queries, const int32_t *left, const double *dt, const double *tau,
+                                   double *query_poses, double *query_vels,
+                                   double *delta, double *poses, double *vels, double *landmarks) {
+  if (!h || count <= 0 || n_queries <= 0 || !left || !dt || !tau) return GPSLAM_E_INVALID;
+  if (!query_poses && !query_vels && !delta && !poses && !vels && !landmarks) return GPSLAM_E_INVALID;
+  int rc = ps_guard(h, "sample_posterior_at");
+  if (rc || (rc = ps_at_guard(h, query_vels != nullptr))) return rc;
+  if ((rc = ps_at_width(h, n_queries, "sample_posterior_at")) < 0) return rc;
+  PsAt at;
+  at.qposes = query_poses; at.qvels = query_vels;
+  if ((rc = ps_at_upload(h, n_queries, left, dt, tau, at))) return rc;
+  return ps_sample(h, count, seed, first, noise, PsOut{delta, poses, vels, landmarks}, &at);
 }
 
 int gpslam_hip_sample_posterior(gpslam_hip_handle *h, int32_t count, uint64_t seed, uint64_t first,

@@ -37,6 +37,7 @@
 #include "../../include/gpslam_hip_qc.h"
 #include "../../include/gpslam_hip_noise.h"
 #include "../../include/gpslam_hip_sampling.h"
+#include "../../include/gpslam_hip_sampling_at.h"
 
 // boost::optional<Matrix&> -- the type of the reference's Jacobian arguments (gpslam/gp/GaussianProcessPriorPose3.h:60-64:
 // `boost::optional<gtsam::Matrix&> H1 = boost::none`).  Where Boost is installed its header is used; where it is not (this image), the
@@ -1483,6 +1484,45 @@ inline std::vector<Values> samplePosterior(const NonlinearFactorGraph &graph, co
   detail::check(gpslam_hip_sample_posterior(s.h, count, seed, first, nullptr, nullptr, P.data(), V.data(), wl ? LM.data() : nullptr), s.h, "sample_posterior");
   std::vector<Values> out((size_t)count, s.values);
   for (int k = 0; k < count; k++) s.scatter(out[k], P.data() + k * wp, V.data() + k * wv, LM.data() + k * wl);
+  return out;
+}
+
+/// The same draws in continuous time (gpslam_hip_sample_posterior_at; include/gpslam_hip_sampling_at.h): per draw the support
+/// states as samplePosterior returns them AND the pose at time tau[q] after the state with pose key left[q] (interval length dt[q]),
+/// conditioned on that draw's own support states, with the GP's conditional noise and the correlation of the queries that share an
+/// interval.  Queries are ordered along the chain; within an interval dt is one number and 0 < tau < dt increases strictly.  The
+/// bridge's noise is the Qc_model the graph's GP priors share: a graph whose GP priors differ in Qc_model, GPSLAM_ROT3_BIAS chains and
+/// world-frame velocities are refused (std::invalid_argument).
+template <typename POSE> struct PosteriorDrawsAt {
+  std::vector<Values> support;               // count draws, the keys of `values`
+  std::vector<std::vector<POSE>> queries;    // count x the queries
+};
+template <typename POSE>
+inline PosteriorDrawsAt<POSE> samplePosteriorAt(const NonlinearFactorGraph &graph, const Values &values, const std::vector<Key> &left,
+                                                const std::vector<double> &dt, const std::vector<double> &tau, int count, uint64_t seed = 0,
+                                                uint64_t first = 0) {
+  if (count <= 0) throw std::invalid_argument("samplePosteriorAt: count must be positive");
+  if (left.empty() || left.size() != dt.size() || left.size() != tau.size()) throw std::invalid_argument("samplePosteriorAt: size mismatch");
+  detail::Session s;
+  s.share_qc = true;          // (GP priors of the graph's first Qc_model use the handle's Qc: the one the bridge draws with)
+  s.build(graph, values);
+  const size_t nq = left.size();
+  std::vector<int32_t> idx(nq);
+  for (size_t q = 0; q < nq; q++) idx[q] = s.state_of(left[q]);
+  const size_t wp = (size_t)s.N * s.pd, wv = (size_t)s.N * s.d, wl = (size_t)s.L * s.ld, wq = nq * (size_t)s.pd;
+  std::vector<double> P(count * wp), V(count * wv), LM(std::max<size_t>(count * wl, 1)), Q(count * wq);
+  detail::check(gpslam_hip_sample_posterior_at(s.h, count, seed, first, nullptr, (int32_t)nq, idx.data(), dt.data(), tau.data(), Q.data(), nullptr,
+                                               nullptr, P.data(), V.data(), wl ? LM.data() : nullptr), s.h, "sample_posterior_at");
+  PosteriorDrawsAt<POSE> out;
+  out.support.assign((size_t)count, s.values);
+  out.queries.resize((size_t)count);
+  for (int k = 0; k < count; k++) {
+    s.scatter(out.support[k], P.data() + k * wp, V.data() + k * wv, LM.data() + k * wl);
+    for (size_t q = 0; q < nq; q++) {
+      const double *r = Q.data() + k * wq + q * s.pd;
+      out.queries[k].push_back(detail::VT<POSE>::un(std::vector<double>(r, r + s.pd)));
+    }
+  }
   return out;
 }
 

@@ -84,6 +84,11 @@ SAMPLING_SYMBOLS = [
 SAMPLING_AT_SYMBOLS = [
     "gpslam_hip_posterior_noise_dim_at", "gpslam_hip_posterior_noise_at", "gpslam_hip_sample_posterior_at",
 ]
+# every symbol include/gpslam_hip_sampling_stats.h declares (those draws reduced on the device to moment sums, collision counts,
+# clearances and path lengths; a list of its own again)
+SAMPLING_STATS_SYMBOLS = [
+    "gpslam_hip_sample_posterior_stats", "gpslam_hip_posterior_moments",
+]
 # every symbol include/gpslam_hip_noise.h declares (learning measurement noise: the per-kind statistic, the predicted covariances, the
 # gradient, the EM updates; a list of its own again)
 NOISE_SYMBOLS = [
@@ -345,6 +350,23 @@ def _sampling_at_lib():
     for name in SAMPLING_AT_SYMBOLS:
         getattr(lib, name).restype = C.c_int
     lib._sampling_at_bound = True
+    return lib
+
+
+def _sampling_stats_lib():
+    """The library with the argument types of include/gpslam_hip_sampling_stats.h set."""
+    lib = _sampling_at_lib()
+    if not hasattr(lib, "gpslam_hip_sample_posterior_stats"):
+        raise GpslamHipError("this libgpslam_hip.so has no sampling statistics entry points (include/gpslam_hip_sampling_stats.h)")
+    if getattr(lib, "_sampling_stats_bound", False):
+        return lib
+    dp, ip, lp, vp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_void_p
+    lib.gpslam_hip_sample_posterior_stats.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, dp, C.c_int32, ip, dp, dp,
+                                                      C.c_int32, dp, C.c_double, C.c_int32, lp, dp, dp, lp, dp, dp]
+    lib.gpslam_hip_posterior_moments.argtypes = [C.c_int32, C.c_int32, C.c_int64, dp, dp, dp, dp]
+    for name in SAMPLING_STATS_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
+    lib._sampling_stats_bound = True
     return lib
 
 
@@ -955,6 +977,92 @@ class ChainSolver:
                                                               nq, left.ctypes.data_as(C.POINTER(C.c_int32)), dt.ctypes.data_as(dp), tau.ctypes.data_as(dp), *[None if a is None else a.ctypes.data_as(dp) for a in out])
         self._chk(rc, "sample_posterior_at")
         return out
+
+    def sample_posterior_stats(self, left, dt, tau, count, seed=0, first=0, noise=None, obstacles=None, margin=0.0, want=None, resume=None):
+        """count draws at the query times as sample_posterior_at makes them, reduced on the device (include/gpslam_hip_sampling_stats.h):
+        no query pose comes to the host.  Returns a dict:
+          n                 the number of draws in the per-query sums
+          s1, s2            (n_queries, d), (n_queries, d (d + 1) / 2): sums of the local coordinates eta of the draws' query poses
+                            around interpolate_poses() of the estimate, under the handle's chart, and of the lower triangle of eta eta^T
+          mean, cov         posterior_moments(n, s1, s2) (cov None with fewer than two draws)
+          hits              (n_queries,) int64: draws with a clearance below zero at that query
+          clearance, length (count,): min over the queries of (distance to the nearest obstacle's surface - margin), and the length of
+                            the polyline through the query positions -- of THIS call's draws
+        obstacles: (n, w + 1) rows of centre and radius, w = 3 on POSE3 and 2 elsewhere.  want: a subset of ("moments", "hits",
+        "clearance", "length"); by default the moments, hits and clearance when obstacles are given, and the length where poses have a
+        position (not ROT3).  What is not asked for is None.  resume: an earlier result over the same queries to continue -- its n,
+        s1, s2 and hits are the starting values, and the result equals one call over all the draws to the bit."""
+        count = int(count)
+        names = ("moments", "hits", "clearance", "length")
+        if obstacles is not None:
+            obstacles = _f64(obstacles)
+            if obstacles.ndim != 2 or obstacles.shape[1] != (4 if self.kind == POSE3 else 3):
+                raise GpslamHipError("sample_posterior_stats: obstacles must be n x (w + 1): a centre, then a radius")
+        n_obs = 0 if obstacles is None else len(obstacles)
+        if want is None:
+            want = ("moments",) + (("hits", "clearance") if n_obs else ()) + (("length",) if self.kind != ROT3 else ())
+        if not set(want) <= set(names):
+            raise GpslamHipError("sample_posterior_stats: want names " + ", ".join(names))
+        left, dt, tau = _i32(left), _f64(dt), _f64(tau)
+        nq = len(left)
+        if len(dt) != nq or len(tau) != nq:
+            raise GpslamHipError("sample_posterior_stats: left, dt and tau differ in length")
+        dp, lp = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        if noise is not None:
+            noise = _f64(noise)
+            if noise.shape != (count, self.posterior_noise_dim_at(nq)):
+                raise GpslamHipError("sample_posterior_stats: noise must be count x posterior_noise_dim_at(n_queries)")
+        d, n = self.d, max(count, 0)
+        tri = d * (d + 1) // 2
+        mom, hit = "moments" in want, "hits" in want
+        n_draws = C.c_int64(0)
+        s1 = s2 = hits = None
+        if resume is not None:
+            if (mom and resume["s1"] is None) or (hit and resume["hits"] is None):
+                raise GpslamHipError("sample_posterior_stats: resume lacks the sums this call asks for")
+            n_draws = C.c_int64(int(resume["n"]))
+            if mom:
+                s1, s2 = _f64(resume["s1"]).copy(), _f64(resume["s2"]).copy()
+                if s1.shape != (nq, d) or s2.shape != (nq, tri):
+                    raise GpslamHipError("sample_posterior_stats: resume holds sums of other queries")
+            if hit:
+                hits = np.ascontiguousarray(np.asarray(resume["hits"], dtype=np.int64)).copy()
+                if hits.shape != (nq,):
+                    raise GpslamHipError("sample_posterior_stats: resume holds counts of other queries")
+        else:
+            if mom:
+                s1, s2 = np.zeros((nq, d)), np.zeros((nq, tri))
+            if hit:
+                hits = np.zeros(nq, dtype=np.int64)
+        clearance = np.zeros(n) if "clearance" in want else None
+        length = np.zeros(n) if "length" in want else None
+        opt = lambda a, t: None if a is None else a.ctypes.data_as(t)
+        rc = _sampling_stats_lib().gpslam_hip_sample_posterior_stats(
+            self._h, count, int(seed), int(first), opt(noise, dp), nq, left.ctypes.data_as(C.POINTER(C.c_int32)), dt.ctypes.data_as(dp), tau.ctypes.data_as(dp),
+            n_obs, opt(obstacles, dp) if n_obs else None, float(margin), 0 if resume is None else 1, C.byref(n_draws),
+            opt(s1, dp), opt(s2, dp), opt(hits, lp), opt(clearance, dp), opt(length, dp))
+        self._chk(rc, "sample_posterior_stats")
+        mean = cov = None
+        if mom:
+            mean, cov = self.posterior_moments(n_draws.value, s1, s2, cov=n_draws.value >= 2)
+        return dict(n=n_draws.value, s1=s1, s2=s2, mean=mean, cov=cov, hits=hits, clearance=clearance, length=length)
+
+    @staticmethod
+    def posterior_moments(n, s1, s2, cov=True):
+        """(mean (n_queries, d), cov (n_queries, d, d) or None) of n draws from the sums sample_posterior_stats returns: mean = s1 / n,
+        cov = (S2 - n mean mean^T) / (n - 1).  Host arithmetic."""
+        s1, s2 = _f64(s1), _f64(s2)
+        nq, d = s1.shape
+        if s2.shape != (nq, d * (d + 1) // 2):
+            raise GpslamHipError("posterior_moments: s2 must be n_queries x d (d + 1) / 2")
+        dp = C.POINTER(C.c_double)
+        mean = np.zeros((nq, d))
+        P = np.zeros((nq, d, d)) if cov else None
+        rc = _sampling_stats_lib().gpslam_hip_posterior_moments(d, nq, int(n), s1.ctypes.data_as(dp), s2.ctypes.data_as(dp), mean.ctypes.data_as(dp),
+                                                                 None if P is None else P.ctypes.data_as(dp))
+        if rc < 0:
+            raise GpslamHipError("posterior_moments failed (%d): n must be at least 1, and 2 for the covariance" % rc)
+        return mean, P
 
     def run_gn(self, iters, timed=False):
         st = Stats()

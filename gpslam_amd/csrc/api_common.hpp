@@ -181,6 +181,11 @@ struct Sampling {
   // coefficients of every query, and the query slabs of a chunk
   DevBuf at_ptr, at_left, at_coef;
   DevBuf at_poses, at_vels;
+  // gpslam_hip_sample_posterior_stats: a call's q^ with the interpolators' tables it comes from, its obstacles, the per-query sums,
+  // and per chunk the clearance and segment slabs with the per-draw numbers they reduce to
+  DevBuf st_ref, st_left, st_coef, st_obs;
+  DevBuf st_s1, st_s2, st_hits;
+  DevBuf st_g, st_seg, st_part, st_clear, st_len;
 };
 
 // gpslam_hip_meas_noise_statistic / gpslam_hip_meas_predicted_covariances (meas_noise.hip): per kind the factors' order by left state

@@ -15,8 +15,15 @@
 // staged noise rows are n_noise_at wide -- k_ps_noise writes the bridge's normals behind the rows', one kernel and one arithmetic for
 // both -- the pose and velocity slabs are kept whether or not the caller asks for them, and ONE k_ps_bridge launch per chunk, behind
 // the chunk's last k_ps_emit, walks every run of queries of every draw of the chunk from that draw's own support states in the slabs.
+//
+// Statistics of those draws (include/gpslam_hip_sampling_stats.h): a second optional part (PsStats) behind the
+// first.  Once per call k_interp_query writes q^ of every query; per chunk k_ps_moments, behind the chunk's k_ps_bridge, walks the
+// chunk's draws of each query in order out of the query slab -- local coordinates around q^ into the running sums, clearances and
+// segment lengths into two draws x queries slabs -- and k_ps_paths reduces those slabs, a workgroup per draw and tile of queries and
+// level after level, to one clearance and one length per draw.  No
+// query slab goes to the host: per chunk the draws' clearances and lengths, at the end of the call the per-query sums.
 #include "api_common.hpp"
-#include "../../include/gpslam_hip_sampling_at.h"
+#include "../../include/gpslam_hip_sampling_stats.h"
 
 #include <cmath>
 
@@ -250,6 +257,136 @@ template <int MF> __global__ void __launch_bounds__(128) k_ps_bridge(PsBridge a)
   }
 }
 
+// where a pose's position sits in its row (gpslam_hip_sampling_stats.h): the first two coordinates, or the translation of SE(3)
+template <int MF> struct PsPos {
+  static constexpr int w = MF == POSE3 ? 3 : 2, at = MF == POSE3 ? 9 : 0;
+};
+
+// a pose row out of a slab: 16-byte loads where every row starts on 16 bytes (an even pose_dim), 8-byte loads elsewhere
+template <int PD> __device__ __forceinline__ void ps_row(const double *p, double *x) {
+  if constexpr (PD % 2 == 0) {
+#pragma unroll
+    for (int c = 0; c < PD; c += 2) {
+      const double2 v = *reinterpret_cast<const double2 *>(p + c);
+      x[c] = v.x; x[c + 1] = v.y;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < PD; c++) x[c] = p[c];
+  }
+}
+
+struct PsMoments {
+  const double *qposes;     // the chunk's query slab: draws x nq x pd (what k_ps_bridge wrote)
+  const double *ref;        // nq x pd: q^, the interpolated estimate
+  const double *obs;        // n_obs x (w + 1): centre, radius
+  int draws, nq, chart, n_obs;
+  double margin;
+  double *s1, *s2;          // the running sums, nq x d and nq x d (d + 1) / 2 (rows packed as PsBridge::Lq); both or neither
+  long long *hits;          // nq, or null
+  bool need_g;              // clearances wanted (for hits or for gslab)
+  double *gslab, *lslab;    // draws x nq: g_kq and |p_k,q+1 - p_k,q| (0 behind the last query); either may be null
+};
+// One work item per query: q^ and the query's sums in registers, the chunk's draws in order k = 0, 1, ... -- so a sum is the same
+// number however the call is cut into chunks or continued -- and no atomics: every sum has one owner.
+template <int MF> __global__ void __launch_bounds__(128) k_ps_moments(PsMoments a) {
+  constexpr int d = MTraits<MF>::d, pd = MTraits<MF>::pd, T = d * (d + 1) / 2;
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= a.nq) return;
+  const bool mom = a.s1 != nullptr;
+  double ref[pd], s1[d], s2[T];
+  long long hits = a.hits ? a.hits[q] : 0;
+  if (mom) ps_row<pd>(a.ref + (size_t)q * pd, ref);
+#pragma unroll
+  for (int c = 0; c < d; c++) s1[c] = mom ? a.s1[(size_t)q * d + c] : 0.0;
+#pragma unroll
+  for (int c = 0; c < T; c++) s2[c] = mom ? a.s2[(size_t)q * T + c] : 0.0;
+  for (int k = 0; k < a.draws; k++) {
+    const size_t at = (size_t)k * a.nq + q;
+    const double *P = a.qposes + at * pd;
+    double x[pd];
+    ps_row<pd>(P, x);
+    if (mom) {
+      double eta[d], Hd[1];
+      PoseFactors<double, MF, false>::prior(ref, x, a.chart, eta, Hd);     // Local(q^, q) in the handle's chart
+#pragma unroll
+      for (int r = 0; r < d; r++) {
+        s1[r] += eta[r];
+#pragma unroll
+        for (int c = 0; c <= r; c++) s2[r * (r + 1) / 2 + c] += eta[r] * eta[c];
+      }
+    }
+    if constexpr (MF != ROT3) {
+      constexpr int w = PsPos<MF>::w, p0 = PsPos<MF>::at;
+      if (a.need_g) {
+        double g = INFINITY;
+        for (int o = 0; o < a.n_obs; o++) {
+          const double *ob = a.obs + (size_t)o * (w + 1);
+          double r2 = 0.0;
+#pragma unroll
+          for (int c = 0; c < w; c++) { const double dx = x[p0 + c] - ob[c]; r2 += dx * dx; }
+          g = fmin(g, sqrt(r2) - ob[w]);
+        }
+        g -= a.margin;
+        if (a.gslab) a.gslab[at] = g;
+        if (g < 0.0) hits++;
+      }
+      if (a.lslab) {
+        double len = 0.0;
+        if (q + 1 < a.nq) {
+          double r2 = 0.0;
+#pragma unroll
+          for (int c = 0; c < w; c++) { const double dx = P[pd + p0 + c] - x[p0 + c]; r2 += dx * dx; }
+          len = sqrt(r2);
+        }
+        a.lslab[at] = len;
+      }
+    }
+  }
+  if (mom) {
+#pragma unroll
+    for (int c = 0; c < d; c++) a.s1[(size_t)q * d + c] = s1[c];
+#pragma unroll
+    for (int c = 0; c < T; c++) a.s2[(size_t)q * T + c] = s2[c];
+  }
+  if (a.hits) a.hits[q] = hits;
+}
+
+// entries of a row that one workgroup of k_ps_paths reduces: 16 per lane
+constexpr int kPsTile = 256 * 16;
+
+struct PsPaths {
+  const double *gin, *lin;          // draws x width: clearances and segment lengths, or the partial results of the level before
+  int width, parts;                 // parts = ceil(width / kPsTile)
+  double *gout, *lout;              // draws x parts: with parts == 1 the draws' clearance and length; either pair may be null
+};
+// One workgroup per (draw, tile of kPsTile entries): lane t takes the tile's entries t, t + 256, ... in ascending order, then a fixed
+// tree over the lanes in LDS; the host launches it again over the partial results until one is left per draw.  The tiles are cut
+// by the number of queries alone, so the order of every addition is the same wherever the draw sits in a chunk or a call.  (The
+// minimum is exact in any order.)  One workgroup per draw was measured first: at 1e6 states a chunk is one draw, and 256 lanes
+// walking 16 million entries took 27 ms per slab.
+__global__ void __launch_bounds__(256) k_ps_paths(PsPaths a) {
+  __shared__ double sm[256], sl[256];
+  const int t = threadIdx.x;
+  const size_t k = blockIdx.x / (unsigned)a.parts;
+  const int p = (int)(blockIdx.x - k * a.parts), q1 = min(a.width, (p + 1) * kPsTile);
+  double m = INFINITY, l = 0.0;
+  for (int q = p * kPsTile + t; q < q1; q += 256) {
+    if (a.gin) m = fmin(m, a.gin[k * a.width + q]);
+    if (a.lin) l += a.lin[k * a.width + q];
+  }
+  sm[t] = m; sl[t] = l;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) { sm[t] = fmin(sm[t], sm[t + s]); sl[t] += sl[t + s]; }
+    __syncthreads();
+  }
+  if (t == 0) {
+    if (a.gout) a.gout[k * a.parts + p] = sm[0];
+    if (a.lout) a.lout[k * a.parts + p] = sl[0];
+  }
+}
+
 // every refusal, before anything is launched
 int ps_guard(gpslam_hip_handle *h, const char *what) {
   int rc = need_compiled(h);
@@ -275,6 +412,16 @@ struct PsAt {
   int nq, nruns;
   double Lq[21];
   double *qposes, *qvels;   // the caller's outputs; either may be null
+};
+
+// the second optional part, with the first only: statistics of the draws at the query times (gpslam_hip_sample_posterior_stats).
+// q^, the obstacles and the starting sums are on the device (h->ps.st_ref, st_obs, st_s1, st_s2, st_hits) before ps_sample is called
+struct PsStats {
+  int n_obs;
+  double margin;
+  double *s1, *s2;          // the caller's outputs; any may be null (s1 and s2 together)
+  int64_t *hits;
+  double *clearance, *length;
 };
 
 // draws per chunk: the widest slab row decides (with queries: the noise row with the bridge's normals, the query poses)
@@ -306,9 +453,9 @@ struct PsOut {
 };
 
 // the draws, chunk by chunk, over the linearisation in place; at: the queries' part (null: gpslam_hip_sample_posterior, which
-// launches what it always launched)
+// launches what it always launched); st: the statistics' part (null: gpslam_hip_sample_posterior_at, likewise)
 int ps_draws(gpslam_hip_handle *h, const LaunchMode &m, int count, uint64_t seed, uint64_t first, const double *noise, const PsOut &o,
-             const PsAt *at = nullptr) {
+             const PsAt *at = nullptr, const PsStats *st = nullptr) {
   int rc;
   const int N = h->N, b = h->b, nl = h->nl, n_noise = ps_noise_dim(h), chunk = ps_chunk(h, count, at);
   const int ldn = n_noise + (at ? 2 * h->d * at->nq : 0);          // a staged noise row
@@ -322,6 +469,23 @@ int ps_draws(gpslam_hip_handle *h, const LaunchMode &m, int count, uint64_t seed
   if (o.lms && nl > 0) HIPCHK(h->ps.lms.reserve((size_t)chunk * nl * sizeof(double)));
   if (at) HIPCHK(h->ps.at_poses.reserve((size_t)chunk * wqp * sizeof(double)));
   if (at && at->qvels) HIPCHK(h->ps.at_vels.reserve((size_t)chunk * wqv * sizeof(double)));
+  PsMoments ma;
+  if (st) {
+    const size_t slab = (size_t)chunk * at->nq * sizeof(double);
+    if (st->clearance) HIPCHK(h->ps.st_g.reserve(slab));
+    if (st->length) HIPCHK(h->ps.st_seg.reserve(slab));
+    if (st->clearance) HIPCHK(h->ps.st_clear.reserve((size_t)chunk * sizeof(double)));
+    if (st->length) HIPCHK(h->ps.st_len.reserve((size_t)chunk * sizeof(double)));
+    ma.qposes = h->ps.at_poses.as<double>(); ma.ref = h->ps.st_ref.as<double>(); ma.obs = h->ps.st_obs.as<double>();
+    ma.nq = at->nq; ma.chart = h->cfg.chart; ma.n_obs = st->n_obs; ma.margin = st->margin;
+    ma.s1 = st->s1 ? h->ps.st_s1.as<double>() : nullptr; ma.s2 = st->s1 ? h->ps.st_s2.as<double>() : nullptr;
+    ma.hits = st->hits ? h->ps.st_hits.as<long long>() : nullptr;
+    ma.need_g = st->hits || st->clearance;
+    ma.gslab = st->clearance ? h->ps.st_g.as<double>() : nullptr; ma.lslab = st->length ? h->ps.st_seg.as<double>() : nullptr;
+    // k_ps_paths' partial results, level after level: the first level's behind each other, the second's behind those
+    const size_t p1 = (size_t)nblocks(at->nq, kPsTile), p2 = (size_t)nblocks((int)p1, kPsTile);
+    if (p1 > 1 && (st->clearance || st->length)) HIPCHK(h->ps.st_part.reserve(2 * (size_t)chunk * (p1 + p2) * sizeof(double)));
+  }
   PsPlace pa;
   pa.M = h->M; pa.Mc = h->Mc; pa.npri = h->lpri.count(); pa.ld = h->ld;
   pa.rowE = h->rowE.as<double>(); pa.rowCE = h->rowCE.as<double>();
@@ -371,6 +535,38 @@ int ps_draws(gpslam_hip_handle *h, const LaunchMode &m, int count, uint64_t seed
       }
       HIPCHK(hipGetLastError());
     }
+    if (st) {
+      // the chunk's draws into the per-query sums and the two slabs, one work item per query; then the slabs' rows reduced, tile by tile
+      ma.draws = nk;
+      const unsigned nb = (unsigned)nblocks(at->nq, 128);
+      switch (h->mf) {
+        case LINEAR2: k_ps_moments<LINEAR2><<<dim3(nb), dim3(128), 0, h->stream>>>(ma); break;
+        case LINEAR3: k_ps_moments<LINEAR3><<<dim3(nb), dim3(128), 0, h->stream>>>(ma); break;
+        case POSE2: k_ps_moments<POSE2><<<dim3(nb), dim3(128), 0, h->stream>>>(ma); break;
+        case ROT3: k_ps_moments<ROT3><<<dim3(nb), dim3(128), 0, h->stream>>>(ma); break;
+        case POSE3: k_ps_moments<POSE3><<<dim3(nb), dim3(128), 0, h->stream>>>(ma); break;
+        default: return fail(h, GPSLAM_E_UNSUPPORTED, "sample_posterior_stats: no reduction kernel for this manifold");
+      }
+      HIPCHK(hipGetLastError());
+      if (st->clearance || st->length) {
+        // level after level until one number per draw is left: the slabs, then partial results in the two halves of st_part by turns
+        const size_t p1 = (size_t)nblocks(at->nq, kPsTile);
+        double *part[2] = {h->ps.st_part.as<double>(), h->ps.st_part.as<double>() + 2 * (size_t)nk * p1};
+        PsPaths ta;
+        ta.gin = ma.gslab; ta.lin = ma.lslab; ta.width = at->nq;
+        for (int level = 0;; level++) {
+          ta.parts = nblocks(ta.width, kPsTile);
+          const bool last = ta.parts == 1;
+          double *dst = part[level & 1];
+          ta.gout = !st->clearance ? nullptr : last ? h->ps.st_clear.as<double>() : dst;
+          ta.lout = !st->length ? nullptr : last ? h->ps.st_len.as<double>() : dst + (size_t)nk * ta.parts;
+          k_ps_paths<<<dim3((unsigned)((size_t)nk * ta.parts)), dim3(256), 0, h->stream>>>(ta);
+          HIPCHK(hipGetLastError());
+          if (last) break;
+          ta.gin = ta.gout; ta.lin = ta.lout; ta.width = ta.parts;
+        }
+      }
+    }
     // the one read of a chunk: the pivot flag (sticky over the chunk's solves), then the slabs
     int flag = 0;
     HIPCHK(hipMemcpyAsync(&flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -382,12 +578,23 @@ int ps_draws(gpslam_hip_handle *h, const LaunchMode &m, int count, uint64_t seed
     if (o.lms && nl > 0) HIPCHK(hipMemcpyAsync(o.lms + (size_t)k0 * nl, h->ps.lms.p, (size_t)nk * nl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (at && at->qposes) HIPCHK(hipMemcpyAsync(at->qposes + (size_t)k0 * wqp, h->ps.at_poses.p, (size_t)nk * wqp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (at && at->qvels) HIPCHK(hipMemcpyAsync(at->qvels + (size_t)k0 * wqv, h->ps.at_vels.p, (size_t)nk * wqv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (st && st->clearance) HIPCHK(hipMemcpyAsync(st->clearance + k0, h->ps.st_clear.p, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (st && st->length) HIPCHK(hipMemcpyAsync(st->length + k0, h->ps.st_len.p, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  if (st) {
+    // the per-query sums, once
+    const size_t nq = (size_t)at->nq, d = (size_t)h->d;
+    if (st->s1) HIPCHK(hipMemcpyAsync(st->s1, h->ps.st_s1.p, nq * d * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (st->s1) HIPCHK(hipMemcpyAsync(st->s2, h->ps.st_s2.p, nq * (d * (d + 1) / 2) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (st->hits) HIPCHK(hipMemcpyAsync(st->hits, h->ps.st_hits.p, nq * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   return 0;
 }
 
-int ps_sample(gpslam_hip_handle *h, int count, uint64_t seed, uint64_t first, const double *noise, const PsOut &o, const PsAt *at = nullptr) {
+int ps_sample(gpslam_hip_handle *h, int count, uint64_t seed, uint64_t first, const double *noise, const PsOut &o, const PsAt *at = nullptr,
+              const PsStats *st = nullptr) {
   int rc;
   h->mg.invalidate();             // the solver's buffers, which the marginals' getters read, are rewritten below
   const size_t nE = (size_t)h->M * sizeof(double), nCE = (size_t)h->Mc * sizeof(double);
@@ -406,7 +613,7 @@ int ps_sample(gpslam_hip_handle *h, int count, uint64_t seed, uint64_t first, co
   {
     PsPriors guard(h);            // (back in place on every way out of this block)
     if (npri) guard.swap();
-    rc = ps_draws(h, m, count, seed, first, noise, o, at);
+    rc = ps_draws(h, m, count, seed, first, noise, o, at, st);
   }
   // the linearisation's own errors back into the tables: the handle is as a call of gpslam_hip_get_rows leaves it
   if (nE) HIPCHK(hipMemcpyAsync(h->rowE.p, save, nE, hipMemcpyDeviceToDevice, h->stream));
@@ -438,7 +645,7 @@ int ps_at_width(gpslam_hip_handle *h, int n_queries, const char *what) {
 }
 
 // what the bridge refuses on top of ps_guard, before anything is launched
-int ps_at_guard(gpslam_hip_handle *h, bool query_vels) {
+int ps_at_guard(gpslam_hip_handle *h, bool query_vels, const char *what = "sample_posterior_at") {
   const char *why = nullptr;
   bool own_qc = false;
   for (int32_t q : h->gp_q) own_qc = own_qc || q != 0;
@@ -446,7 +653,7 @@ int ps_at_guard(gpslam_hip_handle *h, bool query_vels) {
   else if (h->vw) why = "world-frame velocities (velocity_world: the interval's local variable differs)";
   else if (own_qc) why = "GP priors with a Qc of their own (gpslam_hip_add_gp_priors_qc): the bridge's noise is the handle's Qc";
   else if (query_vels && h->mf != LINEAR2 && h->mf != LINEAR3) why = "query_vels on a Lie group (GPSLAM_LINEAR2 / LINEAR3 only, as interpolate_velocities)";
-  if (why) return fail(h, GPSLAM_E_UNSUPPORTED, (std::string("sample_posterior_at: not supported on ") + why).c_str());
+  if (why) return fail(h, GPSLAM_E_UNSUPPORTED, (std::string(what) + ": not supported on " + why).c_str());
   return 0;
 }
 
@@ -489,9 +696,102 @@ int ps_at_upload(gpslam_hip_handle *h, int nq, const int32_t *left, const double
   return 0;
 }
 
+// what the statistics read on the device before the first draw: q^ of every query by the interpolators' own kernel over the
+// estimate, the obstacles, and the sums a continued call starts from (zeros otherwise)
+int ps_stats_upload(gpslam_hip_handle *h, int nq, const int32_t *left, const double *dt, const double *tau, const PsStats &st,
+                    const double *obstacles, bool accumulate) {
+  int rc;
+  const int d = h->d, pd = h->pd, w = h->mf == POSE3 ? 3 : 2;
+  std::vector<double> coef((size_t)nq * 4);
+  for (int q = 0; q < nq; q++) interp_coef(dt[q], tau[q], &coef[4 * (size_t)q]);
+  std::vector<int> li(left, left + nq);
+  if ((rc = upload(h, h->ps.st_left, li)) || (rc = upload(h, h->ps.st_coef, coef))) return rc;
+  HIPCHK(h->ps.st_ref.reserve((size_t)nq * pd * sizeof(double)));
+  HIPCHK(h->ps.st_obs.reserve(std::max<size_t>((size_t)st.n_obs * (w + 1), 1) * sizeof(double)));
+  if (st.n_obs > 0) HIPCHK(hipMemcpyAsync(h->ps.st_obs.p, obstacles, (size_t)st.n_obs * (w + 1) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  const size_t n1 = (size_t)nq * d * sizeof(double), n2 = (size_t)nq * (d * (d + 1) / 2) * sizeof(double), nh = (size_t)nq * sizeof(int64_t);
+  if (st.s1) {
+    HIPCHK(h->ps.st_s1.reserve(n1));
+    HIPCHK(h->ps.st_s2.reserve(n2));
+    if (accumulate) {
+      HIPCHK(hipMemcpyAsync(h->ps.st_s1.p, st.s1, n1, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(h->ps.st_s2.p, st.s2, n2, hipMemcpyHostToDevice, h->stream));
+    } else {
+      HIPCHK(hipMemsetAsync(h->ps.st_s1.p, 0, n1, h->stream));
+      HIPCHK(hipMemsetAsync(h->ps.st_s2.p, 0, n2, h->stream));
+    }
+  }
+  if (st.hits) {
+    HIPCHK(h->ps.st_hits.reserve(nh));
+    if (accumulate) HIPCHK(hipMemcpyAsync(h->ps.st_hits.p, st.hits, nh, hipMemcpyHostToDevice, h->stream));
+    else HIPCHK(hipMemsetAsync(h->ps.st_hits.p, 0, nh, h->stream));
+  }
+  QueryArgs<double> a;
+  a.pose = h->pose.as<double>(); a.vel = h->vel.as<double>(); a.stride = h->stride; a.count = nq;
+  a.left = h->ps.st_left.as<int>(); a.coef = h->ps.st_coef.as<double>(); a.out = h->ps.st_ref.as<double>(); a.out_H = nullptr;
+  a.vw = h->vw;
+  dispatch_mf(h->mf, [&](auto tag) { k_interp_query<double, decltype(tag)::value, false><<<dim3(nblocks(nq, 128)), dim3(128), 0, h->stream>>>(a); });
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));      // (the caller's arrays are read)
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gpslam_hip_sample_posterior_stats(gpslam_hip_handle *h, int32_t count, uint64_t seed, uint64_t first, const double *noise,
+                                      int32_t n_queries, const int32_t *left, const double *dt, const double *tau,
+                                      int32_t n_obstacles, const double *obstacles, double margin,
+                                      int32_t accumulate, int64_t *n_draws,
+                                      double *s1, double *s2, int64_t *hits, double *clearance, double *length) {
+  if (!h || count <= 0 || n_queries <= 0 || !left || !dt || !tau) return GPSLAM_E_INVALID;
+  if (!s1 && !s2 && !hits && !clearance && !length) return GPSLAM_E_INVALID;
+  if ((s1 == nullptr) != (s2 == nullptr)) return GPSLAM_E_INVALID;
+  if (n_obstacles < 0 || n_obstacles > 1024 || (n_obstacles > 0 && !obstacles)) return GPSLAM_E_INVALID;
+  if ((n_obstacles == 0) != (!hits && !clearance)) return GPSLAM_E_INVALID;
+  if (!(margin >= 0.0)) return GPSLAM_E_INVALID;
+  if ((s1 || hits) && !n_draws) return GPSLAM_E_INVALID;
+  if (accumulate && n_draws && *n_draws < 0) return GPSLAM_E_INVALID;
+  const char *what = "sample_posterior_stats";
+  int rc = ps_guard(h, what);
+  if (rc || (rc = ps_at_guard(h, false, what))) return rc;
+  if (h->mf == ROT3 && (hits || clearance || length))
+    return fail(h, GPSLAM_E_UNSUPPORTED, "sample_posterior_stats: hits, clearance and length are not supported on GPSLAM_ROT3 (a rotation has no position)");
+  const int w = h->mf == POSE3 ? 3 : 2;
+  for (int o = 0; o < n_obstacles; o++)
+    if (!(obstacles[(size_t)o * (w + 1) + w] >= 0.0))
+      return fail(h, GPSLAM_E_INVALID, ("sample_posterior_stats: obstacle " + std::to_string(o) + ": the radius must not be negative").c_str());
+  if ((rc = ps_at_width(h, n_queries, what)) < 0) return rc;
+  PsAt at;
+  at.qposes = nullptr; at.qvels = nullptr;
+  if ((rc = ps_at_upload(h, n_queries, left, dt, tau, at))) return rc;
+  const PsStats st{n_obstacles, margin, s1, s2, hits, clearance, length};
+  if ((rc = ps_stats_upload(h, n_queries, left, dt, tau, st, obstacles, accumulate != 0))) return rc;
+  if ((rc = ps_sample(h, count, seed, first, noise, PsOut{nullptr, nullptr, nullptr, nullptr}, &at, &st))) return rc;
+  if (n_draws) *n_draws = (accumulate ? *n_draws : 0) + count;
+  return 0;
+}
+
+int gpslam_hip_posterior_moments(int32_t d, int32_t n_queries, int64_t n_draws, const double *s1, const double *s2,
+                                 double *mean, double *cov) {
+  if (d <= 0 || n_queries < 0 || !s1 || !mean || (cov && !s2)) return GPSLAM_E_INVALID;
+  if (n_draws < 1 || (cov && n_draws < 2)) return GPSLAM_E_INVALID;
+  const double n = (double)n_draws;
+  const int T = d * (d + 1) / 2;
+  for (int q = 0; q < n_queries; q++) {
+    double *m = mean + (size_t)q * d;
+    for (int c = 0; c < d; c++) m[c] = s1[(size_t)q * d + c] / n;
+    if (!cov) continue;
+    for (int r = 0; r < d; r++)
+      for (int c = 0; c <= r; c++) {
+        const double v = (s2[(size_t)q * T + r * (r + 1) / 2 + c] - n * m[r] * m[c]) / (n - 1.0);
+        cov[((size_t)q * d + r) * d + c] = v;
+        cov[((size_t)q * d + c) * d + r] = v;
+      }
+  }
+  return 0;
+}
 
 int gpslam_hip_posterior_noise_dim(gpslam_hip_handle *h, int32_t *n_noise) {
   int rc = need_compiled(h);

@@ -38,6 +38,7 @@
 #include "../../include/gpslam_hip_noise.h"
 #include "../../include/gpslam_hip_sampling.h"
 #include "../../include/gpslam_hip_sampling_at.h"
+#include "../../include/gpslam_hip_sampling_stats.h"
 
 // boost::optional<Matrix&> -- the type of the reference's Jacobian arguments (gpslam/gp/GaussianProcessPriorPose3.h:60-64:
 // `boost::optional<gtsam::Matrix&> H1 = boost::none`).  Where Boost is installed its header is used; where it is not (this image), the
@@ -1523,6 +1524,59 @@ inline PosteriorDrawsAt<POSE> samplePosteriorAt(const NonlinearFactorGraph &grap
       out.queries[k].push_back(detail::VT<POSE>::un(std::vector<double>(r, r + s.pd)));
     }
   }
+  return out;
+}
+
+/// Statistics of those draws, reduced on the device (gpslam_hip_sample_posterior_stats; include/gpslam_hip_sampling_stats.h): no
+/// draw comes to the host.  Per query the mean and covariance of the draws' local coordinates around the interpolated estimate (the
+/// tangent Marginals::interpolatedCovariance speaks in) and the number of draws closer than `margin` to a spherical obstacle; per
+/// draw the smallest clearance over the queries and the length of the polyline through the query positions.  obstacles: rows of
+/// (centre, radius), the centre in 3-D for Pose3 and in the plane otherwise; may be empty.  Rot3 has no position: moments only.
+struct PosteriorStats {
+  int d = 0;
+  long long draws = 0;
+  std::vector<double> s1, s2;            // queries x d, queries x d (d + 1) / 2: the sums the moments come from
+  std::vector<double> mean, cov;         // queries x d, queries x d x d (cov empty with fewer than two draws)
+  std::vector<long long> hits;           // per query (empty without obstacles)
+  std::vector<double> clearance, length; // per draw (clearance empty without obstacles, length empty on Rot3); the share of
+                                         // clearance < 0 estimates the probability that the path collides
+};
+inline PosteriorStats samplePosteriorStats(const NonlinearFactorGraph &graph, const Values &values, const std::vector<Key> &left,
+                                           const std::vector<double> &dt, const std::vector<double> &tau, int count,
+                                           const std::vector<std::vector<double>> &obstacles = {}, double margin = 0.0, uint64_t seed = 0,
+                                           uint64_t first = 0) {
+  if (count <= 0) throw std::invalid_argument("samplePosteriorStats: count must be positive");
+  if (left.empty() || left.size() != dt.size() || left.size() != tau.size()) throw std::invalid_argument("samplePosteriorStats: size mismatch");
+  detail::Session s;
+  s.share_qc = true;          // (as samplePosteriorAt)
+  s.build(graph, values);
+  const size_t nq = left.size(), d = (size_t)s.d, w = s.manifold == GPSLAM_POSE3 ? 3 : 2;
+  std::vector<int32_t> idx(nq);
+  for (size_t q = 0; q < nq; q++) idx[q] = s.state_of(left[q]);
+  std::vector<double> obs;
+  for (const auto &o : obstacles) {
+    if (o.size() != w + 1) throw std::invalid_argument("samplePosteriorStats: an obstacle is a centre and a radius");
+    obs.insert(obs.end(), o.begin(), o.end());
+  }
+  const bool position = s.manifold != GPSLAM_ROT3, obst = !obstacles.empty();
+  PosteriorStats out;
+  out.d = s.d;
+  out.s1.assign(nq * d, 0.0);
+  out.s2.assign(nq * (d * (d + 1) / 2), 0.0);
+  std::vector<int64_t> hits(obst ? nq : 0);
+  if (obst) out.clearance.assign((size_t)count, 0.0);
+  if (position) out.length.assign((size_t)count, 0.0);
+  int64_t n = 0;
+  detail::check(gpslam_hip_sample_posterior_stats(s.h, count, seed, first, nullptr, (int32_t)nq, idx.data(), dt.data(), tau.data(),
+                                                  (int32_t)obstacles.size(), obst ? obs.data() : nullptr, margin, 0, &n, out.s1.data(), out.s2.data(),
+                                                  obst ? hits.data() : nullptr, obst ? out.clearance.data() : nullptr,
+                                                  position ? out.length.data() : nullptr), s.h, "sample_posterior_stats");
+  out.draws = (long long)n;
+  out.hits.assign(hits.begin(), hits.end());
+  out.mean.assign(nq * d, 0.0);
+  if (n >= 2) out.cov.assign(nq * d * d, 0.0);
+  if (gpslam_hip_posterior_moments(s.d, (int32_t)nq, n, out.s1.data(), out.s2.data(), out.mean.data(), n >= 2 ? out.cov.data() : nullptr) != 0)
+    throw std::runtime_error("samplePosteriorStats: posterior_moments failed");
   return out;
 }
 

@@ -31,10 +31,12 @@ LIB = os.path.join(LIBDIR, "libgpslam_hip.so")
 # only; include/gpslam_hip_qc.h), posterior sampling by perturbed solves (sampling.hip: fp64 only; include/gpslam_hip_sampling.h),
 # learning measurement noise from the marginals (meas_noise.hip: fp64 only; include/gpslam_hip_noise.h),
 # and the level-0 row and fused kernels with their launchers (level0.hip: the only unit that includes level0.hpp, so every form of
-# k_fused_level0, k_chunk_forward_rows and k_chunk_backward_rows is compiled once).
+# k_fused_level0, k_chunk_forward_rows and k_chunk_backward_rows is compiled once), and the segmented landmark elimination with
+# compile()'s plan for it (fatsep.hip: the only unit that includes fatsep.hpp, so every k_fs_* / k_fat_* kernel is compiled there, with
+# fp64 and with fp32 rows; the other units see fatsep_plan.hpp, the plan without a kernel).
 # A unit holds the kernels its own launch statements name; a header that launches none costs its includers no device code.
 SOURCES = ["api.hip", "api_impl64.hip", "api_impl32.hip", "level0.hip", "upper.hip", "marginals.hip", "marginals_clo.hip", "marginals_fs.hip", "closures.hip", "fixedlag.hip", "marginals_pairs.hip",
-           "dogleg.hip", "evidence.hip", "qc_learn.hip", "sampling.hip", "meas_noise.hip"]
+           "dogleg.hip", "evidence.hip", "qc_learn.hip", "sampling.hip", "meas_noise.hip", "fatsep.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"]
 # where a translation unit's project files live: read and hashed BEFORE hipcc starts (a unit that reads a project file from anywhere
 # else is refused: its contents as of the start of the compile are not known)

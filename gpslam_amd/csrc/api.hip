@@ -807,8 +807,7 @@ int gpslam_hip_fs_set_split(gpslam_hip_handle *h, int32_t rank, int32_t nranks, 
   h->mg.invalidate();
   return 0;
 }
-int gpslam_hip_fs_split_info(gpslam_hip_handle *h, int32_t out4[4]) { return GPS_BY_PRECISION(gpslam_hip_fs_split_info, h, out4); }
-int gpslam_hip_fs_set_top(gpslam_hip_handle *h, int32_t nb_top) { return GPS_BY_PRECISION(gpslam_hip_fs_set_top, h, nb_top); }
+// (gpslam_hip_fs_split_info and gpslam_hip_fs_set_top use nothing of a precision: fatsep.hip defines them)
 int gpslam_hip_fs_interface(gpslam_hip_handle *h, void **send, size_t *send_bytes, void **recv, size_t *recv_bytes) {
   return GPS_BY_PRECISION(gpslam_hip_fs_interface, h, send, send_bytes, recv, recv_bytes);
 }

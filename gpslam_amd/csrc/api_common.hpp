@@ -1,7 +1,8 @@
 // api_common.hpp -- what the translation units of the library's host side share (api.hip: the C ABI; api_impl64.hip / api_impl32.hip:
 // api_impl.inc + api_iterate.inc once per row precision; closures.hip, fixedlag.hip, the four marginals*.hip, dogleg.hip, evidence.hip,
-// qc_learn.hip, sampling.hip, meas_noise.hip): the handle and the host helpers.  This file launches no kernel, so including it compiles none: a unit holds the
-// kernels its own launch statements name (level0.hip: the level-0 row and fused forms, behind kernels.hpp's declarations).
+// qc_learn.hip, sampling.hip, meas_noise.hip, fatsep.hip): the handle and the host helpers.  This file launches no kernel, so including it compiles none: a unit holds the
+// kernels its own launch statements name (level0.hip: the level-0 row and fused forms, behind kernels.hpp's declarations; fatsep.hip: the
+// segmented landmark elimination, the one includer of fatsep.hpp -- everybody else sees fatsep_plan.hpp, the plan without a kernel).
 // The marginals' state is marginals.hpp's (h->mg); device buffers free themselves (devbuf.hpp: no list names them)
 // (round 3: api.hip was one 3.5-minute translation unit; the fp64 and fp32 halves compile side by side now)
 #pragma once
@@ -26,7 +27,7 @@
 #include "kernels.hpp"
 #include "closures.hpp"
 #include "marginals.hpp"
-#include "fatsep.hpp"
+#include "fatsep_plan.hpp"
 #include "upper.hpp"
 
 using namespace gps;
@@ -280,7 +281,7 @@ struct gpslam_hip_handle {
   // segment sharding
   DevBuf halo_add, iface_send, iface_recv, top_blk, top_x;
   DevBuf scal, flag, api_e, api_H;
-  // landmark elimination at scale (fatsep.hpp): segments + fat separators instead of the dense border
+  // landmark elimination at scale (fatsep_plan.hpp; fatsep.hip): segments + fat separators instead of the dense border
   FatSepPlan fs;
   DevBuf lm_gL;             // undamped landmark gradient of the segmented path (the dense path keeps it behind lm_S)
   Plan plan;                // compile(): which kernels serve this graph, in which form
@@ -351,6 +352,36 @@ void closures_collect(gpslam_hip_handle *h, int p, bool keep_z);
 int closures_add(gpslam_hip_handle *h);
 // row length of W = U [X | Z] (CloPass::ldw)
 inline int clo_ldw(const gpslam_hip_handle *h) { return 1 + h->nl + h->clo.nc; }
+
+// The segmented landmark elimination (fatsep.hip: the one unit that includes fatsep.hpp's kernels).  The Jacobian rows' type is chosen
+// inside, once per call, from the handle's precision; both precision namespaces and marginals_fs.hip call these.  fs_build: compile()'s
+// share -- segment plan, level sets of the cyclic reduction, buffers, the dynamic-LDS attributes of the handle's row type (touch_lo /
+// touch_hi: first / last state touched by the factors of each landmark).  fs_forward: segment interiors -> fat blocks -> the
+// cyclic-reduction levels, down to one block or to the two end blocks of a piece of a split chain (y_own: the sweep and the Schur
+// complements in two launches through THIS Y buffer, whatever the plan's choice).  fs_solve: the whole solve behind an assembly.  A
+// piece of a split chain: fs_pack_record behind fs_forward (the interface record into the send buffer), fs_split_solve once the
+// records of every piece are in (the top system, then the piece's backward half at h->ph_lambda).
+int fs_build(gpslam_hip_handle *h, const std::vector<int> &touch_lo, const std::vector<int> &touch_hi);
+int fs_forward(gpslam_hip_handle *h, double lambda, double *y_own = nullptr);
+int fs_solve(gpslam_hip_handle *h, double lambda);
+int fs_pack_record(gpslam_hip_handle *h);
+int fs_split_solve(gpslam_hip_handle *h);
+// ... and the launches that stand inside other steps, each on the stream it is given.  fs_lmprior_err: the landmark priors' error,
+// nbl partial sums (launch_other_factors; an fp32 handle's error pass is the fp64 half's, so the type of the sums is the caller's).
+// fs_lm_update: landmarks += dL and |dL|_inf folded into scal[slot] (launch_retract).  fs_mask_mul: dL with the landmarks a
+// neighbour piece counts zeroed, into fs.lm_tmp (trial_scalars).
+void fs_lmprior_err(gpslam_hip_handle *h, int nbl, double *partial, hipStream_t st);
+void fs_lmprior_err(gpslam_hip_handle *h, int nbl, float *partial, hipStream_t st);
+void fs_lm_update(gpslam_hip_handle *h, int slot, hipStream_t st);
+void fs_mask_mul(gpslam_hip_handle *h, const double *dL, hipStream_t st);
+// The segmented path sends the light factor kernels (launch_factors) and its own row-table kernels (fs_forward) to the handle's second
+// stream, underneath the chain's, only on graphs of at least this many states: everywhere else everything stays on one stream.  A/B of "never"
+// against "always" (scripts/ab_fork.py, wall clock of run_gn(20), ms per iteration): Plaza2 (4091 states) 0.152 / 0.192 -- its
+// timeline: k_lin 7 us beside k_meas 10 us, then 12 us of nothing before the reduction starts; config 5's SO(3) mix 3e4 0.100 /
+// 0.117, 1e5 0.208 / 0.213, 1e6 1.518 / 1.540; config 4's mix 1e5 0.885 / 0.916, 3e5 1.388 / 1.411, 1e6 3.019 / 2.997 -- joining two
+// streams costs more idle time (12 us and up) than the shorter of two concurrent kernels saves, and two kernels side by side slow each
+// other down: only the segmented landmark path (config 4's mix) at 1e6 states gains (0.7 %), and only it forks.
+constexpr int kForkMinStates = 524288;
 
 // State Gaussians (fixedlag.hip; fp64 only: compile() refuses them on an fp32 handle).  state_gauss_upload: compile()'s share (row0: the
 // first row of each factor in the full-width table).  state_gauss_eval: the rows [A | 0], their error entries (pass 0) and the error
@@ -489,6 +520,8 @@ template <typename F> void dispatch_fk(int fk, F &&f) {
 // force_sharded = 1 forces the sharded code path on a single segment (self-test of the exchange plumbing)
 bool sharded(const gpslam_hip_handle *h) { return h->cfg.nranks > 1 || h->cfg.force_sharded == 1; }
 bool has_right_rank(const gpslam_hip_handle *h) { return sharded(h) && h->cfg.rank < h->cfg.nranks - 1; }
+// a piece of a chain split at shared cut states (gpslam_hip_fs_set_split)
+bool split_piece(const gpslam_hip_handle *h) { return h->fs.active && h->fs.split; }
 
 // some measurement factor or closure carries a loss (noiseModel::Robust)
 bool any_robust(const gpslam_hip_handle *h) {

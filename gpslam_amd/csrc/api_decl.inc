@@ -9,8 +9,6 @@ int gpslam_hip_fs_lm_trial_phase1(gpslam_hip_handle *h, double lambda);
 int gpslam_hip_fs_lm_trial_phase2(gpslam_hip_handle *h, double *out6);
 int gpslam_hip_fs_phase1(gpslam_hip_handle *h, double lambda);
 int gpslam_hip_fs_phase2(gpslam_hip_handle *h, gpslam_hip_stats *st);
-int gpslam_hip_fs_set_top(gpslam_hip_handle *h, int32_t nb_top);
-int gpslam_hip_fs_split_info(gpslam_hip_handle *h, int32_t out4[4]);
 int gpslam_hip_get_between_pairs_weights(gpslam_hip_handle *h, double *w);
 int gpslam_hip_get_meas_weights(gpslam_hip_handle *h, int32_t kind, double *w);
 int gpslam_hip_get_rows(gpslam_hip_handle *h, int32_t *n_rows, double *rowLR, double *rowE, double *rowM, int32_t *rowLm);
@@ -39,4 +37,3 @@ int launch_assemble(gpslam_hip_handle *h, const LaunchMode &m, bool save_g, int 
 int launch_solve(gpslam_hip_handle *h, const LaunchMode &m, double lambda);
 int launch_retract(gpslam_hip_handle *h, const LaunchMode &m, int slot);
 int launch_meas_inspect(gpslam_hip_handle *h, int kind, int first, int count, void *out_e, void *out_J);
-int fs_forward(gpslam_hip_handle *h, double lambda, double *y_own = nullptr);

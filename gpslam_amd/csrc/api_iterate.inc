@@ -12,7 +12,6 @@ enum class Scheme {
   SHARDED,   // a segment of the chain: dense landmark border, interface records (nranks > 1 / force_sharded)
   SPLIT      // a piece of a chain split at shared cut states: fat separators (gpslam_hip_fs_set_split)
 };
-bool split_piece(const gpslam_hip_handle *h) { return h->fs.active && h->fs.split; }
 Scheme scheme(const gpslam_hip_handle *h) { return split_piece(h) ? Scheme::SPLIT : sharded(h) ? Scheme::SHARDED : Scheme::LOCAL; }
 int dist_nranks(const gpslam_hip_handle *h) { return split_piece(h) ? h->fs.nranks : h->cfg.nranks; }
 
@@ -121,7 +120,7 @@ struct DistErr {
 };
 
 // ---------------------------------------------------------------- the solve steps of a sharded handle (a split piece's: fs_split_phase1,
-// fs_split_solve in api_impl.inc)
+// in api_impl.inc, fs_split_solve in fatsep.hip)
 
 // phase 1: linearise, assemble, eliminate the local segment down to its separator -> interface record.  lm_trial: the rows are those
 // of the linearisation point (lm_begin) and the assembly also stores the gradient.
@@ -240,7 +239,7 @@ int trial_scalars(gpslam_hip_handle *h, const LaunchMode &m, double *out6) {
     const Real *gL = h->fs.active ? h->lm_gL.as<Real>() : h->lm_S.as<Real>() + (size_t)nl * h->R, *own = dL;
     if ((rc = launch_dot(h, dL, gL, nl, 5))) return rc;
     if (sc == Scheme::SPLIT) {
-      k_fs_mask_mul<Real><<<dim3(nblocks(nl, 256)), dim3(256), 0, h->stream>>>(dL, h->fs.d_lm_own.as<int>(), h->ld, nl, h->fs.lm_tmp.as<Real>());
+      fs_mask_mul(h, dL, h->stream);
       own = h->fs.lm_tmp.as<Real>();
     }
     if ((rc = launch_dot(h, own, dL, nl, 6))) return rc;
@@ -603,44 +602,7 @@ int gpslam_hip_lm_reject(gpslam_hip_handle *h) {
 // the caller knows the widest fat block of any piece.  Gauss-Newton: fs_phase1 -> all-gather of the records -> fs_phase2.
 // Levenberg-Marquardt (the caller's loop, as for the dense-border sharding above): gpslam_hip_lm_begin; per trial
 // fs_lm_trial_phase1(lambda) -> all-gather of the records -> fs_lm_trial_phase2(out6) -> all-reduce of out6 -> accept, or
-// gpslam_hip_lm_reject and a larger lambda.
-int gpslam_hip_fs_split_info(gpslam_hip_handle *h, int32_t out4[4]) {
-  int rc = need_compiled(h);
-  if (rc) return rc;
-  if (!out4 || !split_piece(h)) return GPSLAM_E_INVALID;
-  out4[0] = h->fs.NB; out4[1] = h->fs.K; out4[2] = h->fs.C; out4[3] = h->fs.nb_top;
-  return 0;
-}
-int gpslam_hip_fs_set_top(gpslam_hip_handle *h, int32_t nb_top) {
-  int rc = need_local(h);
-  if (rc) return rc;
-  FatSepPlan &p = h->fs;
-  if (!split_piece(h)) return fail(h, GPSLAM_E_INVALID, "fs_set_top: not a piece of a split chain (gpslam_hip_fs_set_split before compile)");
-  if (nb_top < p.NB || nb_top > kFatMax) return fail(h, GPSLAM_E_INVALID, "fs_set_top: the top block size must lie between this piece's fat block size and 128");
-  const int P = p.nranks, NT = nb_top;
-  const size_t NT2 = (size_t)NT * NT, RS = 3 * NT2 + 2 * NT;
-  p.nb_top = NT;
-  std::vector<int> elim, upd;
-  int nlinks = 0, endl = 0;
-  FatSepPlan::build_levels(P + 1, false, elim, upd, p.tlevels, p.ttop, nlinks, endl);
-  if (elim.empty()) elim.assign(6, 0);
-  if (upd.empty()) upd.assign(3, 0);
-  HIPCHK(upload_vec(h->stream, p.d_telim, elim));
-  HIPCHK(upload_vec(h->stream, p.d_tupd, upd));
-  HIPCHK(p.send.reserve(RS * sizeof(Real)));
-  HIPCHK(p.recv.reserve((size_t)P * RS * sizeof(Real)));
-  HIPCHK(p.tD.reserve((size_t)(P + 1) * NT2 * sizeof(Real)));
-  HIPCHK(p.tlink.reserve((size_t)std::max(nlinks, P) * NT2 * sizeof(Real)));
-  HIPCHK(p.tg.reserve((size_t)(P + 1) * NT * sizeof(Real)));
-  HIPCHK(p.tQ.reserve((size_t)(P + 1) * NT2 * sizeof(Real)));
-  HIPCHK(p.tS1.reserve((size_t)(P + 1) * NT2 * sizeof(Real)));
-  HIPCHK(p.tS2.reserve((size_t)(P + 1) * NT2 * sizeof(Real)));
-  HIPCHK(p.tsv.reserve((size_t)(P + 1) * 2 * NT * sizeof(Real)));
-  HIPCHK(p.tx.reserve((size_t)(P + 1) * NT * sizeof(Real)));
-  // (the dynamic-LDS attribute of k_fat_elim_mfma / k_fat_top was set to the largest fat block's size by compile(): fs_build)
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return 0;
-}
+// gpslam_hip_lm_reject and a larger lambda.  (gpslam_hip_fs_split_info and gpslam_hip_fs_set_top: fatsep.hip.)
 int gpslam_hip_fs_interface(gpslam_hip_handle *h, void **send, size_t *send_bytes, void **recv, size_t *recv_bytes) {
   int rc = need_piece(h, "fs_interface");
   if (rc) return rc;

@@ -1,7 +1,7 @@
 // marginals_fs.hip -- gpslam_hip_marginals on the segmented landmark path (fatsep.hpp; gpslam_hip_marginals_on_segments): the selected
 // inversion through the nested dissection.  I: interior states, F: fat variables (cut states and all landmarks); H_II is block diagonal
 // over the segments (A_s = L L^T along the chain, k_fs_factor), S = H_FF - H_FI H_II^-1 H_IF the block-tridiagonal fat chain.
-//   (a) the forward half at lambda = 0 (impl64::fs_forward with y_own: the solver's own launches, the sweep in its two-launch form
+//   (a) the forward half at lambda = 0 (fatsep.hip: fs_forward with y_own: the solver's own launches, the sweep in its two-launch form
 //       into the marginals' own Y): fac = [W | E], Y = L^-1 H[I_s, B_s], and per eliminated fat block m its factor L_m (Dfat),
 //       P = L_m^-1 H(m,l) (link) and Q = L_m^-1 H(m,r) (Qbuf);
 //   (b) Sigma_FF = S^-1, blocks Sigma_{k,k} and Sigma_{k,k+1}: the top block's inverse (k_mg_fs_top), then the cyclic-reduction levels
@@ -498,7 +498,7 @@ int marginals_fs(gpslam_hip_handle *h) {
   HIPCHK(hipMemsetAsync(h->mg.G.p, 0, gbytes, st));
   int rc;
   if ((rc = impl64::launch_factors(h, LaunchMode{}, 0, 0)) || (rc = impl64::launch_assemble(h, LaunchMode{}, false))) return rc;
-  if ((rc = impl64::fs_forward(h, 0.0, h->mg.G.as<double>()))) return rc;
+  if ((rc = fs_forward(h, 0.0, h->mg.G.as<double>()))) return rc;
   MgFsChain c;
   c.Dfat = p.Dfat.as<double>(); c.link = p.link.as<double>(); c.Qbuf = p.Qbuf.as<double>();
   c.SD = h->mg.fsD.as<double>(); c.SP = h->mg.fsP.as<double>(); c.NB = NB; c.flag = h->flag.as<int>();
@@ -506,11 +506,8 @@ int marginals_fs(gpslam_hip_handle *h) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mg_fs_level), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mg_fs_level_lds(kMgFsMaxNB)));
   k_mg_fs_top<<<dim3(1), dim3(kMgFsThreads), mg_fs_top_lds(NB), st>>>(c, p.top);
   for (int li = (int)p.levels.size() - 1; li >= 0; li--) {
-    const FatSepPlan::LevelHost &lv = p.levels[li];
-    FatLevel fl;
-    fl.elim = p.d_elim.as<int>() + (size_t)6 * lv.elim_off; fl.nelim = lv.nelim;
-    fl.upd = nullptr; fl.nupd = 0;
-    k_mg_fs_level<<<dim3(lv.nelim), dim3(kMgFsThreads), mg_fs_level_lds(NB), st>>>(c, fl);
+    const FatLevel fl = fat_level(p.levels[li], p.d_elim);
+    k_mg_fs_level<<<dim3(fl.nelim), dim3(kMgFsThreads), mg_fs_level_lds(NB), st>>>(c, fl);
   }
   HIPCHK(hipGetLastError());
   MgFsSeg s;

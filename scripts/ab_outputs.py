@@ -11,13 +11,16 @@ priors, an fp32 handle, one sharded rank through the phase calls, closures in on
 and border Gaussians.  On each graph: iterate_gn, get_rows, run_gn(4) (the pending update, the deferred sums), error, iterate_lm from
 the initial values, an iterate_lm whose every trial is rejected, the weights, linearize_meas, and the callers of the launchers in
 other translation units (marginals, log_determinant, iterate_dogleg).  A call the library refuses is recorded with its message.
---fork adds the one graph that forks onto the second stream (config 4 at 524288 states, one iteration)."""
+The segmented landmark elimination has a list of its own in cases() -- fp64 and fp32 rows, block sizes 6 and 12, the fused sweep and
+its two-launch form, the fat block size NB in each of its three ranges (asserted against segment_plan()) -- and run_split() takes a
+chain split in two pieces through the phase calls, in fp64 and in fp32.
+--fork adds the one graph that forks onto the second stream (config 4 at 524288 states, one iteration): launch_factors and fs_forward."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 
-FORK_STATES = 524288      # kForkMinStates (api_impl.inc)
+FORK_STATES = 524288      # kForkMinStates (the library's constant)
 
 
 def stats_row(st):
@@ -52,8 +55,25 @@ def pairs(N, K, seed):
 
 
 class Case:
-    def __init__(self, name, problem, kw=None, feed=None, after=None, mode="local", only_gn=False):
+    def __init__(self, name, problem, kw=None, feed=None, after=None, mode="local", only_gn=False, nb=None):
         self.name, self.problem, self.kw, self.feed, self.after, self.mode, self.only_gn = name, problem, kw or {}, feed, after, mode, only_gn
+        self.nb = nb      # segmented graphs: (lowest, highest) fat block size NB the plan must report
+
+
+def pose3_local_landmarks(N, L, half=12, seed=5):
+    """an SE(3) chain (block size 12) past L point landmarks, each ranged from the states within `half` of its closest approach"""
+    from gpslam_amd import synthetic as S
+    rng = np.random.default_rng(seed)
+    p = S.pose3_chain(N, seed=seed)
+    t = p["pose"][:, 9:12]
+    centre = ((np.arange(L) + 0.5) * (N / L)).astype(np.int64)
+    lmk = t[centre] + np.array([0.0, 4.0, 1.0]) + rng.standard_normal((L, 3))
+    idx = np.concatenate([np.arange(max(c - half, 0), min(c + half, N), 3) for c in centre]).astype(np.int32)
+    lm = np.concatenate([np.full(len(np.arange(max(c - half, 0), min(c + half, N), 3)), l) for l, c in enumerate(centre)]).astype(np.int32)
+    z = np.linalg.norm(lmk[lm] - t[idx], axis=1) + 0.05 * rng.standard_normal(len(idx))
+    p.update(landmarks=lmk + 0.1 * rng.standard_normal((L, 3)), lprior_idx=np.arange(L, dtype=np.int32), lprior=lmk.copy(), lprior_sig=np.full((L, 3), 1.0),
+             prange_idx=idx, prange_lm=lm, prange_z=z, prange_sigma=np.full(len(idx), 0.05))
+    return p
 
 
 def cases(gp, S, fork):
@@ -120,6 +140,35 @@ def cases(gp, S, fork):
                     dict(landmark_dim=2, rank=0, nranks=1, force_sharded=True), feed=one_rank, mode="sharded"))
     out.append(Case("segmented-pose2-600", lambda: S.pose2_local_landmarks_chain(600, window=100, seed=2),
                     dict(chart=gp.CHART_FIRST_ORDER, landmark_dim=2, force_segmented=True), feed=lambda p, s: (s.marginals_on_segments(), S.apply(p, s))[1]))
+    # The segmented landmark elimination (fatsep.hip), every launch of it at the smallest size that reaches it.  The graph above: block
+    # size 6 with fp64 rows, NB = 16 -- k_fs_factor_rows6, k_fs_gev, k_fs_sweep_syrk<6, 3>, k_fs_lm_terms, k_fs_fat_assemble,
+    # k_fat_elim_rows<16> / k_fat_update / k_fat_top / k_fat_back_rows<16>, k_fs_scatter, k_fs_rhs, k_fs_solve1; its landmark priors reach
+    # k_fs_lmprior_err in every error pass, its retractions k_fs_lm_update and k_fs_max_into, its marginals fs_forward through their own
+    # Y (k_fs_sweep, k_fs_syrk<7, 112>).
+    seg_feed = lambda p, s: (s.marginals_on_segments(), S.apply(p, s))[1]
+    seg_kw = dict(chart=gp.CHART_FIRST_ORDER, landmark_dim=2, force_segmented=True)
+    local600 = lambda L=None: S.pose2_local_landmarks_chain(600, L=L, window=100, seed=2)
+    out[-1].nb = (16, 16)
+    # ... with fp32 rows: the <float> instantiation of every kernel above but k_fs_factor_rows6 (the generic k_fs_factor<6> instead)
+    out.append(Case("segmented-fp32-pose2-600", local600, dict(precision=1, **seg_kw), feed=seg_feed, nb=(16, 16)))
+    # ... and with GPSLAM_PLAN_FS_TWO_LAUNCHES: k_fs_sweep and k_fs_syrk<7, 112> through the plan's Y in place of k_fs_sweep_syrk
+    out.append(Case("segmented-two-launches-pose2-600", local600, dict(plan=C.PLAN_FS_TWO_LAUNCHES, **seg_kw), feed=seg_feed, nb=(16, 16)))
+    # block size 12 (SE(3), point landmarks, plain ranges): the generic k_fs_factor<12>, k_fs_gev<12>, k_fs_sweep<12> and k_fs_syrk through
+    # Y, k_fs_rhs<12>, k_fs_solve1<12>
+    def plain_ranges(p, s):
+        s.marginals_on_segments()
+        S.apply(p, s)
+        s.add_range(p["prange_idx"], p["prange_lm"], p["prange_z"], p["prange_sigma"])
+        s.compile()
+        return s
+    out.append(Case("segmented-se3-130", lambda: pose3_local_landmarks(130, 8), dict(landmark_dim=3, force_segmented=True, segment_length=64), feed=plain_ranges, nb=(24, 24)))
+    # the fat block size NB in its three ranges (landmarks per window against a segment length of 128).  Up to 48: the graphs above.
+    # 52 - 80: k_fat_elim_mfma, k_fat_back_w4, and at NB = 52 k_fs_sweep_syrk<6, 7> (NCP = 112), at NB = 80 k_fs_syrk<17, 176>.  Above 80:
+    # k_fat_elim_wide_mfma and k_fs_syrk<20, 272> over two workgroups per segment
+    wide_kw = dict(segment_length=128, **seg_kw)
+    out.append(Case("segmented-nb52-pose2-600", lambda: local600(120), wide_kw, feed=seg_feed, nb=(52, 52)))
+    out.append(Case("segmented-nb80-pose2-300", lambda: S.pose2_local_landmarks_chain(300, L=130, window=100, seed=2), wide_kw, feed=seg_feed, nb=(80, 80)))
+    out.append(Case("segmented-nb92-pose2-400", lambda: S.pose2_local_landmarks_chain(400, L=170, window=100, seed=2), wide_kw, feed=seg_feed, nb=(92, 92)))
     out.append(Case("closure-se3-200", lambda: S.add_loop_closures(S.pose3_chain(200, seed=2), [[3, 196]], seed=8)))
     out.append(Case("closures-pose2-300", lambda: S.add_loop_closures(anchored(strip_landmarks(S.pose2_range_chain(300, seed=9))), [[3, 140], [299, 60], [61, 150]], seed=4)))
     passes = lambda p, s: (s.set_closure_passes(32), s.marginals_keep_closure_columns(), S.apply(p, s))[2]
@@ -184,6 +233,10 @@ def run_case(gp, S, c):
         return out
 
     (c.feed or S.apply)(p, s)
+    if c.nb:
+        plan = s.segment_plan()
+        assert plan["active"] == 1 and c.nb[0] <= plan["NB"] <= c.nb[1], (c.name, plan)
+        rec["segment_plan"] = np.array(list(plan.values()))
     pose0, vel0 = s.get_states()
     lm0 = s.get_landmarks() if s.L else None
     op("plan", lambda: np.array(list(s.plan_info().values())))
@@ -225,6 +278,58 @@ def run_case(gp, S, c):
     rec["refused"] = np.frombuffer("\n".join(log).encode(), dtype=np.uint8)
     s.close()
     return rec, log
+
+
+SPLIT = (("split-2-pieces-pose2-2000", 0), ("split-2-pieces-fp32-pose2-2000", 1))
+
+
+def run_split(gp, S, precision):
+    """A chain split in two pieces held by this process (two handles; the interface records copied between them as the all-gather
+    would): fs_split_info / fs_set_top, two Gauss-Newton iterations through fs_phase1 / fs_phase2 (k_fs_pack_record, then
+    k_fs_top_build, the top system through the reduction's own kernels, k_fs_top_take and the backward half), one fs_lm_trial step
+    that is kept and one that gpslam_hip_lm_reject takes back (k_fs_mask_mul in the trial's scalars)."""
+    from gpslam_amd import sharded
+    P = 2
+    problem = S.pose2_local_landmarks_chain(2000, L=100, window=200)
+    pieces, rec = [], {}
+    for r in range(P):
+        s = gp.ChainSolver(gp.POSE2, chart=gp.CHART_FIRST_ORDER, landmark_dim=2, precision=precision)
+        sharded.apply_split(sharded.split_local_problem(problem, r, P), s, r, P)
+        pieces.append(sharded.SplitSolver(s, r, P))
+    nb_top = max(sv.nb_local for sv in pieces)
+    for r, sv in enumerate(pieces):
+        sv.set_top(nb_top)
+        rec["split_info.%d" % r] = np.array(list(sv.backend.fs_split_info().values()))
+        sv.backend.launch_census(reset=True)
+
+    def exchange():
+        for sv in pieces:
+            rv = sv.recv.view(P, -1)
+            for k in range(P):
+                rv[k].copy_(pieces[k].send)
+
+    def trial(lam):
+        for sv in pieces:
+            sv.backend.fs_lm_trial_phase1(lam)
+        exchange()
+        return np.stack([sv.backend.fs_lm_trial_phase2() for sv in pieces])
+
+    for it in range(2):
+        rec["iterate%d" % it] = np.array(list(sharded.iterate_pieces(pieces).values()))
+    for sv in pieces:
+        sv.backend.lm_begin()
+    rec["trial_kept"] = trial(1e-3)
+    for sv in pieces:
+        sv.backend.lm_begin()
+    rec["trial_rejected"] = trial(1e2)
+    for sv in pieces:
+        sv.backend.lm_reject()
+    for r, sv in enumerate(pieces):
+        rec["final.%d.pose" % r], rec["final.%d.vel" % r] = sv.backend.get_states()
+        rec["final.%d.landmarks" % r] = sv.backend.get_landmarks()
+        rec["census.%d" % r] = np.array(list(sv.backend.launch_census().values()))
+        sv.backend.close()
+    return {k: np.ascontiguousarray(v) for k, v in rec.items()}
 
 
 def compare(a, b):
@@ -270,6 +375,11 @@ def main():
         lm = ["%s trials %d accepted %d" % (k, rec[k][7], rec[k][6]) for k in ("lm", "lm_rejecting") if k in rec]
         print("%-44s %3d arrays; census %s; %s%s" % (c.name, len(rec), {k: int(v) for k, v in cen.items() if v > 0 and k.startswith(("lin_", "flush", "gps_", "meas_", "retract"))},
                                                   "; ".join(lm), "".join("\n      refused: " + l for l in log)), flush=True)
+    for name, precision in SPLIT:
+        if only in name:
+            rec = run_split(gp, S, precision)
+            np.savez(os.path.join(out, name + ".npz"), **rec)
+            print("%-44s %3d arrays; fat block, fat blocks, segment length, top block of piece 0: %s" % (name, len(rec), list(rec["split_info.0"])), flush=True)
     return 0
 
 

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Is the device code of two builds the same?  compare_device_code.py LIB_A LIB_B [--arch gfx950] [--by-symbol]
+"""Is the device code of two builds the same?  compare_device_code.py LIB_A LIB_B [--arch gfx950] [--by-symbol [--renamed OLD=NEW]]
 
 LIB_A / LIB_B: two gpslam_amd/lib directories (obj/*.o and libgpslam_hip.so, as `python -m gpslam_amd.build` leaves them).
 Per object: the gfx950 code object is taken out of .hip_fatbin, and every kernel is compared by name, by the bytes of its code and
 by its metadata (registers, LDS, scratch: the amdhsa.kernels note).  Per symbol, not per file: the order of instantiation moves
 with the host code.  --by-symbol: kernels may move between objects (a refactor that gives a feature a translation unit of its own) --
 every kernel of the whole library is compared by name whichever object holds it, a kernel may neither appear nor vanish, and the
-moves are listed (kernel count per pair of object sets).  Also compares the C ABI (the exported gpslam_hip_* symbols) of the two libraries.  Exit status 1 on any difference.
+moves are listed (kernel count per pair of object sets); --renamed OLD=NEW says that LIB_A's kernel OLD is LIB_B's NEW (a template
+that became a plain kernel: same code, same metadata but for the name).  Also compares the C ABI (the exported gpslam_hip_* symbols) of the two libraries.  Exit status 1 on any difference.
 """
 import argparse
 import hashlib
@@ -70,6 +71,9 @@ def by_symbol(a, ta, tb):
                 per.setdefault(k, {})[o] = v
         libs.append(per)
     la, lb = libs
+    for old, new in (r.split("=") for r in a.renamed):      # compared, code and metadata, under its new name
+        la[new] = {o: (code, meta.replace(old, new)) for o, (code, meta) in la.pop(old).items()}      # (.name and .symbol carry it)
+        print("renamed: %s -> %s" % (old, new))
     moves = {}
     for k in sorted(set(la) | set(lb)):
         if k not in la or k not in lb:
@@ -105,6 +109,7 @@ def main():
     ap.add_argument("--arch", default="gfx950")
     ap.add_argument("--by-symbol", action="store_true", help="whole library, per kernel: kernels may have moved between objects")
     ap.add_argument("--verbose", action="store_true", help="--by-symbol: name the kernels that moved")
+    ap.add_argument("--renamed", action="append", default=[], metavar="OLD=NEW", help="--by-symbol: kernel OLD of LIB_A is kernel NEW of LIB_B (mangled names)")
     a = ap.parse_args()
     bad = 0
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:

@@ -184,7 +184,7 @@ def cyclic_reduction(Dfat, Ofat, gfat):
 
 
 def build_levels(K, keep_last):
-    """Level sets of the block cyclic reduction as FatSepPlan::build_levels (gpslam_amd/csrc/fatsep.hpp) forms them: every
+    """Level sets of the block cyclic reduction as FatSepPlan::build_levels (gpslam_amd/csrc/fatsep_plan.hpp) forms them: every
     level eliminates every other active block; keep_last: the last block is never eliminated (a piece of a split chain
     stops at its two end blocks).  Returns (levels, survivors): levels = list of lists of (m, l, r) with r = None when the
     eliminated block has no right neighbour."""
